@@ -8,12 +8,19 @@ Workload at every N (weak scaling): BASELINE.json configs[1] per GPU — 2562-ve
 GCN (20 layers x 300 hidden, cut 0.33 — the reference defaults, vision/train.py:375-386), bs = 64 per GPU,
 10 000-point Chamfer x 3 draws, fp32, Adam(lr 3e-4).  Synthetic seeded inputs: ellipsoid-surface
 ground-truth clouds, reference weight init.  ``value`` = (N * K iterations of bs 64) / wall time, inputs resident
-in HBM, barrier + synchronize on both sides, max over ranks.  Nothing on the timed (product) leg comes from ``tests/``
-or ``oracle/``.
+in HBM, barrier + synchronize on both sides, max over ranks.  ``ms_per_step`` = wall time of the timed steps / K.  Nothing on
+the timed (product) leg comes from ``tests/`` or ``oracle/``.
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else runs on the GPU.  ``--dump-outputs DIR``
+then writes what the last timed step computed (``loss``, ``verts`` = the predicted vertex positions, ``grad`` = the flat
+all-reduced gradient the optimizer consumed, ``params`` = the flat weights after its update) as float32 ``DIR/<name>.npy``,
+64 MB at most (an array over its share is replaced by a fixed, seeded sample of its elements); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 Extra objects on the JSON line — everything in them is measured IN THIS RUN (nothing is read from ``profiles/``):
 * ``step_ms``   — p10 / median / p90 of the per-iteration device time (one HIP event per iteration boundary on the
   compute stream, SURVEY §8d protocol) over the timed steps.
+Only with ``--full`` (each after the timed steps and the dump; their own ``--no-*`` / ``--*-steps`` options still apply):
 * ``roofline``  — the dominant kernel (fp32-MFMA per-vertex product, hidden x hidden): algorithmic
   2*M*300*300 flop per launch / mean launch duration measured with HIP events on the launch stream during
   extra (untimed) profiled steps, against the 157.3 TFLOP/s fp32 matrix peak (MI355X_MICROARCH.md).
@@ -63,10 +70,15 @@ def parse():
     p.add_argument("--layers", type=int, default=20)
     p.add_argument("--hidden", type=int, default=300)
     p.add_argument("--cloud", default="ellipsoid", choices=["ellipsoid", "cube"])
+    p.add_argument("--full", action="store_true",
+                   help="also run the auxiliary legs after the timed steps: roofline (profiled steps + PMC traffic), alt_modes, "
+                        "named_configs, cpu_baseline.  Off: set up, warm up, time --steps steps, print the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (loss, verts, grad, params) as float32 DIR/<name>.npy, 64 MB at most")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-budget", type=float, default=75.0, help="seconds of wall time for the cpu_baseline leg")
     p.add_argument("--no-traffic", action="store_true", help="skip the child rocprofv3 --pmc passes")
-    p.add_argument("--profile-steps", type=int, default=2)
+    p.add_argument("--profile-steps", type=int, default=2, help="profiled steps of the roofline leg (--full)")
     p.add_argument("--gemm-precision", default="fp32", choices=["fp32", "bf16", "bf16s", "fp32x3"],
                    help="bf16 = operand mode, bf16s = bf16 activation storage (BASELINE configs[3]/[4]), fp32x3 = fp32 products as "
                         "six bf16 MFMA passes on exactly split operands; NOT the headline")
@@ -361,6 +373,19 @@ def measure_traffic(batch, level, hidden, kernel_tag="rowgemmw_kernel<2>"):
         "FETCH_SIZE x2 + WRITE_SIZE (KiB), max over the launches of 2 stack fwd+bwd calls, measured in this run"
 
 
+def dump_outputs(path, arrays, budget=64 << 20):
+    """Each array as float32 ``path/<name>.npy``; one larger than its equal share of ``budget`` bytes is replaced by the
+    elements at a fixed, seeded sample of its flat indices (ascending), so the files stay comparable between builds."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = budget // len(arrays)
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        if x.nbytes > share:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, share // 4, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and (a.launcher == "spawn" or (a.launcher == "auto" and a.gpus > 1)):
@@ -382,6 +407,7 @@ def main():
     args = make_args(num_GCN_layers=a.layers, hidden_GCN_size=a.hidden, number_points=a.points, seed=0,
                      exp_type="bench", exp_id=f"rank{rank}", eval=False, epochs=1, patience=70, batch_size=a.batch,
                      gemm_precision=a.gemm_precision)
+    dump = os.path.abspath(a.dump_outputs) if a.dump_outputs else None
     os.chdir(os.environ.get("TMPDIR", "/tmp"))  # Engine writes config.json under ./experiments
     eng = train.Engine(args, loaders=((), ()))
     verts, faces = amesh.icosphere(a.level)
@@ -424,7 +450,10 @@ def main():
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
     t0 = time.perf_counter()
     marks[0].record()
+    last = {}
     for i in range(a.steps):
+        if dump is not None and i == a.steps - 1:   # the last step's vertex positions, as the encoder returns them
+            hook = eng.encoder.register_forward_hook(lambda mod, inp, res: last.update(verts=res[0]))
         loss = step(a.warmup + i)
         marks[i + 1].record()
     fence()
@@ -442,10 +471,16 @@ def main():
     step_ms = {"p10": pick(0.1), "median": pick(0.5), "p90": pick(0.9), "max": per_step[-1], "sum": sum(per_step), "n": len(per_step),
                "how": "one HIP event per iteration boundary on the compute stream (rank 0)"}
 
+    if dump is not None:
+        hook.remove()
+        if rank == 0:
+            dump_outputs(dump, {"loss": loss, "verts": last["verts"], "grad": eng.bucket.flat,
+                                "params": torch.cat([p.detach().reshape(-1) for p in params])})
+
     # roofline leg: per-launch device time of the MFMA kernels, HIP events on the launch stream
     L = lib.load()
     roof = None
-    if a.profile_steps > 0:
+    if a.full and a.profile_steps > 0:
         L.a3vt_profile_enable(1)
         for i in range(a.profile_steps):
             step(a.warmup + a.steps + i)
@@ -522,12 +557,12 @@ def main():
                    "early_started_in_backward_steps": eng.bucket.early_started_in_backward}
     if roof is not None:
         out["roofline"] = roof
-    if a.gemm_precision == "fp32" and a.alt_steps > 0:   # every rank runs it (the steps hold collectives); rank 0 reports
+    if a.full and a.gemm_precision == "fp32" and a.alt_steps > 0:   # every rank runs it (the steps hold collectives); rank 0 reports
         alt = alt_modes_leg(eng, img, charts, clouds, step, fence, a.alt_steps, world)
         out["alt_modes"] = alt
-    if rank == 0 and world == 1 and default_cfg and not a.no_named_configs:
+    if a.full and rank == 0 and world == 1 and default_cfg and not a.no_named_configs:
         out["named_configs"] = named_configs_leg(eng, dev, a.named_steps)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.level, a.layers, a.hidden, a.points, a.cpu_budget)
     if rank == 0:
         print(json.dumps(out))

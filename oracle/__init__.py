@@ -25,7 +25,7 @@ Pinning status
 * GCN / encoders / Deformation / adjacency / batch_sample (with injected samples) /
   trainer loss scaling: PINNED against the reference itself, imported in the build container
   (``tests/golden/make_golden.py`` → ``tests/golden/*.npz``; ``tests/test_oracle_vs_reference.py``
-  re-runs the comparison live whenever ``/root/reference`` is present).
+  holds the oracle to the reference's stored forward, loss and gradients, fixture g15).
 * Chamfer nearest-neighbour arithmetic, face areas, barycentric weights: these live in
   **PyTorch3D 0.5.0** (``README.md:33``; call sites ``utility/utils.py:20-23,164,179,207,212``), which is
   not vendored in the reference and not installable here, and the reference has no tests.

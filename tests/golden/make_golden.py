@@ -614,7 +614,49 @@ def g11():
     save("g11_loader_batch.npz", **out)
 
 
+G15_CASES = {"vision_g1": (False, False, 1), "touch_g2": (True, False, 2), "finger_g3": (True, True, 3)}
+G15_ADJ = {"touch_g5": (5, False), "finger_g5": (5, True), "touch_g1": (1, False)}
+
+
+def g15():
+    """The reference's Deformation (L=4, H=40) + Chamfer forward / backward on its own mesh files, with the reference's
+    global-RNG sampling (seed 5), for the three chart topologies of tests/test_oracle_vs_reference.py; and the reference's
+    fused adjacency + faces for the three grasp layouts that test compares the product CSR against."""
+    out = {}
+    for tag, (use_touch, finger, grasps) in G15_CASES.items():
+        torch.manual_seed(0)
+        a = NS(use_touch=use_touch, num_grasps=grasps, finger=finger, use_img=False, num_GCN_layers=4, hidden_GCN_size=40, cut=0.33)
+        info, verts = ref.utils.load_mesh_vision(a, OBJ)
+        net = ref.model.Deformation(info, verts, a)
+        B = 2
+        shape = (B, grasps, 25, 4) if finger else (B, grasps, 4, 25, 4)
+        tc = torch.cat((torch.randn(shape[:-1] + (3,)) * 0.1, torch.randint(0, 3, shape[:-1] + (1,)).float()), -1)
+        batch = {"img": torch.zeros(B, 1), "touch_charts": tc}
+        st = {k: v.detach().clone() for k, v in net.state_dict().items()}
+        out_r, mask_r = net(batch["img"], ref.model.prepare_mesh(batch, verts, a))
+        gt = torch.rand(B, 500, 3) * 0.3 - 0.15
+        torch.manual_seed(5)
+        loss_r = 9000 * ref.utils.chamfer_distance(out_r, info["faces"], gt, num=400).mean()
+        loss_r.backward()
+        rp, col, val = omesh.dense_to_csr(info["adj"].numpy())
+        out.update({f"{tag}_adj_rowptr": rp, f"{tag}_adj_col": col, f"{tag}_adj_val": val,
+                    f"{tag}_faces": info["faces"].numpy().astype(np.int32), f"{tag}_verts": verts.numpy(),
+                    f"{tag}_touch_charts": tc.numpy(), f"{tag}_gt": gt.numpy(), f"{tag}_verts_out": out_r.detach().numpy(),
+                    f"{tag}_mask": mask_r.numpy(), f"{tag}_loss": np.float32(loss_r.item())})
+        for k, v in st.items():
+            out[f"{tag}_w:{k}"] = v.numpy()
+        for k, p in net.named_parameters():
+            out[f"{tag}_g:{k}"] = p.grad.numpy()
+    for tag, (grasps, finger) in G15_ADJ.items():
+        info, _ = ref.utils.load_mesh_vision(NS(use_touch=True, num_grasps=grasps, finger=finger, use_img=False), OBJ)
+        rp, col, val = omesh.dense_to_csr(info["adj"].numpy())
+        out.update({f"{tag}_adj_rowptr": rp, f"{tag}_adj_col": col, f"{tag}_adj_val": val,
+                    f"{tag}_faces": info["faces"].numpy().astype(np.int32)})
+    out["pytorch3d_restated"] = np.bool_(True)
+    save("g15_oracle_vs_reference.npz", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15"]
     for w in which:
         globals()[w]()

@@ -337,7 +337,7 @@ def test_bench_under_torchrun_single_rank(cuda):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--batch", "8", "--layers", "3", "--points", "1000", "--no-cpu-baseline", "--no-traffic", "--profile-steps", "1"]
+           "--batch", "8", "--layers", "3", "--points", "1000", "--no-cpu-baseline", "--no-traffic", "--profile-steps", "1", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]
@@ -364,6 +364,36 @@ def test_bench_under_torchrun_single_rank(cuda):
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1"], capture_output=True,
                          text=True, timeout=300, env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))
     assert bad.returncode != 0 and "WORLD_SIZE" in (bad.stderr + bad.stdout)
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(cuda, tmp_path):
+    """A plain ``bench.py`` run (no ``--full``) times exactly ``--steps`` steps and runs no auxiliary leg; ``--dump-outputs``
+    writes the last timed step's loss, vertex positions, gradient and updated weights as float32, and a second run with the
+    same arguments (same seeded inputs) writes the same values."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--layers", "3", "--points", "1000"]
+    lines = []
+    for run in ("a", "b"):
+        res = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, env=env)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines.append(json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["step_ms"]["n"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert not {"roofline", "alt_modes", "named_configs", "cpu_baseline"} & set(d)
+    names = ("loss", "verts", "grad", "params")
+    out = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(x.dtype == np.float32 for x in out.values())
+    assert out["verts"].shape == (8, 2562, 3) and np.isfinite(out["verts"]).all()
+    assert float(out["loss"]) == d["config"]["final_loss"]
+    assert out["grad"].size == out["params"].size == d["rccl"]["bucket_bytes"] // 4
+    assert sum(x.nbytes for x in out.values()) <= 64 << 20
+    for n in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{n}.npy"), out[n], err_msg=n)
 
 
 def test_gradients_written_into_the_bucket_equal_the_autograd_path(cuda, tmp_path):

@@ -516,6 +516,32 @@ def test_bench_self_launch_command_line(monkeypatch):
     assert bench.self_launch(a) == 2                                      # refused: 4 asked, 2 visible
 
 
+def test_bench_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs``: every array as float32 ``<name>.npy``; one over its equal share of the byte budget is cut
+    to a fixed, seeded, ascending sample of its elements, the same in every run; a plain run's options stay lean."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(10000, dtype=torch.float64).reshape(100, 100)
+    arrays = {"loss": torch.tensor(1.5), "verts": torch.randn(4, 5, 3), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=3 * 4000)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert all(x.dtype == np.float32 for x in got.values())
+    assert got["loss"].shape == () and float(got["loss"]) == 1.5
+    np.testing.assert_array_equal(got["verts"], arrays["verts"].numpy())
+    s = got["big"]
+    assert s.shape == (1000,) and np.all(np.diff(s) > 0) and np.all(s == np.round(s)) and s.max() < 10000
+    for n in arrays:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{n}.npy"), got[n])
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") - 128 for n in arrays) <= 3 * 4000
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 4
+
+
 def test_library_adam_on_cpu_tensors_is_torch_adam():
     """a3vt_amd.optim.Adam (the trainer's optimizer, vision/train.py:64) IS a torch.optim.Adam: what its kernel does not take — here
     CPU parameters — goes through torch's own step, bit for bit, and the state_dict has torch's layout."""

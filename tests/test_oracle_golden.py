@@ -65,8 +65,8 @@ def test_g3_small_deformation_fwd_bwd(tag, use_touch):
     ch = og.prepare_mesh(torch.from_numpy(z["touch_charts"]), verts, 2, use_touch)
     out, mask = og.deformation_forward(st, {"adj": adj}, ch, use_touch, 3, 0.33)
     assert np.array_equal(mask.numpy(), z["mask"])
-    # Bit for bit on the machine that produced the fixture (same BLAS code path: tests/test_oracle_vs_reference.py asserts
-    # exact equality against the live reference there); another CPU may block its matmuls differently -> last-bit slack.
+    # Bit for bit on the machine that produced the fixture (same BLAS code path as the reference run that wrote it); another
+    # CPU may block its matmuls differently -> last-bit slack.
     np.testing.assert_allclose(out.detach().numpy(), z["verts_out"], rtol=0, atol=2e-6)
     samples = [(torch.from_numpy(z["face_idx"][r].astype(np.int64)), torch.from_numpy(z["u"][r]), torch.from_numpy(z["v"][r]))
                for r in range(3)]

@@ -6,11 +6,11 @@ R=${1:-r06}
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/refresh
 mkdir -p $O
-python bench.py > $O/${R}_bench_default.json 2> $O/bench.err
+python bench.py --full > $O/${R}_bench_default.json 2> $O/bench.err
 tail -c 700 $O/${R}_bench_default.json
-python bench.py --gemm-precision bf16s --no-cpu-baseline > $O/${R}_bench_bf16s.json 2>/dev/null; tail -c 400 $O/${R}_bench_bf16s.json
-python bench.py --gemm-precision bf16 --no-cpu-baseline > $O/${R}_bench_bf16_operand_mode.json 2>/dev/null; tail -c 400 $O/${R}_bench_bf16_operand_mode.json
-python bench.py --gemm-precision fp32x3 --no-cpu-baseline > $O/${R}_bench_fp32x3.json 2>/dev/null; tail -c 400 $O/${R}_bench_fp32x3.json
+python bench.py --full --gemm-precision bf16s --no-cpu-baseline > $O/${R}_bench_bf16s.json 2>/dev/null; tail -c 400 $O/${R}_bench_bf16s.json
+python bench.py --full --gemm-precision bf16 --no-cpu-baseline > $O/${R}_bench_bf16_operand_mode.json 2>/dev/null; tail -c 400 $O/${R}_bench_bf16_operand_mode.json
+python bench.py --full --gemm-precision fp32x3 --no-cpu-baseline > $O/${R}_bench_fp32x3.json 2>/dev/null; tail -c 400 $O/${R}_bench_fp32x3.json
 python tools/measure_protocol.py > $O/${R}_timing_protocol.json 2> $O/protocol.err; tail -c 400 $O/${R}_timing_protocol.json
 python tools/named_configs.py > $O/${R}_named_configs.jsonl 2> $O/named.err; cut -c 1-300 $O/${R}_named_configs.jsonl
 python tools/named_configs.py --precision bf16 >> $O/${R}_named_configs.jsonl 2>> $O/named.err
