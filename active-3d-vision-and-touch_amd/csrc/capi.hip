@@ -97,16 +97,22 @@ constexpr int kQuadCols = 160;   // quad-major columns of a hybrid layer output:
 static std::atomic<long long> g_path_counts[PATH_COUNT];
 void path_count(int which) { g_path_counts[which].fetch_add(1, std::memory_order_relaxed); }
 static int g_csr_algo = 0;       // 0 = by shape, 1 = half-wave ("rows"), 2 = channel-sliced where it fits, long rows included
-// A split the channel-sliced kernels of gcn_csrqs.hip take (a3vt_adj_split; P short enough for the slots a thread keeps)
-static bool split_usable(const a3vt_adj_split *sp, int n_vert, int cut_len) {
-  return sp && sp->rowptr && sp->col && sp->scale && sp->cls && sp->max_degree > 0 && sp->max_degree <= csrqs_max_degree() &&
-         csrqs_fits(n_vert, cut_len);
-}
 static SplitRef split_ref(const a3vt_adj_split *sp) {
   return sp ? SplitRef{sp->rowptr, sp->col, sp->scale, sp->cls} : SplitRef{nullptr, nullptr, nullptr, nullptr};
 }
-static bool use_csrq(int batch, int n_vert, int hidden, int cut_len, int gemm_bf16, int max_degree) {
-  if (gemm_bf16 == 1 || gemm_bf16 == 2) return false;   // the bf16 operand / storage modes keep the half-wave kernels (mode 3 stores fp32: as mode 0)
+// A split comes whole or not at all (include/a3vt.h).  The stack entry points refuse anything else before they launch, so
+// that behind them `split != nullptr` means all four arrays are there.
+static bool split_whole(const a3vt_adj_split *sp) {
+  const SplitRef r = split_ref(sp);
+  return !sp || (r.rowptr && r.col && r.scale && r.cls);
+}
+// A split the channel-sliced kernels of gcn_csrqs.hip take (P short enough for the slots a thread keeps)
+static bool split_usable(const a3vt_adj_split *sp, int n_vert, int cut_len) {
+  return sp && sp->max_degree > 0 && sp->max_degree <= csrqs_max_degree() && csrqs_fits(n_vert, cut_len);
+}
+static bool use_csrq(int batch, int n_vert, int hidden, int cut_len, int mode, int max_degree) {
+  // the bf16 operand / storage modes keep the half-wave kernels (GEMM_FP32X3 stores fp32: as GEMM_FP32)
+  if (mode == GEMM_BF16_OPERANDS || mode == GEMM_BF16_STORAGE) return false;
   // Rows longer than the eight index slots a thread keeps in registers fall back to per-lane CSR walks: on the fused
   // vision + touch graphs (mean degree 12-26, hub rows of ~1150) that made the step 108 ms where the half-wave kernels
   // take 64 — those graphs stay on the half-wave kernels unless the test hook forces them (they are correct, just slow).
@@ -157,6 +163,101 @@ static int reduce_bias_partials(const float *slab, size_t layer_stride, int nsla
 
 static inline int mask_ld(int hidden, int cut_len) { return pad4(cut_len) / 4 + (hidden + 3) / 4; }
 
+// Hub rows of a CSR (rows longer than csr_heavy_degree()): listed once into `slot`, then every aggregation of the call hands
+// them to whole workgroups.  *heavy = NULL when the degree bound rules them out.
+static int hub_rows(const int32_t *rowptr, int n_vert, int max_degree, float *slot, int32_t **heavy, hipStream_t s) {
+  *heavy = nullptr;
+  if (max_degree > 0 && max_degree <= csr_heavy_degree()) return 0;
+  *heavy = reinterpret_cast<int32_t *>(slot);
+  return launch_csr_heavy_list(rowptr, n_vert, *heavy, s);
+}
+
+// Weight images of the layers [i0, i1) of a stack, image i at dst + i * stride, up to kMaxImages layers per launch.
+// transpose = 1 (forward): W_i^T as [rowgemm_bt_rows(hidden)][ld of the layer's input]; transpose = 0 (backward): W_i zero
+// padded as [rowgemm_bt_rows(width of dX_i)][ld of hidden].  w0 / wh: the row widths of layer 0 / of the hidden layers on
+// that side.  kind: GEMM_FP32 (fp32 images: modes 0 and 1, and layer 0 of mode 3), GEMM_BF16_STORAGE (bf16 images, widths
+// in bf16) or GEMM_FP32X3 (three bf16 images per layer; hidden layers only).
+static int launch_stack_images(int kind, int transpose, const float *const *weights, int i0, int i1, int in_features,
+                               int hidden, int w0, int wh, float *dst, size_t stride, hipStream_t s) {
+  auto ld = [&](int w) { return kind == GEMM_BF16_STORAGE ? 2 * pad16(w / 2) : pad16(w); };
+  for (; i0 < i1; i0 += kMaxImages) {
+    WeightImages wi{};
+    wi.count = i1 - i0 < kMaxImages ? i1 - i0 : kMaxImages;
+    wi.dst = dst + stride * i0;
+    wi.dst_stride = stride;
+    wi.n = hidden;
+    wi.transpose = transpose;
+    int max_rows = 0, max_ld = kind == GEMM_FP32 && transpose ? ld(wh) : 0;   // (the fp32 forward grid spans the hidden width)
+    for (int j = 0; j < wi.count; ++j) {
+      const int w = i0 + j == 0 ? w0 : wh;
+      wi.w[j] = weights[i0 + j];
+      wi.k[j] = i0 + j == 0 ? in_features : hidden;
+      wi.rows[j] = rowgemm_bt_rows(transpose ? hidden : w);
+      wi.ld[j] = ld(transpose ? w : wh);
+      max_rows = wi.rows[j] > max_rows ? wi.rows[j] : max_rows;
+      max_ld = wi.ld[j] > max_ld ? wi.ld[j] : max_ld;
+    }
+    const int rc = kind == GEMM_FP32X3 ? launch_weight_images3(wi, s)
+                   : kind == GEMM_BF16_STORAGE ? launch_weight_images16(wi, max_rows, max_ld, s)
+                                               : launch_weight_images(wi, max_rows, max_ld, s);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// dW / db of the output layer (k inputs, 3 outputs) from the thin kernels' partial slabs
+static int reduce_output_grads(const float *dw_slab, const float *db_slab, int k, float *grad_w, float *grad_b, int acc,
+                               hipStream_t s) {
+  const size_t n = (size_t)k * 3;
+  if (int rc = launch_slab_reduce_za(dw_slab, thin_num_slabs(), n, n, n, grad_w, acc, s)) return rc;
+  return launch_slab_reduce_za(db_slab, thin_num_slabs(), 3, 3, 3, grad_b, acc, s);
+}
+
+// The path decisions of a stack call in modes 0, 1 and 3.  The forward and the backward both take them from here: they
+// must agree on the weight images and on the layout of the activations in the stash.
+//   Layer outputs are row-major [M][hidden] on the half-wave path.  On the channel-sliced path ("hybrid" rows) the block of
+// M * hidden floats holds columns [0, 160) quad-major [batch][40][n_vert] float4 — the aggregated channels written by the
+// aggregation kernel, the rest of the product kernel's first column group by its epilogue — followed by columns
+// [160, hidden) row-major [M][hidden - 160].  160 = ten 16-column tiles = the input tiles of two waves of dw_kernel and
+// ten whole K chunks of rowgemm_kernel: no tile or chunk straddles the two parts.  Every consumer reads either.
+struct StackPlan {
+  bool x3;        // mode 3: the products of hidden layers 1 .. L-2 on the split-operand kernels (gcn_gemm3.hip)
+  int omode;      // operand mode of every other product (the first layer, narrow or short stacks)
+  bool quad;      // hidden layers on the channel-sliced aggregation: hybrid rows
+  bool qsplit;    // ... through the split (a3vt_adj_split) rather than the CSR
+  int qcols;      // columns of a layer's output kept quad-major
+  int rm_ld;      // row stride of the row-major part
+  size_t rm_off;  // its offset inside a layer's block
+};
+// rec: the layout recorded with the stash (stash_layout_lookup: 1 / 0), or -1 to decide by shape
+static StackPlan stack_plan(int mode, int batch, int n_vert, int hidden, int num_layers, int cut_len, int max_degree,
+                            const a3vt_adj_split *split, int rec) {
+  StackPlan p{};
+  const size_t m = (size_t)batch * n_vert;
+  p.x3 = mode == GEMM_FP32X3 && num_layers > 2 && rowgemm3_stack_ok((long long)m, hidden, mask_ld(hidden, cut_len));
+  p.omode = mode == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;
+  // a usable split stands for "every row short": the hub and seam rows are gone from P
+  const bool split_ok = split_usable(split, n_vert, cut_len);
+  p.quad = num_layers > 1 &&
+           (rec >= 0 ? rec == 1 : use_csrq(batch, n_vert, hidden, cut_len, mode, split_ok ? csrq_max_degree() : max_degree));
+  p.qsplit = p.quad && split_ok;   // P and J are symmetric: the same image serves A^T
+  p.qcols = p.quad ? kQuadCols : 0;
+  p.rm_ld = hidden - p.qcols;
+  p.rm_off = m * p.qcols;
+  return p;
+}
+
+// The slot-major index image of the channel-sliced aggregation (none on the half-wave path): from the split when the plan
+// takes it, from the CSR otherwise
+static int launch_stack_ell(const StackPlan &p, const a3vt_adj_split *split, const int32_t *rowptr, const int32_t *col,
+                            const float *val, int n_vert, int32_t *ell, hipStream_t s) {
+  if (p.qsplit) {
+    const SplitRef r = split_ref(split);
+    return launch_csrqs_image(r.rowptr, r.col, r.scale, r.cls, n_vert, ell, s);
+  }
+  return p.quad ? launch_csrq_ell(rowptr, col, val, n_vert, ell, s) : 0;
+}
+
 static StackLayout stack_layout(int batch, int n_vert, int in_features, int hidden, int num_layers, int cut_len,
                                 int need_backward, int gemm_mode = 0) {
   StackLayout L{};
@@ -170,7 +271,7 @@ static StackLayout stack_layout(int batch, int n_vert, int in_features, int hidd
   };
   const int kmax = hidden > pad4(in_features) ? hidden : pad4(in_features);
   L.wt_stride = align_up((size_t)rowgemm_bt_rows(kmax) * pad16(kmax), 64);
-  if (gemm_mode == 3 && L.wt_stride < 3 * (size_t)kX3ImageFloats) L.wt_stride = 3 * (size_t)kX3ImageFloats;   // hi / mid / lo images (gcn_gemm3.hip)
+  if (gemm_mode == GEMM_FP32X3 && L.wt_stride < 3 * (size_t)kX3ImageFloats) L.wt_stride = 3 * (size_t)kX3ImageFloats;   // hi / mid / lo images (gcn_gemm3.hip)
   L.wt = take(L.wt_stride * (num_layers > 1 ? num_layers - 1 : 1));
   L.za = take(m * (cpad > 4 ? cpad : 4));
   L.z3 = take(2 * m * 4);
@@ -213,7 +314,7 @@ static int check_stack_dims(int ld_feats, int in_features, int num_layers, int h
 }
 
 
-// ---- bf16 STORAGE mode (gemm_bf16 == 2): scratch layout and the stack loops on the bf16 kernels (gcn_bf16s.hip) ----------
+// ---- bf16 STORAGE mode (GEMM_BF16_STORAGE): scratch layout and the stack loops on the bf16 kernels (gcn_bf16s.hip) ----------
 static inline int pad8(int n) { return (n + 7) & ~7; }
 // ReLU-sign bytes per row in this mode: the aggregated-channel bytes cover pad8(cut_len) columns, and the row length is
 // even so that the 2-byte groups of an 8-column epilogue store never straddle rows
@@ -271,6 +372,7 @@ static Stack16Layout stack16_layout(int batch, int n_vert, int in_features, int 
 
 static int check_stack16_dims(int num_layers, int hidden, int in_features) {
   if (num_layers < 2) { set_error("gcn_stack: the bf16 storage mode needs at least one hidden layer"); return -1; }
+  if (num_layers - 1 > kMaxImages) { set_error("gcn_stack: bf16 storage mode supports up to %d hidden layers", kMaxImages); return -1; }
   if (hidden > 304 || hidden % 4 != 0 || hidden < 16) { set_error("gcn_stack: bf16 storage mode: hidden=%d unsupported", hidden); return -1; }
   if (in_features > 600) { set_error("gcn_stack: in_features=%d > 600 unsupported", in_features); return -1; }
   if (in_features > 304 && in_features % 8 != 0) {
@@ -292,29 +394,11 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
   const int mld = mask_ld16(hidden, cut_len);
   const size_t mpad = (m + 31) / 32 * 32;
   using u16 = unsigned short;
-  int32_t *heavy = nullptr;
-  if (max_degree <= 0 || max_degree > csr_heavy_degree()) {
-    heavy = reinterpret_cast<int32_t *>(scratch + L.heavy);
-    if (int rc = launch_csr_heavy_list(rowptr, n_vert, heavy, s)) return rc;
-  }
-  if (num_layers - 1 > kMaxImages) { set_error("gcn_stack: bf16 storage mode supports up to %d hidden layers", kMaxImages); return -1; }
-  {
-    WeightImages wi{};
-    int max_ld = 0;
-    for (int i = 0; i + 1 < num_layers; ++i) {
-      wi.w[i] = weights[i];
-      wi.k[i] = i == 0 ? in_features : hidden;
-      wi.rows[i] = rowgemm_bt_rows(hidden);
-      wi.ld[i] = 2 * pad16((i == 0 ? L.ld0 : L.ldh) / 2);
-      max_ld = wi.ld[i] > max_ld ? wi.ld[i] : max_ld;
-    }
-    wi.dst = scratch + L.wt;
-    wi.dst_stride = L.wt_stride;
-    wi.n = hidden;
-    wi.count = num_layers - 1;
-    wi.transpose = 1;
-    if (int rc = launch_weight_images16(wi, rowgemm_bt_rows(hidden), max_ld, s)) return rc;
-  }
+  int32_t *heavy;
+  if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
+  if (int rc = launch_stack_images(GEMM_BF16_STORAGE, 1, weights, 0, num_layers - 1, in_features, hidden, L.ld0, L.ldh,
+                                   scratch + L.wt, L.wt_stride, s))
+    return rc;
   // the input rows in bf16: behind the hidden layers' rows in the stash when there is one (the backward reads them there)
   u16 *f16 = acts ? static_cast<u16 *>(acts) + (size_t)(num_layers - 1) * m * L.ldh : reinterpret_cast<u16 *>(scratch + L.feats16);
   if (int rc = launch_cvt_rows(feats, ld_feats, in_features, f16, L.ld0, (long long)m, s)) return rc;
@@ -347,7 +431,7 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
     g.maskb = mk;
     g.mld = mld;
     g.moff = L.cpad / 4;
-    g.bf16 = 2;
+    g.mode = GEMM_BF16_STORAGE;
     {
       ProfScope ps(PROF_GEMM_FWD, s);
       if (int rc = launch_rowgemm(g, EPI_FWD_HIDDEN, s)) return rc;
@@ -368,8 +452,8 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
   ProfScope pso(PROF_OUT, s);
   if (int rc = launch_thin16_fwd_product(x, ldx, hidden, weights[last], (long long)m, scratch + L.z3, s)) return rc;
   const SplitRef sref = split_ref(split);
-  return launch_csr3(scratch + L.z3, biases[last], rowptr, col, val, heavy, n_vert, batch, update, 3, s,
-                     split && split->rowptr ? &sref : nullptr, false);
+  return launch_csr3(scratch + L.z3, biases[last], rowptr, col, val, heavy, n_vert, batch, update, 3, s, split ? &sref : nullptr,
+                     false);
 }
 
 static int stack_bwd16(const float *feats, int ld_feats, int in_features, const float *const *weights, int num_layers,
@@ -387,11 +471,8 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
   const int last = num_layers - 1;
   using u16 = unsigned short;
   const u16 *acts16 = static_cast<const u16 *>(acts);
-  int32_t *heavyT = nullptr;
-  if (max_degreeT <= 0 || max_degreeT > csr_heavy_degree()) {
-    heavyT = reinterpret_cast<int32_t *>(scratch + L.heavy);
-    if (int rc = launch_csr_heavy_list(rowptrT, n_vert, heavyT, s)) return rc;
-  }
+  int32_t *heavyT;
+  if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
   // the stack's input in bf16: the forward left it behind the hidden layers' rows in the stash (a3vt_gcn_stack_stash_bytes)
   const u16 *f16 = acts16 + (size_t)last * m * L.ldh;
   (void)feats;
@@ -409,36 +490,20 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
     ProfScope pso(PROF_OUT, s);
     if (int rc = launch_pad3to4(grad_update, (long long)m, du4, s)) return rc;
     const SplitRef sref = split_ref(split);
-    if (int rc = launch_csr3(du4, nullptr, rowptrT, colT, valT, heavyT, n_vert, batch, res, 4, s,
-                             split && split->rowptr ? &sref : nullptr, true))
+    if (int rc = launch_csr3(du4, nullptr, rowptrT, colT, valT, heavyT, n_vert, batch, res, 4, s, split ? &sref : nullptr, true))
       return rc;
     const u16 *x = acts16 + (size_t)(last - 1) * m * L.ldh;
     if (int rc = launch_thin16_bwd_main(x, L.ldh, hidden, weights[last], res, grad_update, (long long)m, 1, ping[0], L.ldh,
                                         scratch + L.thin_dw_slab, scratch + L.thin_db_slab, s))
       return rc;
-    if (int rc = launch_slab_reduce_za(scratch + L.thin_dw_slab, thin_num_slabs(), (size_t)hidden * 3, (size_t)hidden * 3,
-                                       (size_t)hidden * 3, grad_weights[last], acc, s))
+    if (int rc = reduce_output_grads(scratch + L.thin_dw_slab, scratch + L.thin_db_slab, hidden, grad_weights[last],
+                                     grad_biases[last], acc, s))
       return rc;
-    if (int rc = launch_slab_reduce_za(scratch + L.thin_db_slab, thin_num_slabs(), 3, 3, 3, grad_biases[last], acc, s)) return rc;
   }
   // bf16 images Bt = W_i (zero padded) for dX_i = dZ W_i^T
-  {
-    WeightImages wi{};
-    int max_rows = 0;
-    for (int i = 0; i < last; ++i) {
-      wi.w[i] = weights[i];
-      wi.k[i] = i == 0 ? in_features : hidden;
-      wi.rows[i] = rowgemm_bt_rows(i == 0 ? ld_feats : L.ldh);
-      wi.ld[i] = 2 * pad16(L.ldh / 2);
-      max_rows = wi.rows[i] > max_rows ? wi.rows[i] : max_rows;
-    }
-    wi.dst = scratch + L.wt;
-    wi.dst_stride = L.wt_stride;
-    wi.n = hidden;
-    wi.count = last;
-    wi.transpose = 0;
-    if (int rc = launch_weight_images16(wi, max_rows, 2 * pad16(L.ldh / 2), s)) return rc;
-  }
+  if (int rc = launch_stack_images(GEMM_BF16_STORAGE, 0, weights, 0, last, in_features, hidden, ld_feats, L.ldh, scratch + L.wt,
+                                   L.wt_stride, s))
+    return rc;
   u16 *dza = reinterpret_cast<u16 *>(scratch + L.za);
   const int cpad = L.cpad, ldza = cpad > 8 ? cpad : 8;
   const size_t db_layer_stride = align_up((size_t)csr_bwd_num_slabs(batch, n_vert) * (cpad > 8 ? cpad : 8), 64);
@@ -499,7 +564,7 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
     r.ldb = pad16(L.ldh / 2);
     r.zeros = zeros;
     r.m = (int)m;
-    r.bf16 = 2;
+    r.mode = GEMM_BF16_STORAGE;
     if (i == 0) {
       r.n_store = ld_feats;
       r.c = grad_feats;
@@ -552,7 +617,13 @@ int a3vt_csr_validate(const int32_t *rowptr, const int32_t *col, int n_vert, int
 int a3vt_adj_split_validate(const int32_t *rowptr, const int32_t *col, const float *val, int n_vert,
                             const int32_t *p_rowptr, const int32_t *p_col, const float *scale, const uint8_t *cls) {
   A3VT_CHECK_ARG(rowptr && col && val && p_rowptr && p_col && scale && cls && n_vert > 0);
-  if (p_rowptr[0] != 0) { set_error("adj_split: p_rowptr[0]=%d", p_rowptr[0]); return -1; }
+  // p_rowptr first, whole: the row walks below (and the symmetry search into rows not yet walked) index p_col with it
+  if (p_rowptr[0] != 0 || p_rowptr[n_vert] > rowptr[n_vert]) {
+    set_error("adj_split: p_rowptr[0]=%d p_rowptr[n]=%d (the matrix has %d entries)", p_rowptr[0], p_rowptr[n_vert], rowptr[n_vert]);
+    return -1;
+  }
+  for (int i = 0; i < n_vert; ++i)
+    if (p_rowptr[i + 1] < p_rowptr[i]) { set_error("adj_split: p_rowptr not monotone at %d", i); return -1; }
   // the two classes, ascending
   int ns = 0, nc = 0;
   for (int i = 0; i < n_vert; ++i) {
@@ -639,7 +710,7 @@ size_t a3vt_gcn_stack_scratch_bytes(int batch, int n_vert, int in_features, int 
   // mode 2 has a layout of its own): a caller that sizes its scratch here may pass any gemm_bf16
   size_t most = 0;
   for (int mode = 0; mode <= 3; ++mode) {
-    if (mode == 2 && num_layers < 2) continue;
+    if (mode == GEMM_BF16_STORAGE && num_layers < 2) continue;
     const size_t b = a3vt_gcn_stack_scratch_bytes_mode(batch, n_vert, in_features, hidden, num_layers, cut_len, need_backward, mode);
     most = b > most ? b : most;
   }
@@ -651,7 +722,7 @@ size_t a3vt_gcn_stack_scratch_bytes_mode(int batch, int n_vert, int in_features,
   // (a size query never fails: sizes no stack call accepts give 0 — the layouts below divide by some of them)
   if (batch <= 0 || n_vert <= 0 || in_features <= 0 || hidden <= 0 || num_layers <= 0 || cut_len < 0 || gemm_bf16 < 0 || gemm_bf16 > 3)
     return 0;
-  if (gemm_bf16 == 2)
+  if (gemm_bf16 == GEMM_BF16_STORAGE)
     return stack16_layout(batch, n_vert, in_features, hidden, num_layers, cut_len, need_backward).total * sizeof(float);
   return stack_layout(batch, n_vert, in_features, hidden, num_layers, cut_len, need_backward, gemm_bf16).total * sizeof(float);
 }
@@ -662,7 +733,7 @@ int a3vt_gcn_stack_stash_bytes(int batch, int n_vert, int hidden, int num_layers
   *acts_bytes = *mask_bytes = 0;
   if (num_layers < 2) return 0;
   const size_t m = (size_t)batch * n_vert, mpad = (m + 31) / 32 * 32;
-  if (gemm_bf16 == 2) {
+  if (gemm_bf16 == GEMM_BF16_STORAGE) {
     // the hidden layers' bf16 rows, then the stack's INPUT rows in bf16 (the backward needs them for dW_0 and would otherwise
     // convert the fp32 features a second time; sized for the widest input a stack accepts: in_features <= 600), + slack for
     // 16-byte reads of the last row's tail
@@ -693,11 +764,11 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
   float *acts = static_cast<float *>(acts_v);
   A3VT_CHECK_ARG(feats && weights && biases && rowptr && col && val && scratch && update);
   A3VT_CHECK_ARG((acts == nullptr) == (masks == nullptr) || num_layers < 2);
-  A3VT_CHECK_ARG(n_vert > 0 && batch > 0);
-  A3VT_CHECK_ARG(gemm_bf16 >= 0 && gemm_bf16 <= 3);
+  A3VT_CHECK_ARG(n_vert > 0 && batch > 0 && split_whole(split));
+  A3VT_CHECK_ARG(gemm_bf16 >= GEMM_FP32 && gemm_bf16 <= GEMM_FP32X3);
   if (int rc = check_stack_dims(ld_feats, in_features, num_layers, hidden, cut_len)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (gemm_bf16 == 2)  // bf16 storage: `acts` holds bf16 rows (a3vt_gcn_stack_stash_bytes)
+  if (gemm_bf16 == GEMM_BF16_STORAGE)  // bf16 storage: `acts` holds bf16 rows (a3vt_gcn_stack_stash_bytes)
     return stack_fwd16(feats, ld_feats, in_features, weights, biases, num_layers, hidden, cut_len, rowptr, col, val,
                        max_degree, split, n_vert, batch, acts, masks, scratch, update, s);
   const float *zeros = zero_page();
@@ -708,83 +779,30 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
   const int mld = mask_ld(hidden, cut_len);
   const size_t mpad = (m + 31) / 32 * 32;
 
-  // the 3-channel aggregation of the output layer through the split (any P: its rows are walked from global memory)
-  const SplitRef sref = split_ref(split);
-  const SplitRef *sp3 = split && split->rowptr && split->col && split->scale && split->cls ? &sref : nullptr;
-  // hub rows (if any): listed once, then every layer's aggregation hands them to whole workgroups
-  int32_t *heavy = nullptr;
-  if (max_degree <= 0 || max_degree > csr_heavy_degree()) {
-    heavy = reinterpret_cast<int32_t *>(scratch + L.heavy);
-    if (int rc = launch_csr_heavy_list(rowptr, n_vert, heavy, s)) return rc;
-  }
-  // Gemm mode 3 ("fp32x3", gcn_gemm3.hip): the hidden-layer products whose shape the split-operand kernels take run there;
-  // everything else of the call (the first layer, narrow or short stacks) on the exact fp32 kernels.
-  const bool x3 = gemm_bf16 == 3 && rowgemm3_stack_ok((long long)m, hidden, mask_ld(hidden, cut_len));
-  const int omode = gemm_bf16 == 1 ? 1 : 0;   // operand mode of the kernels shared with modes 0 / 1
-  // transposed, zero-padded weight images of all hidden layers (one launch)
-  const bool batched_images = num_layers - 1 <= kMaxImages;
-  if (x3) {   // layers 1 .. L-2 as three bf16 images each; layer 0 (K = in_features) keeps its fp32 image
-    for (int i0 = 1; i0 + 1 < num_layers; i0 += kMaxImages) {
-      WeightImages w3{};
-      const int cnt = num_layers - 1 - i0 < kMaxImages ? num_layers - 1 - i0 : kMaxImages;
-      for (int j = 0; j < cnt; ++j) {
-        w3.w[j] = weights[i0 + j];
-        w3.k[j] = hidden;
-      }
-      w3.dst = scratch + L.wt + L.wt_stride * i0;
-      w3.dst_stride = L.wt_stride;
-      w3.n = hidden;
-      w3.count = cnt;
-      w3.transpose = 1;
-      if (int rc = launch_weight_images3(w3, s)) return rc;
-    }
-  }
-  if (batched_images && num_layers > 1) {
-    WeightImages wi{};
-    for (int i = 0; i + 1 < (x3 ? 2 : num_layers); ++i) {
-      wi.w[i] = weights[i];
-      wi.k[i] = i == 0 ? in_features : hidden;
-      wi.rows[i] = rowgemm_bt_rows(hidden);
-      wi.ld[i] = pad16(i == 0 ? ld_feats : hidden);
-    }
-    wi.dst = scratch + L.wt;
-    wi.dst_stride = L.wt_stride;
-    wi.n = hidden;
-    wi.count = x3 ? 1 : num_layers - 1;
-    wi.transpose = 1;
-    if (int rc = launch_weight_images(wi, rowgemm_bt_rows(hidden), pad16(ld_feats > hidden ? ld_feats : hidden), s)) return rc;
-  }
-
-  // a usable split stands for "every row short": the hub and seam rows are gone from P
-  const bool split_ok = split_usable(split, n_vert, cut_len);
-  const bool quad = use_csrq(batch, n_vert, hidden, cut_len, gemm_bf16, split_ok ? csrq_max_degree() : max_degree) && num_layers > 1;
-  const bool qsplit = quad && split_ok;
-  if (num_layers > 1) path_count(quad ? PATH_STACK_QUAD : PATH_STACK_ROWS);
-  if (qsplit) path_count(PATH_STACK_SPLIT);
-  if (num_layers > 1) stash_layout_record(masks, quad);
+  int32_t *heavy;
+  if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
+  const StackPlan P = stack_plan(gemm_bf16, batch, n_vert, hidden, num_layers, cut_len, max_degree, split, -1);
+  const int qcols = P.qcols, rm_ld = P.rm_ld;
+  const size_t rm_off = P.rm_off;
+  // transposed, zero-padded weight images of the hidden layers; mode 3: layers 1 .. L-2 as three bf16 images each, layer 0
+  // (K = in_features) keeps its fp32 image
+  if (P.x3)
+    if (int rc = launch_stack_images(GEMM_FP32X3, 1, weights, 1, num_layers - 1, in_features, hidden, ld_feats, hidden,
+                                     scratch + L.wt, L.wt_stride, s))
+      return rc;
+  if (int rc = launch_stack_images(GEMM_FP32, 1, weights, 0, P.x3 ? 1 : num_layers - 1, in_features, hidden, ld_feats, hidden,
+                                   scratch + L.wt, L.wt_stride, s))
+    return rc;
+  if (num_layers > 1) path_count(P.quad ? PATH_STACK_QUAD : PATH_STACK_ROWS);
+  if (P.qsplit) path_count(PATH_STACK_SPLIT);
+  if (num_layers > 1) stash_layout_record(masks, P.quad);
   int32_t *ell = reinterpret_cast<int32_t *>(scratch + L.ell);
-  if (qsplit) {
-    if (int rc = launch_csrqs_image(split->rowptr, split->col, split->scale, split->cls, n_vert, ell, s)) return rc;
-  } else if (quad) {
-    if (int rc = launch_csrq_ell(rowptr, col, val, n_vert, ell, s)) return rc;
-  }
-  // Layer outputs.  Row-major [M][hidden] on the half-wave path; on the channel-sliced path ("hybrid" rows) the block of
-  // M * hidden floats holds columns [0, 160) quad-major [batch][40][n_vert] float4 — the aggregated channels written by
-  // the aggregation kernel, the rest of the product kernel's first column group by its epilogue — followed by columns
-  // [160, hidden) row-major [M][hidden - 160].  160 = ten 16-column tiles = the input tiles of two waves of dw_kernel
-  // and ten whole K chunks of rowgemm_kernel: no tile or chunk straddles the two parts.  Every consumer reads either.
-  const int qcols = quad ? kQuadCols : 0;                    // columns of a layer's output kept quad-major
-  const int rm_ld = hidden - qcols;                          // row stride of the row-major part
-  const size_t rm_off = m * qcols;                           // its offset inside a layer's block
+  if (int rc = launch_stack_ell(P, split, rowptr, col, val, n_vert, ell, s)) return rc;
   const float *x = feats, *xq = nullptr;                     // x: pre-offset so that x + row * ldx + col is column col
   int ldx = ld_feats;
   for (int i = 0; i + 1 < num_layers; ++i) {
     const int k = i == 0 ? ld_feats : hidden;       // K walked by the kernel (pad columns of feats are zero)
-    const int kin = i == 0 ? in_features : hidden;  // rows of W_i
-    float *wt = scratch + L.wt + L.wt_stride * i;
-    const bool l3 = x3 && i > 0;   // this layer's product on the split-operand kernel
-    if (!batched_images && !l3)
-      if (int rc = launch_transpose_pad(weights[i], kin, hidden, wt, rowgemm_bt_rows(hidden), pad16(k), s)) return rc;
+    const bool l3 = P.x3 && i > 0;   // this layer's product on the split-operand kernel
     float *y = acts ? acts + (size_t)i * m * hidden : scratch + L.ping[i & 1];
     RowGemmArgs g{};
     g.a0 = g.a1 = x;
@@ -796,7 +814,7 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
       g.a0q_nvert = n_vert;
       g.a0q_quads = qcols / 4;
     }
-    g.bt = wt;
+    g.bt = scratch + L.wt + L.wt_stride * i;
     g.ldb = pad16(k);
     g.zeros = zeros;
     g.m = (int)m;
@@ -811,8 +829,8 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
     g.maskb = mk;
     g.mld = mld;
     g.moff = cpad / 4;
-    g.bf16 = l3 ? 3 : omode;
-    if (quad) {   // raw columns [0, cpad) leave the product quad-major, for the channel-sliced aggregation;
+    g.mode = l3 ? GEMM_FP32X3 : P.omode;
+    if (P.quad) {   // raw columns [0, cpad) leave the product quad-major, for the channel-sliced aggregation;
       g.zq_nvert = n_vert;   // activated columns [cpad, 160) quad-major into the layer's output
       g.zq_quads = cpad / 4;
       g.yq = y;
@@ -823,10 +841,10 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
       ProfScope ps(PROF_GEMM_FWD, s);
       if (int rc = launch_rowgemm(g, EPI_FWD_HIDDEN, s)) return rc;
     }
-    if (quad) {
+    if (P.quad) {
       uint8_t *sq = masks ? masks + (size_t)(num_layers - 1) * mpad * mld + (size_t)i * signq_stride(m, cut_len) : nullptr;
       ProfScope psa(PROF_AGG, s);
-      if (qsplit) {
+      if (P.qsplit) {
         if (int rc = launch_csrqs_fwd(scratch + L.za, biases[i], cut_len, ell, n_vert, batch, y, qcols / 4, sq, 1, s)) return rc;
       } else if (int rc = launch_csrq_fwd(scratch + L.za, biases[i], cut_len, rowptr, col, val, heavy, ell, n_vert, batch, y, qcols / 4, sq, 1, s)) {
         return rc;
@@ -842,8 +860,10 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
   }
   const int klast = num_layers == 1 ? in_features : hidden;
   ProfScope pso(PROF_OUT, s);
+  // the 3-channel aggregation of the output layer through the split (any P: its rows are walked from global memory)
+  const SplitRef sref = split_ref(split);
   return launch_thin_fwd(x, ldx, klast, weights[num_layers - 1], biases[num_layers - 1], rowptr, col, val, heavy, n_vert,
-                         batch, scratch + L.z3, update, xq, qcols / 4, s, sp3);
+                         batch, scratch + L.z3, update, xq, qcols / 4, s, split ? &sref : nullptr);
 }
 
 int a3vt_gcn_stack_bwd(const float *feats, int ld_feats, int in_features, const float *const *weights,
@@ -881,13 +901,13 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
   const float *acts = static_cast<const float *>(acts_v);
   (void)biases; (void)rowptr; (void)col; (void)val;
   A3VT_CHECK_ARG(feats && weights && rowptrT && colT && valT && grad_update && grad_weights && grad_biases);
-  A3VT_CHECK_ARG(grad_feats && scratch && n_vert > 0 && batch > 0);
-  A3VT_CHECK_ARG(gemm_bf16 >= 0 && gemm_bf16 <= 3);
+  A3VT_CHECK_ARG(grad_feats && scratch && n_vert > 0 && batch > 0 && split_whole(split));
+  A3VT_CHECK_ARG(gemm_bf16 >= GEMM_FP32 && gemm_bf16 <= GEMM_FP32X3);
   A3VT_CHECK_ARG(num_layers == 1 || acts != nullptr);
   A3VT_CHECK_ARG(num_layers <= 2 || masks != nullptr);
   if (int rc = check_stack_dims(ld_feats, in_features, num_layers, hidden, cut_len)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (gemm_bf16 == 2)
+  if (gemm_bf16 == GEMM_BF16_STORAGE)
     return stack_bwd16(feats, ld_feats, in_features, weights, num_layers, hidden, cut_len, rowptrT, colT, valT,
                        max_degreeT, split, n_vert, batch, acts, masks, grad_update, grad_weights, grad_biases, grad_feats,
                        scratch, acc, s);
@@ -901,29 +921,16 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
   const int last = num_layers - 1;
 
   const SplitRef sref = split_ref(split);
-  const SplitRef *sp3 = split && split->rowptr && split->col && split->scale && split->cls ? &sref : nullptr;
-  // hub rows of A^T (if any): listed once for every aggregation of this call
-  int32_t *heavyT = nullptr;
-  if (max_degreeT <= 0 || max_degreeT > csr_heavy_degree()) {
-    heavyT = reinterpret_cast<int32_t *>(scratch + L.heavy);
-    if (int rc = launch_csr_heavy_list(rowptrT, n_vert, heavyT, s)) return rc;
-  }
-
+  int32_t *heavyT;
+  if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
   // the layout the forward left in this stash (recorded by a3vt_gcn_stack_fwd); a stash this library did not write: by shape
-  const int rec = stash_layout_lookup(masks);
-  const bool quad = masks != nullptr && num_layers > 1 &&
-                    (rec >= 0 ? rec == 1 : use_csrq(batch, n_vert, hidden, cut_len, gemm_bf16,
-                                                    split_usable(split, n_vert, cut_len) ? csrq_max_degree() : max_degreeT));
-  const bool qsplit = quad && split_usable(split, n_vert, cut_len);   // P and J are symmetric: the same image serves A^T
+  const StackPlan P = stack_plan(gemm_bf16, batch, n_vert, hidden, num_layers, cut_len, max_degreeT, split,
+                                 masks ? stash_layout_lookup(masks) : 0);
+  const bool quad = P.quad;
+  const int qcols = P.qcols, rm_ld = P.rm_ld;
+  const size_t rm_off = P.rm_off;
   int32_t *ellT = reinterpret_cast<int32_t *>(scratch + L.ell);
-  if (qsplit) {
-    if (int rc = launch_csrqs_image(split->rowptr, split->col, split->scale, split->cls, n_vert, ellT, s)) return rc;
-  } else if (quad) {
-    if (int rc = launch_csrq_ell(rowptrT, colT, valT, n_vert, ellT, s)) return rc;
-  }
-  const int qcols = quad ? kQuadCols : 0;            // hybrid activation rows (a3vt_gcn_stack_fwd)
-  const int rm_ld = hidden - qcols;
-  const size_t rm_off = m * qcols;
+  if (int rc = launch_stack_ell(P, split, rowptrT, colT, valT, n_vert, ellT, s)) return rc;
   // ---- output layer
   {
     const float *xl = num_layers == 1 ? feats : acts + (size_t)(last - 1) * m * hidden;
@@ -936,51 +943,22 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
     if (int rc = launch_thin_bwd(x, ldx, k, weights[last], rowptrT, colT, valT, heavyT, n_vert, batch, grad_update,
                                  scratch + L.z3, num_layers > 1, gprev, ldg, ldg, scratch + L.thin_dw_slab,
                                  scratch + L.thin_db_slab, quad ? scratch + L.gq : nullptr, cpad / 4, quad ? xl : nullptr,
-                                 qcols / 4, s, sp3))
+                                 qcols / 4, s, split ? &sref : nullptr))
       return rc;
-    if (int rc = launch_slab_reduce_za(scratch + L.thin_dw_slab, thin_num_slabs(), (size_t)k * 3, (size_t)k * 3, (size_t)k * 3,
-                                       grad_weights[last], acc, s))
+    if (int rc = reduce_output_grads(scratch + L.thin_dw_slab, scratch + L.thin_db_slab, k, grad_weights[last], grad_biases[last],
+                                     acc, s))
       return rc;
-    if (int rc = launch_slab_reduce_za(scratch + L.thin_db_slab, thin_num_slabs(), 3, 3, 3, grad_biases[last], acc, s)) return rc;
   }
 
-  const bool x3 = gemm_bf16 == 3 && rowgemm3_stack_ok((long long)m, hidden, mask_ld(hidden, cut_len));   // as a3vt_gcn_stack_fwd
-  const int omode = gemm_bf16 == 1 ? 1 : 0;
-  // zero-padded weight images (Bt = W_i for dX) of all hidden layers, one launch
-  const bool batched_images = num_layers - 1 <= kMaxImages;
-  if (x3) {   // layers 1 .. L-2: three bf16 images each (layer 0's dX has the plain epilogue: exact kernels, fp32 image)
-    for (int i0 = 1; i0 < last; i0 += kMaxImages) {
-      WeightImages w3{};
-      const int cnt = last - i0 < kMaxImages ? last - i0 : kMaxImages;
-      for (int j = 0; j < cnt; ++j) {
-        w3.w[j] = weights[i0 + j];
-        w3.k[j] = hidden;
-      }
-      w3.dst = scratch + L.wt + L.wt_stride * i0;
-      w3.dst_stride = L.wt_stride;
-      w3.n = hidden;
-      w3.count = cnt;
-      w3.transpose = 0;
-      if (int rc = launch_weight_images3(w3, s)) return rc;
-    }
-  }
-  if (batched_images && num_layers > 1) {
-    WeightImages wi{};
-    int max_rows = 0;
-    for (int i = 0; i < (x3 ? 1 : last); ++i) {
-      wi.w[i] = weights[i];
-      wi.k[i] = i == 0 ? in_features : hidden;
-      wi.rows[i] = rowgemm_bt_rows(i == 0 ? ld_feats : hidden);
-      wi.ld[i] = pad16(hidden);
-      max_rows = wi.rows[i] > max_rows ? wi.rows[i] : max_rows;
-    }
-    wi.dst = scratch + L.wt;
-    wi.dst_stride = L.wt_stride;
-    wi.n = hidden;
-    wi.count = x3 ? 1 : last;
-    wi.transpose = 0;
-    if (int rc = launch_weight_images(wi, max_rows, pad16(hidden), s)) return rc;
-  }
+  // zero-padded weight images (Bt = W_i for dX) of the hidden layers; mode 3: layers 1 .. L-2 as three bf16 images each
+  // (layer 0's dX has the plain epilogue: exact kernels, fp32 image)
+  if (P.x3)
+    if (int rc = launch_stack_images(GEMM_FP32X3, 0, weights, 1, last, in_features, hidden, ld_feats, hidden, scratch + L.wt,
+                                     L.wt_stride, s))
+      return rc;
+  if (int rc = launch_stack_images(GEMM_FP32, 0, weights, 0, P.x3 ? 1 : last, in_features, hidden, ld_feats, hidden,
+                                   scratch + L.wt, L.wt_stride, s))
+    return rc;
 
   // ---- hidden layers, last to first.  g = dL/dY_i already multiplied by the ReLU mask of layer i.
   const int db_rows = quad ? batch : csr_bwd_num_slabs(batch, n_vert);
@@ -1000,7 +978,7 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
       const uint8_t *sq = masks + (size_t)(num_layers - 1) * mpad * mld + (size_t)i * signq_stride(m, cut_len);
       ProfScope psa(PROF_AGG, s);
       // the (mesh, channel) partials of this layer: summed over the meshes by ONE launch for all layers behind the loop
-      if (qsplit) {
+      if (P.qsplit) {
         if (int rc = launch_csrqs_bwd(scratch + L.gq, cut_len, ellT, n_vert, batch, dza, sq,
                                       scratch + L.db_slab + (size_t)i * db_layer_stride, s))
           return rc;
@@ -1056,10 +1034,10 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
       d.m = (int)m;
       d.k_in = w;
       d.n_out = hidden;
-      d.bf16 = omode;
-      if (x3 && i > 0) {   // hidden layer of a mode-3 stack: the split-operand kernel when it takes the shape
-        d.bf16 = 3;
-        if (!dw3_ok(d)) d.bf16 = omode;
+      d.mode = P.omode;
+      if (P.x3 && i > 0) {   // hidden layer of a mode-3 stack: the split-operand kernel when it takes the shape
+        d.mode = GEMM_FP32X3;
+        if (!dw3_ok(d)) d.mode = P.omode;
       }
       {
         ProfScope ps(PROF_DW, s);
@@ -1071,11 +1049,6 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
     }
 
     // dX_i = dZ W_i^T  (masked by the ReLU of layer i-1, whose output is X_i)
-    const int n_store = i == 0 ? ld_feats : hidden;
-    float *wp = scratch + L.wt + L.wt_stride * i;
-    const bool l3 = x3 && i > 0;
-    if (!batched_images && !l3)
-      if (int rc = launch_copy_pad(weights[i], kin, hidden, wp, rowgemm_bt_rows(n_store), pad16(hidden), s)) return rc;
     RowGemmArgs r{};
     r.a0 = dza;
     r.lda0 = cpad > 0 ? cpad : 4;
@@ -1086,13 +1059,13 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
     r.a1 = g;
     r.lda1 = hidden;
     r.ksplit = cpad;
-    r.bt = wp;
+    r.bt = scratch + L.wt + L.wt_stride * i;
     r.ldb = pad16(hidden);
     r.zeros = zeros;
     r.m = (int)m;
     r.k = hidden;
-    r.n_store = n_store;
-    r.bf16 = l3 ? 3 : omode;
+    r.n_store = i == 0 ? ld_feats : hidden;
+    r.mode = P.x3 && i > 0 ? GEMM_FP32X3 : P.omode;
     if (i == 0) {
       r.c = grad_feats;
       r.ldc = ld_feats;
@@ -1210,14 +1183,11 @@ int a3vt_gcn_layer_fwd(const float *x, int ld_x, int in_features, const float *w
   g.ldc2 = cpad > 4 ? cpad : 4;
   g.csplit = cut_len;
   g.no_relu = relu ? 0 : 1;
-  g.bf16 = gemm_bf16 == 1 ? 1 : 0;   // (mode 3 is a stack mode: a lone layer runs exact)
+  g.mode = gemm_bf16 == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;   // (mode 3 is a stack mode: a lone layer runs exact)
   if (int rc = launch_rowgemm(g, EPI_FWD_HIDDEN, s)) return rc;
   if (cut_len > 0) {
-    int32_t *heavy = nullptr;
-    if (max_degree <= 0 || max_degree > csr_heavy_degree()) {
-      heavy = reinterpret_cast<int32_t *>(scratch + L.heavy);
-      if (int rc = launch_csr_heavy_list(rowptr, n_vert, heavy, s)) return rc;
-    }
+    int32_t *heavy;
+    if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
     if (int rc = launch_csr_fwd(scratch + L.za, g.ldc2, bias, cut_len, rowptr, col, val, heavy, n_vert, batch, y, ld_y,
                                 nullptr, 0, relu ? 1 : 0, s))
       return rc;
@@ -1246,11 +1216,8 @@ int a3vt_gcn_layer_bwd(const float *x, int ld_x, int in_features, const float *w
   if (int rc = launch_fill_zero(grad_bias, out_features, s)) return rc;
   if (cut_len > 0) {
     // dZ[:, :c] = A^T G[:, :c] (columns c..cpad pass through), bias gradient = column sums of G[:, :c]
-    int32_t *heavyT = nullptr;
-    if (max_degreeT <= 0 || max_degreeT > csr_heavy_degree()) {
-      heavyT = reinterpret_cast<int32_t *>(scratch + L.heavy);
-      if (int rc = launch_csr_heavy_list(rowptrT, n_vert, heavyT, s)) return rc;
-    }
+    int32_t *heavyT;
+    if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
     if (int rc = launch_csr_bwd(ga, cpad, cut_len, rowptrT, colT, valT, heavyT, n_vert, batch, dz, npad,
                                 scratch + L.db_slab, s))
       return rc;
@@ -1281,7 +1248,7 @@ int a3vt_gcn_layer_bwd(const float *x, int ld_x, int in_features, const float *w
     d.m = (int)m;
     d.k_in = w;
     d.n_out = out_features;
-    d.bf16 = gemm_bf16 == 1 ? 1 : 0;
+    d.mode = gemm_bf16 == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;
     if (int rc = launch_dw(d, s)) return rc;
     if (int rc = launch_slab_reduce(scratch + L.dw_slab, dw_num_slabs(out_features), (size_t)w * out_features,
                                     (size_t)w * out_features, grad_weight + (size_t)c0 * out_features, s))
@@ -1303,7 +1270,7 @@ int a3vt_gcn_layer_bwd(const float *x, int ld_x, int in_features, const float *w
   r.m = (int)m;
   r.k = npad;
   r.n_store = ld_x;
-  r.bf16 = gemm_bf16 == 1 ? 1 : 0;
+  r.mode = gemm_bf16 == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;
   r.c = grad_x;
   r.ldc = ld_x;
   return launch_rowgemm(r, EPI_PLAIN, s);
@@ -1333,7 +1300,7 @@ int a3vt_rowgemm(const float *a, int lda, int m, int k, const float *wt, int n_o
   g.n_store = n_out;
   g.c = c;
   g.ldc = ldc;
-  g.bf16 = gemm_bf16 == 1 ? 1 : 0;   // (mode 3 is a stack mode: a lone layer runs exact)
+  g.mode = gemm_bf16 == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;   // (mode 3 is a stack mode: a lone layer runs exact)
   return launch_rowgemm(g, EPI_PLAIN, static_cast<hipStream_t>(stream));
 }
 
@@ -1369,7 +1336,7 @@ int a3vt_posenc_wide_fwd(const float *verts, const float *mask, int m, int input
   A3VT_CHECK_ARG(verts && mask && pe_params && feats && acts && scratch && m > 0);
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
-  A3VT_CHECK_ARG(gemm_bf16 == 0 || gemm_bf16 == 1);
+  A3VT_CHECK_ARG(gemm_bf16 == GEMM_FP32 || gemm_bf16 == GEMM_BF16_OPERANDS);
   return launch_posenc_wide_fwd(verts, mask, m, input_size, pe_params, feats, ld_feats, acts, scratch, zeros, gemm_bf16,
                                 static_cast<hipStream_t>(stream));
 }
@@ -1379,7 +1346,7 @@ int a3vt_posenc_wide_bwd(const float *verts, const float *mask, int m, int input
   A3VT_CHECK_ARG(verts && mask && pe_params && grad_feats && acts && grad_verts && grad_params && scratch && m > 0);
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
-  A3VT_CHECK_ARG(gemm_bf16 == 0 || gemm_bf16 == 1);
+  A3VT_CHECK_ARG(gemm_bf16 == GEMM_FP32 || gemm_bf16 == GEMM_BF16_OPERANDS);
   return launch_posenc_wide_bwd(verts, mask, m, input_size, pe_params, grad_feats, ld_feats, acts, grad_verts, grad_params,
                                 scratch, zeros, gemm_bf16, static_cast<hipStream_t>(stream));
 }

@@ -323,7 +323,7 @@ bool dww_ok(const DwArgs &a) {
 #ifdef A3VT_DBG_DWW_OFF   // variant build (tools/build_variants.sh rgw): dw_kernel everywhere, for A/B timing
   return false;
 #endif
-  if (a.bf16 != 0 || a.xq_nvert <= 0 || a.z0q_nvert != a.xq_nvert || a.xq == nullptr) return false;
+  if (a.mode != GEMM_FP32 || a.xq_nvert <= 0 || a.z0q_nvert != a.xq_nvert || a.xq == nullptr) return false;
   if (a.k_in != kDK || a.n_out != kDN || a.xq_quads != kDXQ || a.z0q_quads != kDZQ || a.zsplit != 4 * kDZQ) return false;
   if (a.ldx_src != kDXRW || a.ldz1 != kDLdz || a.m % a.xq_nvert != 0 || a.m % kDStageRows != 0 || a.xq_nvert < 16) return false;
   if (a.m > 3000000) return false;                    // 32-bit byte offsets inside every array

@@ -644,9 +644,9 @@ static int launch_rowgemm_nt(const RowGemmArgs &a, int grid_y, hipStream_t s) {
   const int max_wg = env_wg > 0 ? env_wg : 256 * C::WG_PER_CU;
   // one tile per wave until every CU has a workgroup; beyond that the kernel deals tiles evenly (two per wave per round)
   const int grid = cdiv(tiles, C::WAVES) < max_wg ? cdiv(tiles, C::WAVES) : max_wg;
-  if (a.bf16 == 2)
+  if (a.mode == GEMM_BF16_STORAGE)
     A3VT_LAUNCH((rowgemm_kernel<NT, EPI, C::NSTAGE, C::WAVES, 2>), dim3(grid, grid_y), dim3(64 * C::WAVES), shmem, s, a);
-  else if (a.bf16)
+  else if (a.mode == GEMM_BF16_OPERANDS)
     A3VT_LAUNCH((rowgemm_kernel<NT, EPI, C::NSTAGE, C::WAVES, 1>), dim3(grid, grid_y), dim3(64 * C::WAVES), shmem, s, a);
   else {
     // the exact fp32 products of the full-width layers take their A operand straight into registers (ADIRECT)
@@ -702,8 +702,8 @@ __global__ __launch_bounds__(256) void rowtile_kernel(RowGemmArgs p) {
 template <int EPI>
 static int launch_rowtile(const RowGemmArgs &a, hipStream_t s) {
   const dim3 grid(cdiv(a.n_store, 16), cdiv(cdiv(a.m, 16), 4));
-  if (a.bf16 == 2) A3VT_LAUNCH((rowtile_kernel<EPI, 2>), grid, dim3(256), 0, s, a);
-  else if (a.bf16) A3VT_LAUNCH((rowtile_kernel<EPI, 1>), grid, dim3(256), 0, s, a);
+  if (a.mode == GEMM_BF16_STORAGE) A3VT_LAUNCH((rowtile_kernel<EPI, 2>), grid, dim3(256), 0, s, a);
+  else if (a.mode == GEMM_BF16_OPERANDS) A3VT_LAUNCH((rowtile_kernel<EPI, 1>), grid, dim3(256), 0, s, a);
   else A3VT_LAUNCH((rowtile_kernel<EPI, 0>), grid, dim3(256), 0, s, a);
   A3VT_CHECK_LAUNCH();
   return 0;
@@ -768,8 +768,8 @@ bool rowgemm_quad_major_ok(int m, int n_store, int cpad) {
 }
 
 int launch_rowgemm(const RowGemmArgs &a, int epi, hipStream_t s) {
-  if (a.bf16 == 3) return launch_rowgemm3(a, epi, s);   // split-operand mode: its own kernel and checks (gcn_gemm3.hip)
-  if (a.a0q_nvert > 0 && (a.bf16 == 2 || a.m % a.a0q_nvert != 0 || a.ksplit != a.a0q_quads * 4)) {
+  if (a.mode == GEMM_FP32X3) return launch_rowgemm3(a, epi, s);   // split-operand mode: its own kernel and checks (gcn_gemm3.hip)
+  if (a.a0q_nvert > 0 && (a.mode == GEMM_BF16_STORAGE || a.m % a.a0q_nvert != 0 || a.ksplit != a.a0q_quads * 4)) {
     set_error("rowgemm: quad-major a0 needs ksplit = 4 * quads (ksplit=%d quads=%d) and whole meshes (m=%d)", a.ksplit, a.a0q_quads, a.m);
     return -1;
   }
@@ -778,9 +778,9 @@ int launch_rowgemm(const RowGemmArgs &a, int epi, hipStream_t s) {
     set_error("rowgemm: quad-major activations need the quad-major forward epilogue and at most 160 columns (yq_quads=%d)", a.yq_quads);
     return -1;
   }
-  if (a.zq_nvert > 0 && (epi == EPI_PLAIN || a.bf16 == 2 || a.c2 == nullptr || a.m % a.zq_nvert != 0 ||
+  if (a.zq_nvert > 0 && (epi == EPI_PLAIN || a.mode == GEMM_BF16_STORAGE || a.c2 == nullptr || a.m % a.zq_nvert != 0 ||
                          a.zq_quads * 4 != pad4(a.csplit) || !rowgemm_quad_major_ok(a.m, a.n_store, a.zq_quads * 4))) {
-    set_error("rowgemm: quad-major output unsupported for m=%d n=%d csplit=%d epi=%d mode=%d", a.m, a.n_store, a.csplit, epi, a.bf16);
+    set_error("rowgemm: quad-major output unsupported for m=%d n=%d csplit=%d epi=%d mode=%d", a.m, a.n_store, a.csplit, epi, a.mode);
     return -1;
   }
   if (epi == EPI_DX_MASK && (a.maskb == nullptr || 32 * a.mld > 4096)) {
@@ -1326,11 +1326,11 @@ int dw_num_slabs(int n_out) {
   return 256 / g > 0 ? 256 / g : 1;
 }
 
-int dw_images(const DwArgs &a) { return a.bf16 != 3 && dww_ok(a) ? dww_images() : dw_num_slabs(a.n_out); }
+int dw_images(const DwArgs &a) { return a.mode != GEMM_FP32X3 && dww_ok(a) ? dww_images() : dw_num_slabs(a.n_out); }
 int dw_slab_capacity(int n_out) { return dw_num_slabs(n_out) > dww_images() ? dw_num_slabs(n_out) : dww_images(); }
 
 int launch_dw(const DwArgs &a0, hipStream_t s) {
-  if (a0.bf16 == 3) return launch_dw3(a0, s);   // split-operand mode (gcn_gemm3.hip)
+  if (a0.mode == GEMM_FP32X3) return launch_dw3(a0, s);   // split-operand mode (gcn_gemm3.hip)
   DwArgs a = a0;
 #ifdef A3VT_DBG_DW_NOHYB   // timing-only: the plain kernel on the same buffers (wrong results)
   a.xq = nullptr; a.xq_nvert = a.xq_quads = a.z0q_nvert = a.z0q_quads = 0; a.ldx_src = 0;
@@ -1339,7 +1339,7 @@ int launch_dw(const DwArgs &a0, hipStream_t s) {
   if (a.ldx_src == 0) a.ldx_src = a.ldx;
   if ((a.xq_nvert > 0 && (a.xq == nullptr || a.xq_quads * 4 > a.k_in || a.m % a.xq_nvert != 0)) ||
       (a.z0q_nvert > 0 && (a.z0q_quads * 4 != a.zsplit || a.m % a.z0q_nvert != 0)) ||
-      (a.xq_nvert > 0 && a.z0q_nvert > 0 && a.xq_nvert != a.z0q_nvert) || a.bf16 == 2 ||
+      (a.xq_nvert > 0 && a.z0q_nvert > 0 && a.xq_nvert != a.z0q_nvert) || a.mode == GEMM_BF16_STORAGE ||
       (a.xq_nvert > 0 && a.xq_nvert < 32) || (a.z0q_nvert > 0 && a.z0q_nvert < 32) ||
       ((a.xq_nvert > 0 || a.z0q_nvert > 0) && (a.ldx_src == 4 || a.ldz1 == 4 || a.ldz0 == 4))) {
     set_error("dw: quad-major operands unsupported (xq %d x %d, z0q %d x %d, m=%d)", a.xq_nvert, a.xq_quads, a.z0q_nvert,
@@ -1400,17 +1400,17 @@ int launch_dw(const DwArgs &a0, hipStream_t s) {
   // fast path: every wave owns 4-5 input tiles and 2-3 output tiles (true for 300 x 300)
   const int tin = cdiv(a.k_in, 16), tout = cdiv(a.n_out, 16), groups = dw_col_groups(a.n_out);
   const bool fast = tin / 4 >= 4 && tin <= 20 && (tout / groups) / 4 >= 2 && cdiv(tout, groups) <= 12;
-  if (hyb && (a.bf16 || (a.xq_nvert > 0 && !fast))) {
+  if (hyb && (a.mode != GEMM_FP32 || (a.xq_nvert > 0 && !fast))) {
     set_error("dw: quad-major operands need the fp32 kernels (and quad-major X the 300-wide shape): k_in=%d n_out=%d mode=%d",
-              a.k_in, a.n_out, a.bf16);
+              a.k_in, a.n_out, a.mode);
     return -1;
   }
   const dim3 grid(dw_num_slabs(a.n_out), groups);
   // narrow inputs: at most one input tile per wave row, 2-3 output tiles per wave column; row-major X (the first layer's)
-  const bool narrow = !a.bf16 && tin <= 4 && a.xq_nvert == 0 && (tout / groups) / 4 >= 2 && cdiv(tout, groups) <= 12;
+  const bool narrow = a.mode == GEMM_FP32 && tin <= 4 && a.xq_nvert == 0 && (tout / groups) / 4 >= 2 && cdiv(tout, groups) <= 12;
   if (narrow && hyb) A3VT_LAUNCH((dw_kernel<false, false, true, true>), grid, dim3(1024), shmem, s, args);
   else if (narrow) A3VT_LAUNCH((dw_kernel<false, false, false, true>), grid, dim3(1024), shmem, s, args);
-  else if (a.bf16) A3VT_LAUNCH((dw_kernel<false, true, false>), grid, dim3(1024), shmem, s, args);
+  else if (a.mode == GEMM_BF16_OPERANDS) A3VT_LAUNCH((dw_kernel<false, true, false>), grid, dim3(1024), shmem, s, args);
   else if (fast && hyb) A3VT_LAUNCH((dw_kernel<true, false, true>), grid, dim3(1024), shmem, s, args);
   else if (fast) A3VT_LAUNCH((dw_kernel<true, false, false>), grid, dim3(1024), shmem, s, args);
   else if (hyb) A3VT_LAUNCH((dw_kernel<false, false, true>), grid, dim3(1024), shmem, s, args);

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
 // The register-resident form takes the hidden layers of the bf16 storage mode: K in (288, 320] bf16, up to 19 column
 // tiles, sign rows that fit the LDS slots, 16-byte aligned rows.  Everything else stays on rowgemm_kernel.
 bool rowgemm16_ok(const RowGemmArgs &a, int epi) {
-  if (a.bf16 != 2 || (epi != EPI_FWD_HIDDEN && epi != EPI_DX_MASK)) return false;
+  if (a.mode != GEMM_BF16_STORAGE || (epi != EPI_FWD_HIDDEN && epi != EPI_DX_MASK)) return false;
   if (a.k <= 144 || a.k > 160 || a.ldb < 160 || a.n_store > 304 || a.n_store < 32) return false;
   if (a.ldc % 8 != 0 || a.ldc > 304 || a.ldc < a.n_store) return false;
   if (a.lda0 % 4 != 0 || a.lda1 % 4 != 0 || a.ksplit % 4 != 0) return false;

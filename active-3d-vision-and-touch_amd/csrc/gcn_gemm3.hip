@@ -902,7 +902,7 @@ bool rowgemm3_stack_ok(long long m, int hidden, int mld) {
 }
 
 bool rowgemm3_ok(const RowGemmArgs &a, int epi) {
-  if (a.bf16 != 3 || (epi != EPI_FWD_HIDDEN && epi != EPI_DX_MASK)) return false;
+  if (a.mode != GEMM_FP32X3 || (epi != EPI_FWD_HIDDEN && epi != EPI_DX_MASK)) return false;
   if (!rowgemm3_dims_ok(a.m, a.k, a.n_store)) return false;
   if (a.lda0 % 4 != 0 || a.lda1 % 4 != 0 || a.ksplit % 4 != 0 || a.ldc % 4 != 0 || a.csplit > a.n_store) return false;
   // the kernel addresses A rows with 32-bit float offsets from a0 / a1
@@ -920,7 +920,7 @@ int launch_rowgemm3(const RowGemmArgs &a0, int epi, hipStream_t s) {
   RowGemmArgs a = a0;
   a.rem_row0 = a.rem_rows = 0;
   if (!rowgemm3_ok(a, epi)) {
-    set_error("rowgemm3: unsupported call (m=%d k=%d n=%d epi=%d mode=%d)", a.m, a.k, a.n_store, epi, a.bf16);
+    set_error("rowgemm3: unsupported call (m=%d k=%d n=%d epi=%d mode=%d)", a.m, a.k, a.n_store, epi, a.mode);
     return -1;
   }
   static OncePerDevice once;
@@ -951,7 +951,7 @@ int launch_rowgemm3(const RowGemmArgs &a0, int epi, hipStream_t s) {
 
 // dW shapes of mode 3: both dimensions those of a hidden layer, enough rows for 128 slabs of a few stages each.
 bool dw3_ok(const DwArgs &a) {
-  if (a.bf16 != 3) return false;
+  if (a.mode != GEMM_FP32X3) return false;
   if (a.k_in <= 288 || a.k_in > 304 || a.n_out <= 288 || a.n_out > 304 || a.m < 96 * 128) return false;
   if (a.ldz0 % 4 != 0 || a.ldz1 % 4 != 0 || a.zsplit % 4 != 0 || a.zsplit > 160 || a.n_out > a.ldz1) return false;
   const int ldx_src = a.ldx_src > 0 ? a.ldx_src : a.ldx;
@@ -967,7 +967,7 @@ int launch_dw3(const DwArgs &a0, hipStream_t s) {
   DwArgs a = a0;
   if (a.ldx_src == 0) a.ldx_src = a.ldx;
   if (!dw3_ok(a)) {
-    set_error("dw3: unsupported call (m=%d k_in=%d n_out=%d zsplit=%d mode=%d)", a.m, a.k_in, a.n_out, a.zsplit, a.bf16);
+    set_error("dw3: unsupported call (m=%d k_in=%d n_out=%d zsplit=%d mode=%d)", a.m, a.k_in, a.n_out, a.zsplit, a.mode);
     return -1;
   }
   static OncePerDevice once;

@@ -451,7 +451,7 @@ bool rowgemmw_ok(const RowGemmArgs &a, int epi) {
 #ifdef A3VT_DBG_RGW_OFF   // variant build (tools/build_variants.sh rgw): the round-5 kernel everywhere, for A/B timing
   return false;
 #endif
-  if (a.bf16 != 0 || (epi != EPI_FWD_HIDDEN && epi != EPI_DX_MASK)) return false;
+  if (a.mode != GEMM_FP32 || (epi != EPI_FWD_HIDDEN && epi != EPI_DX_MASK)) return false;
   if (a.zq_nvert <= 0 || a.a0q_nvert != a.zq_nvert || a.c2 == nullptr || a.m % a.zq_nvert != 0 || a.m % 16 != 0) return false;
   if (a.k <= 288 || a.k > 304 || a.n_store <= 288 || a.n_store > 304 || a.n_store % 4 != 0 || a.k % 4 != 0) return false;
   if (a.ksplit != a.a0q_quads * 4 || a.ldc % 4 != 0 || a.lda1 % 4 != 0 || a.ldb < 304) return false;

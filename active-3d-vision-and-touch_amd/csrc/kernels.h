@@ -7,6 +7,9 @@
 namespace a3vt {
 
 enum { EPI_PLAIN = 0, EPI_FWD_HIDDEN = 1, EPI_DX_MASK = 2 };
+// Gemm modes (RowGemmArgs::mode, DwArgs::mode; the gemm_bf16 argument of the C ABI): exact fp32, bf16 operands on fp32
+// rows, bf16 storage, fp32x3 (split-operand products of the hidden layers).  Each is described at RowGemmArgs::mode.
+enum GemmMode { GEMM_FP32 = 0, GEMM_BF16_OPERANDS = 1, GEMM_BF16_STORAGE = 2, GEMM_FP32X3 = 3 };
 
 // C[M][*] = A[M][K] * Bt[*][K]^T.  A columns [0,ksplit) come from a0, [ksplit,K) from a1 (same column index).
 struct RowGemmArgs {
@@ -27,16 +30,17 @@ struct RowGemmArgs {
   int ldc, ldc2, csplit, mld, moff;
   int no_relu;  // EPI_FWD_HIDDEN: store the pass-through channels without the ReLU (identity activation)
   int plain_relu;  // EPI_PLAIN: C = max(A Bt^T, 0) (the wide vertex-feature encoder's layers, posenc_wide.hip)
-  // 0: exact fp32 MFMA.  1: fp32 storage, operands rounded to bf16 on the way into v_mfma_f32_16x16x16_bf16.
-  // 2: bf16 STORAGE — a0 / a1 / bt point at bf16 rows (lda*, ldb, k, ksplit still in 4-byte units = pairs of bf16),
+  // GEMM_FP32: exact fp32 MFMA.  GEMM_BF16_OPERANDS: fp32 storage, operands rounded to bf16 on the way into
+  //    v_mfma_f32_16x16x16_bf16.
+  // GEMM_BF16_STORAGE — a0 / a1 / bt point at bf16 rows (lda*, ldb, k, ksplit still in 4-byte units = pairs of bf16),
   //    v_mfma_f32_16x16x32_bf16; EPI_FWD_HIDDEN / EPI_DX_MASK write bf16 (c, c2 as bf16 with ldc, ldc2 in ELEMENTS, all
   //    columns < ldc written), EPI_PLAIN writes fp32.  fp32 accumulation in every mode.
-  // 3: "fp32x3" (gcn_gemm3.hip) — fp32 storage as mode 0, the product as six bf16 MFMA passes on exactly split operands;
+  // GEMM_FP32X3 (gcn_gemm3.hip) — fp32 storage as GEMM_FP32, the product as six bf16 MFMA passes on exactly split operands;
   //    bt points at the THREE bf16 images of the layer (launch_weight_images3; ldb is ignored).  Hidden-layer shapes only
-  //    (rowgemm3_ok): the CALLER decides per stack (rowgemm3_stack_ok) and passes bf16 = 3 with the three images only for
-  //    the layers the kernel takes; every other product of a mode-3 stack is issued as a mode-0 call with an fp32 image.
-  //    A bf16 = 3 call the kernel does not take is an error (launch_rowgemm3 does not fall back: it has no fp32 image).
-  int bf16;
+  //    (rowgemm3_ok): the CALLER decides per stack (rowgemm3_stack_ok) and passes GEMM_FP32X3 with the three images only for
+  //    the layers the kernel takes; every other product of a mode-3 stack is issued as a GEMM_FP32 call with an fp32 image.
+  //    A GEMM_FP32X3 call the kernel does not take is an error (launch_rowgemm3 does not fall back: it has no fp32 image).
+  int mode;   // GemmMode
   // rows [rem_row0, rem_row0 + rem_rows) beyond the m rows of the main loop: the few leftover tiles of the load-balanced
   // split, done by the tail of the same launch (set by launch_rowgemm; 0 = none)
   int rem_row0, rem_rows;
@@ -118,7 +122,7 @@ struct DwArgs {
   float *slab;  // [dw_num_slabs(n_out)][k_in][n_out]
   int ldx, ldz0, ldz1, zsplit;
   int m, k_in, n_out;
-  int bf16;  // as RowGemmArgs::bf16 (0, 1; 3 = the split-operand kernel dw3_kernel, hidden-layer shapes only: dw3_ok)
+  int mode;  // as RowGemmArgs::mode (GEMM_FP32, GEMM_BF16_OPERANDS; GEMM_FP32X3 = dw3_kernel, hidden-layer shapes only: dw3_ok)
   int nstage;  // LDS ring depth (set by launch_dw)
   // Quad-major operands (0 = off; the outputs of the channel-sliced aggregation kernels, gcn_csrq.hip):
   //   xq_nvert > 0 : X columns [0, 4 xq_quads) come from xq [m / xq_nvert][xq_quads][xq_nvert] float4; the other columns
@@ -132,7 +136,7 @@ int dw_num_slabs(int n_out);
 // slab images the launch that takes `a` will write (launch_dw picks the kernel): what launch_slab_reduce* must sum
 int dw_images(const DwArgs &a);
 int dw_slab_capacity(int n_out);   // images to allocate: enough for either kernel
-// dW = X^T dZ of a hidden layer in mode 3 (DwArgs::bf16 == 3, gcn_gemm3.hip; same slabs as launch_dw); dw3_ok: the shapes it takes
+// dW = X^T dZ of a hidden layer in mode 3 (DwArgs::mode == GEMM_FP32X3, gcn_gemm3.hip; same slabs as launch_dw); dw3_ok: the shapes it takes
 bool dw3_ok(const DwArgs &a);
 int launch_dw3(const DwArgs &a, hipStream_t s);
 // True when dw_kernel can take the first 4 * quads columns of a k_in-wide X quad-major (they must end where a wave's input tiles end).

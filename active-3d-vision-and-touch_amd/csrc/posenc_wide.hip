@@ -237,7 +237,7 @@ static int build_images(const WideDims &d, const float *params, float *scratch, 
 static RowGemmArgs plain_gemm(const float *a, int lda, int k, const float *bt, int n_store, float *c, int ldc, size_t m,
                               const float *zeros, int relu, int bf16) {
   RowGemmArgs g{};
-  g.bf16 = bf16 ? 1 : 0;   // bf16 OPERAND mode of the bf16 configurations: fp32 rows in memory, operands rounded into the matrix pipe
+  g.mode = bf16 ? GEMM_BF16_OPERANDS : GEMM_FP32;   // bf16 OPERAND mode of the bf16 configurations: fp32 rows in memory, operands rounded into the matrix pipe
   g.a0 = g.a1 = a;
   g.lda0 = g.lda1 = lda;
   g.ksplit = k;
@@ -323,7 +323,7 @@ int launch_posenc_wide_bwd(const float *verts, const float *mask, int m, int inp
     w.m = m;
     w.k_in = lin;
     w.n_out = nz;
-    w.bf16 = (gemm_bf16 && l > 0) ? 1 : 0;   // layer 0 (its weight gradient and the gradient that goes on to the positions) exact
+    w.mode = (gemm_bf16 && l > 0) ? GEMM_BF16_OPERANDS : GEMM_FP32;   // layer 0 (its weight gradient and the gradient that goes on to the positions) exact
     if (int rc = launch_dw(w, s)) return rc;
     if (int rc = launch_slab_reduce(scratch + L.slab, dw_num_slabs(nz), (size_t)lin * nz, (size_t)lin * nz, scratch + L.dbp, s))
       return rc;

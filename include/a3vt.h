@@ -142,7 +142,7 @@ int a3vt_gcn_stack_bwd_acc(const float *feats, int ld_feats, int in_features,
  * channel-sliced kernels of csrc/gcn_csrqs.hip under the conditions listed above with max_degree <= 12; bf16 storage: the
  * row walk over P plus the two sums).  Same values up to fp32 rounding (another association of the same sums), not bit for
  * bit.  All pointers DEVICE pointers; the struct itself lives on the host.  Vision-only templates are the special case
- * n_seam = n_centre = 0. */
+ * n_seam = n_centre = 0.  A split is passed whole: a non-NULL `split` with any of its four arrays NULL is refused. */
 typedef struct a3vt_adj_split {
   const int32_t *rowptr; /* [n_vert + 1]  CSR of P */
   const int32_t *col;    /* [rowptr[n_vert]]  ascending within a row */

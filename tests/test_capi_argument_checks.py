@@ -50,6 +50,22 @@ def test_csr_and_split_validators_on_host_arrays(L):
     rp2 = rp.copy()
     rp2[3] = rp2[2] - 1                                    # not monotone
     assert L.a3vt_csr_validate(rp2.ctypes.data, col.ctypes.data, v.shape[0], col.size) != 0
+    # the split validator: P's rowptr is checked whole before any row of P is read
+    sp = csr.split()
+    n = v.shape[0]
+    p_rp, p_col = np.ascontiguousarray(sp.rowptr, dtype=np.int32), np.ascontiguousarray(sp.col, dtype=np.int32)
+    scale, cls = np.ascontiguousarray(sp.scale, dtype=np.float32), np.ascontiguousarray(sp.cls, dtype=np.uint8)
+    check = lambda prp: L.a3vt_adj_split_validate(rp.ctypes.data, col.ctypes.data, csr.val.ctypes.data, n, prp.ctypes.data,   # noqa: E731
+                                                  p_col.ctypes.data, scale.ctypes.data, cls.ctypes.data)
+    assert check(p_rp) == 0
+    # row 0 is intact, but its second neighbour j has a row end past P: the symmetry search of (0, j) would probe p_col[nnz(P)]
+    j = int(p_col[p_rp[0] + 1])
+    bad = p_rp.copy()
+    bad[j + 1] = 2 * p_col.size - bad[j] + 1
+    assert check(bad) != 0 and "adj_split" in _err(L)
+    bad = p_rp.copy()
+    bad[n] += 1                                            # one entry more than P has
+    assert check(bad) != 0
 
 
 def test_size_queries_never_fail_on_odd_sizes(L):
@@ -96,6 +112,17 @@ def test_entry_points_refuse_bad_arguments_before_touching_them(L):
     assert L.a3vt_gcn_stack_fwd(None, 52, 50, None, None, 20, 300, 99, None, None, None, 7, 2562, 64, 0, None, None, None, None, None) != 0
     assert _err(L) != ""
     assert L.a3vt_gcn_stack_fwd(FAKE, 51, 50, FAKE, FAKE, 20, 300, 99, FAKE, FAKE, FAKE, 7, 2562, 64, 7, None, None, FAKE, FAKE, None) != 0   # mode 7
+    # a split with one of its arrays missing, in the exact fp32 and the bf16 storage modes (weights: fake host arrays)
+    from a3vt_amd import lib
+    for part in ((FAKE, None, None, None), (FAKE, FAKE, FAKE, None), (None, FAKE, FAKE, FAKE)):
+        sp = ctypes.byref(lib.AdjSplit(*[p.value if p else None for p in part], 10, 0, 0))
+        for mode in (0, 2):
+            assert L.a3vt_gcn_stack_fwd_adj(FAKE, 52, 50, FAKE, FAKE, 20, 300, 99, FAKE, FAKE, FAKE, 7, sp, 2562, 64, mode,
+                                            FAKE, FAKE, FAKE, FAKE, None) != 0
+            assert "argument check failed" in _err(L)
+            assert L.a3vt_gcn_stack_bwd_adj(FAKE, 52, 50, FAKE, FAKE, 20, 300, 99, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, 7, sp, 2562, 64,
+                                            mode, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, 0, None) != 0
+            assert "argument check failed" in _err(L)
     assert L.a3vt_dbg_csr_algo(9) != 0
 
 

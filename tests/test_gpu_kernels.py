@@ -67,7 +67,8 @@ def _state_to(dev, st):
 
 @pytest.mark.parametrize("tname,use_touch,L,H,B", [("ico2", False, 3, 32, 3), ("atlas", True, 4, 300, 2),
                                                      ("ico3", False, 20, 300, 2), ("ico2", False, 1, 300, 2),
-                                                     ("ico4", False, 3, 300, 13)])  # 33306 rows: split launches
+                                                     ("ico4", False, 3, 300, 13),   # 33306 rows: split launches
+                                                     ("ico2", False, 36, 32, 2)])   # 35 hidden layers: two launches of weight images
 def test_gcn_stack_fwd_bwd(cuda, tname, use_touch, L, H, B):
     from a3vt_amd import mesh as amesh, ops
     from oracle import gcn as og
