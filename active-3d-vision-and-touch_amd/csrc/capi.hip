@@ -998,8 +998,11 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
 
     // dW_i = X_i^T dZ.  The kernel covers up to 304 input channels per pass; wider inputs (the 448-wide image
     // model's first layer) go in column blocks of <= 300, each first copied into a contiguous panel (StackLayout::panel).
-    for (int c0 = 0; c0 < kin; c0 += 300) {
-      const int w = kin - c0 < 300 ? kin - c0 : 300;
+    // Up to 304 channels are ONE pass: only the panels start at column c0 (a second pass over 301..304 channels would read
+    // X from column 0).
+    const int cblk = kin > 304 ? 300 : kin;
+    for (int c0 = 0; c0 < kin; c0 += cblk) {
+      const int w = kin - c0 < cblk ? kin - c0 : cblk;
       const float *xs = x;
       int ldxs = ldx;
       if (kin > 304) {

@@ -27,9 +27,9 @@ def adj_matmul(adj, x):
     if isinstance(adj, (tuple, list)):
         rowptr, col, val = adj
         n = rowptr.numel() - 1
-        row = torch.repeat_interleave(torch.arange(n), rowptr[1:] - rowptr[:-1])
+        row = torch.repeat_interleave(torch.arange(n, device=rowptr.device), rowptr[1:] - rowptr[:-1])
         contrib = x[:, col, :] * val.to(x.dtype)[None, :, None]
-        out = torch.zeros(x.shape[0], n, x.shape[2], dtype=x.dtype)
+        out = torch.zeros(x.shape[0], n, x.shape[2], dtype=x.dtype, device=x.device)
         return out.index_add(1, row, contrib)
     return torch.matmul(adj.to(x.dtype), x)
 
@@ -70,6 +70,114 @@ def gcn(x, state, prefix, adj, num_layers, cut=0.33, collect=None, bf16=False):
         if collect is not None:
             collect.append(x)
     return x
+
+
+def adj_t_matmul(adj, x):
+    """``A^T x`` for the adjacency forms :func:`adj_matmul` takes (the backward's aggregation)."""
+    if isinstance(adj, (tuple, list)):
+        rowptr, col, val = adj
+        n = rowptr.numel() - 1
+        row = torch.repeat_interleave(torch.arange(n, device=rowptr.device), rowptr[1:] - rowptr[:-1])
+        contrib = x[:, row, :] * val.to(x.dtype)[None, :, None]
+        out = torch.zeros(x.shape[0], n, x.shape[2], dtype=x.dtype, device=x.device)
+        return out.index_add(1, col, contrib)
+    return torch.matmul(adj.to(x.dtype).t(), x)
+
+
+# ---- the bf16 gemm modes of the stack, rounding where the device rounds (explicit forward and backward) ----------------
+#
+# ``oracle.gcn.gcn(..., bf16=...)`` emulates the forward roundings and leaves the backward to autograd, which rounds the
+# GRADIENT at every ``bf16_round`` (the gradient of t.to(bfloat16) is itself rounded).  The functions below are written
+# out by hand from the device's stack loops (csrc/capi.hip: a3vt_gcn_stack_fwd_adj / a3vt_gcn_stack_bwd_adj for mode 1,
+# stack_fwd16 / stack_bwd16 for mode 2; kernels in csrc/gcn_bf16s.hip) and apply ``rnd`` to VALUES only.  r = ``rnd``,
+# c = cut_len, X_i = input of hidden layer i, mask_i = X_i > 0 (the sign bytes the forward saves are those of the
+# pre-activations; ReLU makes them the same test).
+#
+# Mode 2 ("bf16s", bf16 storage, fp32 sums):
+#   forward   X_0 = r(feats) (cvt_rows; pad8 columns, the padding zero).  Z = X_i r(W_i) (weight image bf16, MFMA fp32
+#             accumulation).  Za = r(Z[:, :c]) (the raw aggregated channels are stored bf16).  Y[:, :c] = r(relu(A Za + b[:c]))
+#             (csr16_fwd / csr16t_fwd, fp32 sums), Y[:, c:] = r(relu(Z[:, c:])) (no bias there, model.py:358).
+#             Output layer: z3 = X_{L-1} W_last with W_last fp32 (thin16_fwd), update = A z3 + b (csr3, through the split
+#             when there is one), all fp32.
+#   backward  dz3 = A^T dU (csr3).  G = r(mask_{L-1} * dz3 W_last^T) (thin16_bwd); dW_last = X_{L-1}^T dz3, db_last = sum dU.
+#             Hidden layer i, top down: dZa = r(A^T G[:, :c]) (csr16_bwd / csr16t_bwd; columns [c, pad8(c)) of that buffer
+#             pass G through unchanged); db_i[:c] = column sums of G[:, :c] itself — the bf16 values the aggregation reads
+#             (its bias partials sum the vertex's OWN row, not the gathered one), db_i[c:] = 0.  dZ = [dZa | G[:, c:]].
+#             dW_i = X_i^T dZ (dw16: exact products of bf16 values, fp32 sums; windows of <= 304 input columns).
+#             dX_i = dZ r(W_i)^T (bf16 image): i > 0 -> G = r(mask_i * dX_i) (EPI_DX_MASK); i = 0 -> grad_feats = dX_0,
+#             stored fp32 (EPI_PLAIN), the padding columns zero.
+# Mode 1 ("bf16", bf16 operands, fp32 storage):
+#   forward   Z = r(X_i) r(W_i) (operands rounded as they enter the matrix pipe), aggregation, bias and ReLU fp32, nothing
+#             stored rounded; the output layer is exact fp32 (launch_thin_fwd takes no operand mode).
+#   backward  the output layer is exact fp32 (launch_thin_bwd): dz3 = A^T dU, G = mask * dz3 W_last^T.  dZa = A^T G[:, :c],
+#             db_i[:c] = column sums of G[:, :c], in fp32.  dW_i = r(X_i)^T r(dZ) (dw_kernel, StackPlan::omode; X_0 through
+#             the column panels when in_features > 304), dX_i = r(dZ) r(W_i)^T, G = mask_i * dX_i and grad_feats = dX_0 fp32.
+# With ``rnd`` the identity both modes are the exact network (the autograd gradients of :func:`gcn`).
+
+def _no_round(t):
+    return t
+
+
+def bf16_hidden_layer(x, weight, bias, adj, cut_len, mode, rnd=bf16_round):
+    """Output Y_i of one hidden layer of a mode-1 / mode-2 stack from its input ``x`` (B,N,K); weight (1,K,H) or (K,H)."""
+    w = rnd(weight.reshape(weight.shape[-2], weight.shape[-1]).to(x.dtype))
+    z = torch.matmul(rnd(x), w)
+    store = rnd if mode == 2 else _no_round
+    za = store(z[..., :cut_len])
+    agg = adj_matmul(adj, za) + bias[:cut_len].to(x.dtype)
+    return store(torch.relu(torch.cat((agg, z[..., cut_len:]), dim=-1)))
+
+
+def bf16_output_layer(x, weight, bias, adj):
+    """The 3-channel output layer of a bf16 stack (both modes): exact, on the last hidden layer's output."""
+    z3 = torch.matmul(x, weight.reshape(weight.shape[-2], weight.shape[-1]).to(x.dtype))
+    return adj_matmul(adj, z3) + bias.to(x.dtype)
+
+
+def bf16_stack_forward(feats, weights, biases, adj, cut_len, mode, rnd=bf16_round):
+    """Whole stack in mode 1 or 2 (see above).  Returns (acts, update): acts[i] = input of layer i (acts[0] = r(feats) in
+    mode 2, feats in mode 1), the argument :func:`bf16_stack_backward` takes."""
+    x = rnd(feats) if mode == 2 else feats
+    acts = [x]
+    for i in range(len(weights) - 1):
+        x = bf16_hidden_layer(x, weights[i], biases[i], adj, cut_len, mode, rnd)
+        acts.append(x)
+    return acts, bf16_output_layer(x, weights[-1], biases[-1], adj)
+
+
+def bf16_stack_backward(acts, weights, adj, cut_len, mode, grad_update, rnd=bf16_round):
+    """Gradients of a mode-1 / mode-2 stack (see above) from the inputs of its layers ``acts`` (the device's own stash for a
+    teacher-forced check, or :func:`bf16_stack_forward`'s) and dL/d update.  Returns (grad_feats, [dW_i], [db_i]) with
+    dW_i shaped like the weights (1,K,H)."""
+    nl = len(weights)
+    store = rnd if mode == 2 else _no_round
+    operand = rnd if mode == 1 else _no_round
+    dt = acts[0].dtype
+    mat = lambda w: w.reshape(w.shape[-2], w.shape[-1]).to(dt)  # noqa: E731
+    dws, dbs = [None] * nl, [None] * nl
+    dz3 = adj_t_matmul(adj, grad_update.to(dt))
+    x = acts[nl - 1]
+    dws[nl - 1] = torch.einsum("bnk,bnj->kj", x, dz3)[None]
+    dbs[nl - 1] = grad_update.to(dt).sum((0, 1))
+    if nl == 1:
+        return torch.matmul(dz3, mat(weights[0]).t()), dws, dbs
+    g = store((x > 0).to(dt) * torch.matmul(dz3, mat(weights[nl - 1]).t()))
+    grad_feats = None
+    for i in range(nl - 2, -1, -1):
+        hidden = g.shape[-1]
+        dza = store(adj_t_matmul(adj, g[..., :cut_len]))
+        db = torch.zeros(hidden, dtype=dt, device=g.device)
+        db[:cut_len] = g[..., :cut_len].sum((0, 1))
+        dz = operand(torch.cat((dza, g[..., cut_len:]), dim=-1))
+        x = acts[i]
+        dws[i] = torch.einsum("bnk,bnj->kj", operand(x), dz)[None]
+        dbs[i] = db
+        dx = torch.matmul(dz, rnd(mat(weights[i])).t())
+        if i > 0:
+            g = store((x > 0).to(dt) * dx)
+        else:
+            grad_feats = dx
+    return grad_feats, dws, dbs
 
 
 def nerf_embedding(p):

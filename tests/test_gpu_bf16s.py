@@ -3,7 +3,10 @@ gradients and weight images bf16 in HBM, fp32 accumulation, fp32 master weights)
 never the headline: forward against the oracle's float64 emulation of exactly these roundings (``oracle.gcn.gcn(...,
 bf16="storage")``) and against the exact fp32 network at the bf16 level; vertex positions of the full 20 x 300 network
 within 5e-3 of the REFERENCE's fp32 positions (fixture g4; SURVEY App. B measured 1.4e-3 for bf16 rounding after every
-layer); gradients against autograd of the emulation at the bf16 level."""
+layer); gradients against autograd of the emulation at the bf16 level.  That autograd rounds the GRADIENT wherever the
+emulation rounds a value (dW through the bf16 weight, grad_feats through the bf16 input, each stored gradient), while the
+device reduces dW and writes grad_feats in fp32: the gradient bound below is sized to that mismatch.
+tests/test_gpu_bf16_exact.py holds the mode to an emulation that rounds where the kernels do."""
 import numpy as np
 import pytest
 import torch

@@ -262,7 +262,10 @@ def test_rowgemm_bf16_operand_mode(cuda, m, k, n):
 def test_gcn_stack_bf16_mode(cuda, tname, use_touch, L, B):
     """BASELINE configs[3]/[4] ("bf16 + MFMA feature MLP"): the stack with bf16 GEMM operands.  Forward against the
     oracle's emulation of the same rounding (float64 otherwise) and against the fp32 path; gradients against autograd of
-    that emulation at the bf16 level (the device's backward products round their operands too)."""
+    that emulation at the bf16 level.  Autograd through ``bf16_round`` rounds the GRADIENT at every rounding point: it rounds
+    dW, grad_feats and the outputs of the backward products to bf16, where the device rounds their operands and keeps dW and
+    grad_feats in fp32 — most of the measured gap.  tests/test_gpu_bf16_exact.py holds this mode to an emulation that
+    rounds where the kernels do."""
     from a3vt_amd import mesh as amesh, ops
     from oracle import gcn as og
     from helpers import rel_l2
@@ -281,7 +284,7 @@ def test_gcn_stack_bf16_mode(cuda, tname, use_touch, L, B):
     with torch.no_grad():
         out_fp32 = og.gcn(feats.double(), {k: v.detach() for k, v in st64.items()}, "mesh_deform_1", adj64, L, 0.33)
     # emulated forward with autograd straight through the roundings: same ReLU masks as the device forward (up to
-    # rounding ties), backward products with unrounded gradients
+    # rounding ties); its backward rounds the gradients at each bf16_round (see the docstring)
     out_emul = og.gcn(f64, st64, "mesh_deform_1", adj64, L, 0.33, bf16=True)
     (out_emul * gup.double()).sum().backward()
     if use_touch:
