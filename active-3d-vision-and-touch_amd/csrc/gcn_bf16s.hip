@@ -528,11 +528,7 @@ __global__ __launch_bounds__(256) void csr16_fwd_kernel(const u16 *__restrict__ 
       const int ch = ch0 + hl * 8;
       const bool on = ch < c;
       const F8 acc = gather_row16(zb, ldza, ch, on, e0, e1, hl, colidx, val);
-#ifdef A3VT_DBG_CSR_NOSTORE   // timing-only ablation (tools/build_variants.sh csr): every gathered value stays live, nothing is stored
-      if (on && acc.lo[0] + acc.lo[1] + acc.lo[2] + acc.lo[3] + acc.hi[0] + acc.hi[1] + acc.hi[2] + acc.hi[3] == 1.2345e-33f)
-#else
       if (on)
-#endif
         csr16_fwd_store(acc, ch, c, c <= 128 ? bs0 : csr16_load_bias(bias, ch, c), relu, y + row * ldy + ch,
                         maskb ? maskb + row * mld : nullptr);
     }
@@ -657,12 +653,8 @@ constexpr int kT16Rows = kT16Tile + kT16Halo + 1;      // LDS rows; the last one
 constexpr int kT16Zero = kT16Rows - 1;
 constexpr int kT16Hdr = 1 + kT16Halo;                  // ints per tile: halo count (-1: row walk), halo vertices
 constexpr int kT16MaxVerts = 16384;                    // bit mask of the builder
-#ifndef A3VT_T16_BUFS
-#define A3VT_T16_BUFS 1
-#endif
-constexpr int kT16Bufs = A3VT_T16_BUFS;                // staging buffers per workgroup: 2 = the next unit's rows arrive during the gathers
-constexpr int kT16MaxUnits = kT16Bufs == 2 ? 32 : 12;  // units per persistent workgroup (their plan headers sit in LDS)
-constexpr int kT16Wgs = kT16Bufs == 2 ? 512 : 1024;    // persistent workgroups of a launch: two (75 KB of LDS each) or four (37 KB) per CU
+constexpr int kT16MaxUnits = 12;                       // units per persistent workgroup (their plan headers sit in LDS)
+constexpr int kT16Wgs = 1024;                          // persistent workgroups of a launch: four (37 KB of LDS each) per CU
 
 __host__ __device__ static inline int t16_tiles(int n_vert) { return (n_vert + kT16Tile - 1) / kT16Tile; }
 size_t csr16t_plan_ints(int n_vert) { return (size_t)t16_tiles(n_vert) * kT16Hdr + (size_t)n_vert * (4 + 8) + 16; }
@@ -750,17 +742,6 @@ int launch_csr16t_build(const int32_t *rowptr, const int32_t *col, const float *
   return 0;
 }
 
-#ifdef A3VT_DBG_T16_STAMPS   // diagnostic build (tools/build_variants.sh t16): wall clock (s_memrealtime, 100 MHz) of thread 0 at the
-// phase boundaries of csr16t_kernel, per workgroup: [0] entry, [1] first unit requested, [3] all units gathered and stored
-__device__ unsigned long long g_t16_stamps[4096 * 4];
-#define T16_STAMP(k)                                                                                             \
-  do {                                                                                                           \
-    if (threadIdx.x == 0 && blockIdx.x < 4096) g_t16_stamps[blockIdx.x * 4 + (k)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define T16_STAMP(k) do { } while (0)
-#endif
-
 struct T16Args {
   const u16 *src;        // [M][ld_src] bf16: raw aggregated columns (forward) / output gradient rows (backward)
   int ld_src;
@@ -776,13 +757,13 @@ struct T16Args {
   const float *val;
 };
 
-// LDS, per staging buffer: rows [kT16Rows][13] x 16 B, slot records [tile] x 16 B, weights [tile] x 32 B, the halo list.
-// Two buffers per workgroup: the rows of its NEXT tile arrive while it gathers the current one.
+// LDS: one staging buffer (rows [kT16Rows][13] x 16 B, slot records [tile] x 16 B, weights [tile] x 32 B, the halo list),
+// then the plan headers of the workgroup's units.
 constexpr int kT16LdsRows = kT16Rows * kT16Pieces * 16;
 constexpr int kT16LdsSlots = kT16Tile * 16, kT16LdsWgt = kT16Tile * 32;
 constexpr int kT16LdsBuf = kT16LdsRows + kT16LdsSlots + kT16LdsWgt;
 constexpr int kT16LdsHdrs = kT16MaxUnits * kT16Hdr * 4;
-constexpr int kT16Lds = kT16Bufs * kT16LdsBuf + kT16LdsHdrs;
+constexpr int kT16Lds = kT16LdsBuf + kT16LdsHdrs;
 static_assert(16 * 128 * 4 <= kT16LdsRows, "bias-gradient staging reuses a rows region");
 
 // blockIdx -> (mesh, tile): the tiles of a mesh on neighbouring workgroups of ONE die (they share halo rows in its L2)
@@ -897,12 +878,8 @@ __device__ __forceinline__ void t16_fwd_store(const F8 &acc, int ch, int c, cons
   o.hi = acc.hi + bs.hi;
   const unsigned bits = (t16_relu_bits(o.lo) | (t16_relu_bits(o.hi) << 8)) & valid_bits;   // [3:0] channels ch..ch+3, [11:8] ch+4..ch+7
   const u32x4 pk = pack8(o);
-  if (ch + 7 < c) {
-#ifndef A3VT_T16_NO_NT   // streaming stores: the results are not read again by this launch, and the L2 write-back at its end shrinks (forward 30.9 -> 28.2 us)
+  if (ch + 7 < c) {   // streaming stores: the results are not read again by this launch, and the L2 write-back at its end shrinks (forward 30.9 -> 28.2 us)
     __builtin_nontemporal_store(pk, reinterpret_cast<u32x4 *>(yo));
-#else
-    *reinterpret_cast<u32x4 *>(yo) = pk;
-#endif
   } else {   // the row's last group: channels ch .. c - 1
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
@@ -915,8 +892,8 @@ __device__ __forceinline__ void t16_fwd_store(const F8 &acc, int ch, int c, cons
 
 // One persistent kernel for both directions.  BWD: the A^T plan; channels [c, cpad) pass the own gradient through; bias-gradient
 // partial sums per workgroup (rows of db_slab beyond the persistent workgroups are written as zeros).
-// Pipeline per workgroup, units u0, u1, ... (stride = the persistent workgroups): while unit j is gathered out of buffer j & 1,
-// unit j + 1's rows arrive in the other buffer and unit j + 2's plan header is on its way into registers.
+// Per workgroup, units u0, u1, ... (stride = the persistent workgroups) go through one staging buffer: unit j + 1's rows are
+// requested once every wave has left unit j's.
 template <bool BWD>
 __global__ __launch_bounds__(256) void csr16t_kernel(T16Args a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -946,7 +923,7 @@ __global__ __launch_bounds__(256) void csr16t_kernel(T16Args a) {
   // vector loads in flight across the gather loop, and the compiler then put an s_waitcnt vmcnt(0) in front of that loop
   // ("flush before a loop that stores and uses loaded registers") — behind the next unit's DMA.  In the steady state the
   // kernel issues no global load but its DMA.
-  char *hdrs = lds + kT16Bufs * kT16LdsBuf;
+  char *hdrs = lds + kT16LdsBuf;
   const unsigned hdrs_a = (unsigned)(size_t)(__attribute__((address_space(3))) char *)hdrs;
   auto valid = [&](long long u) {
     long long b;
@@ -972,20 +949,16 @@ __global__ __launch_bounds__(256) void csr16t_kernel(T16Args a) {
     if (halo > 0) t16_stage_halo(a, buf, b, halo, hdrs_a + (j * kT16Hdr + 1) * 4);
   };
   long long u = blockIdx.x;
-  T16_STAMP(0);
   int halo_c = valid(u) ? count_of(0) : -2;
   if (halo_c > -2) issue(u, 0, halo_c, lds);
-  T16_STAMP(1);
-  int par = 0, j = 0;
-  for (; u < units; u += nwg, par ^= (kT16Bufs - 1), ++j) {
-    char *buf = lds + par * kT16LdsBuf;
+  int j = 0;
+  for (; u < units; u += nwg, ++j) {
+    char *buf = lds;
     // (the builtin, not an asm: the compiler's own bookkeeping must see that nothing is outstanding here)
     __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();         // unit u's rows are in buf; everyone has left the other buffer (unit u - nwg)
+    __builtin_amdgcn_s_barrier();         // unit u's rows are in buf
     const int halo = halo_c;
     halo_c = valid(u + nwg) ? count_of(j + 1) : -2;
-    if (kT16Bufs == 2 && halo_c > -2) issue(u + nwg, j + 1, halo_c, lds + (par ^ 1) * kT16LdsBuf);
-    if (kT16Bufs == 2 && halo == -2) continue;     // (a padding unit: batch not a multiple of 8)
     if (halo > -2) {
     long long b;
     int k;
@@ -1014,11 +987,8 @@ __global__ __launch_bounds__(256) void csr16t_kernel(T16Args a) {
             if (q < 4) out.lo[q] = x;
             else out.hi[q - 4] = x;
           }
-#ifndef A3VT_T16_NO_NT   // streaming stores: the results are not read again by this launch, and the L2 write-back at its end shrinks (forward 30.9 -> 28.2 us)
+          // streaming stores: the results are not read again by this launch, and the L2 write-back at its end shrinks (forward 30.9 -> 28.2 us)
           __builtin_nontemporal_store(pack8(out), reinterpret_cast<u32x4 *>(a.dst + row * a.ld_dst + ch));
-#else
-          *reinterpret_cast<u32x4 *>(a.dst + row * a.ld_dst + ch) = pack8(out);
-#endif
         }
       }
     };
@@ -1049,12 +1019,11 @@ __global__ __launch_bounds__(256) void csr16t_kernel(T16Args a) {
       __builtin_amdgcn_s_waitcnt(0x0070);
     }
     }   // (unit u valid)
-    if (kT16Bufs == 1 && halo_c > -2) {   // one buffer: the next unit's rows are requested when everyone has left this one's
+    if (halo_c > -2) {   // the next unit's rows are requested when everyone has left this one's
       __builtin_amdgcn_s_barrier();
       issue(u + nwg, j + 1, halo_c, buf);
     }
   }
-  T16_STAMP(3);
   if (BWD) {
     wait_vm<0>();
     __syncthreads();          // (no DMA in flight, nobody reads a buffer any more)
@@ -1070,14 +1039,6 @@ __global__ __launch_bounds__(256) void csr16t_kernel(T16Args a) {
     }
   }
 }
-
-#ifdef A3VT_DBG_T16_STAMPS
-}  // namespace a3vt
-extern "C" int a3vt_dbg_t16_stamps(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(a3vt::g_t16_stamps), sizeof(unsigned long long) * 4096 * 4);
-}
-namespace a3vt {
-#endif
 
 int launch_csr16t_fwd(const void *za, int ldza, const float *bias, int c, const int32_t *plan, const int32_t *rowptr,
                       const int32_t *col, const float *val, int n_vert, int batch, void *y, int ldy, uint8_t *maskb, int mld,

@@ -38,24 +38,6 @@ constexpr int kDStage = kDZ_off + 2816;   // 7680 floats = 30 KiB
 constexpr int kDStages = 4;
 constexpr int kDLdsFloats = kDStages * kDStage;
 
-#ifdef A3VT_DBG_RGW_STAMPS   // diagnostic build (tools/build_variants.sh rgw): s_memtime per stage, [workgroup][wave][stage < 96][2]
-__device__ unsigned long long g_dww_stamps[256 * 4 * 96 * 2];
-#define DWW_STAMP(tl, k)                                                                                       \
-  do {                                                                                                         \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 256 && (tl) < 96)                                              \
-      g_dww_stamps[((blockIdx.x * 4 + (threadIdx.x >> 6)) * 96 + (tl)) * 2 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-// wall-clock (s_memrealtime, 100 MHz) of wave 0 at: kernel entry, first stage, behind the last stage, kernel end
-__device__ unsigned long long g_dww_rt[256 * 4];
-#define DWW_RT(k)                                                                                              \
-  do {                                                                                                         \
-    if (threadIdx.x == 0 && blockIdx.x < 256) g_dww_rt[blockIdx.x * 4 + (k)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define DWW_STAMP(tl, k) do { } while (0)
-#define DWW_RT(k) do { } while (0)
-#endif
-
 // MFMA with the accumulator in an AGPR tuple, operands in VGPRs (see w_mfma in gcn_gemmw.hip)
 // (volatile: the order written below — one fragment read of the NEXT k-step behind every third MFMA — is the schedule)
 __device__ __forceinline__ void d_mfma(f32x4 &acc, float a, float b) {
@@ -224,9 +206,7 @@ __device__ __forceinline__ void dww_wave(const DwArgs &p, float *lds, int lane, 
     (frag(0, std::integral_constant<int, 0>{}, std::integral_constant<int, K>{}, xc, zc), ...);
   }(std::make_integer_sequence<int, NKT + NNT>{});
   d_wait<0>(xc, zc);
-  DWW_RT(1);
   for (int tile = tile0; tile < tile1; ++tile) {
-    DWW_STAMP(tile - tile0, 0);
     auto step = [&](auto sc) {
       constexpr int s = decltype(sc)::value;
       float xn[NKT], zn[NNT];
@@ -255,7 +235,6 @@ __device__ __forceinline__ void dww_wave(const DwArgs &p, float *lds, int lane, 
       // tile + 1's loads were issued before the previous barrier; behind them only tile + 2's (loads return in order)
       wait_vmcnt<NDMA>();
     }
-    DWW_STAMP(tile - tile0, 1);
     wait_lgkm0();
     __builtin_amdgcn_s_barrier();   // tile + 1 is in the ring; everyone has left tile - 1's buffer
     step(std::integral_constant<int, 3>{});
@@ -268,7 +247,6 @@ __device__ __forceinline__ void dww_wave(const DwArgs &p, float *lds, int lane, 
     }
     st = (st + 1) & 3;
   }
-  DWW_RT(2);
   // ---- this workgroup's partial sums -> its half of slab image `image`: dW[k = 16 Tk + l16][n = 16 Tn + 4 q + r]
   asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");   // (the last MFMAs' results: see w_mfma_done in gcn_gemmw.hip)
   float *img = p.slab + (size_t)image * kDK * kDN;
@@ -296,7 +274,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // 16-row tiles of this row group (the groups of a half differ by at most one tile)
   const int tiles = p.m / kDStageRows;
   const int t0 = (int)((long long)group * tiles / ngroups), t1 = (int)((long long)(group + 1) * tiles / ngroups);
-  DWW_RT(0);
   if (half == 1 && group < kDwwGroupsA - kDwwGroupsB) {
     float *img = p.slab + (size_t)(kDwwGroupsB + group) * kDK * kDN;
     for (int i = threadIdx.x; i < kDK * 35; i += 256) {
@@ -315,31 +292,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     else if (wave == 2) dww_wave<1, true, 5, false, 10>(p, lds, lane, t0, t1, group);
     else dww_wave<1, true, 4, true, 15>(p, lds, lane, t0, t1, group);
   }
-  DWW_RT(3);
 }
 
 // The shape this kernel takes: exact fp32, a hidden layer of a stack on hybrid rows (dw_kernel<fast, hybrid>'s), enough rows.
 bool dww_ok(const DwArgs &a) {
-#ifdef A3VT_DBG_DWW_OFF   // variant build (tools/build_variants.sh rgw): dw_kernel everywhere, for A/B timing
-  return false;
-#endif
   if (a.mode != GEMM_FP32 || a.xq_nvert <= 0 || a.z0q_nvert != a.xq_nvert || a.xq == nullptr) return false;
   if (a.k_in != kDK || a.n_out != kDN || a.xq_quads != kDXQ || a.z0q_quads != kDZQ || a.zsplit != 4 * kDZQ) return false;
   if (a.ldx_src != kDXRW || a.ldz1 != kDLdz || a.m % a.xq_nvert != 0 || a.m % kDStageRows != 0 || a.xq_nvert < 16) return false;
   if (a.m > 3000000) return false;                    // 32-bit byte offsets inside every array
   return a.m / kDStageRows >= kDwwGroupsA * 5;        // at least five stages per row group (12 288 rows: where hybrid rows start)
 }
-
-#ifdef A3VT_DBG_RGW_STAMPS
-}  // namespace a3vt
-extern "C" int a3vt_dbg_dww_stamps(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(a3vt::g_dww_stamps), sizeof(unsigned long long) * 256 * 4 * 96 * 2);
-}
-extern "C" int a3vt_dbg_dww_rt(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(a3vt::g_dww_rt), sizeof(unsigned long long) * 256 * 4);
-}
-namespace a3vt {
-#endif
 
 int dww_images() { return kDwwGroupsA; }
 

@@ -9,7 +9,6 @@
 // Both use v_mfma_f32_16x16x4_f32 (exact fp32 fma chain, 64 FLOP/clk/SIMD — MI355X_MICROARCH.md
 // "Matrix cores"), operands staged HBM/L2 -> LDS with LDS-DMA (global_load_lds_dwordx4), counted
 // vmcnt waits and raw s_barrier so the next chunk's DMA stays in flight under the MFMAs.
-#include <stdlib.h>
 #include <type_traits>
 
 #include "common.h"
@@ -17,21 +16,6 @@
 #include "gemm_tile.h"
 
 namespace a3vt {
-
-
-#ifdef A3VT_DBG_RG_STAMPS   // diagnostic build (tools/build_variants.sh stamps): s_memrealtime (100 MHz) at the phase boundaries
-__device__ unsigned long long g_rg_stamps[2 * 256 * 64];   // [real time | shader cycles][workgroup][round (<= 8)][8]; a3vt_dbg_rg_stamps
-#define RG_STAMP(round, k)                                                                                   \
-  do {                                                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x < 256 && blockIdx.y == 0 && (round) < 8) {                            \
-      g_rg_stamps[blockIdx.x * 64 + (round) * 8 + (k)] = __builtin_amdgcn_s_memrealtime();                   \
-      g_rg_stamps[256 * 64 + blockIdx.x * 64 + (round) * 8 + (k)] = __builtin_amdgcn_s_memtime();            \
-    }                                                                                                        \
-  } while (0)
-#else
-#define RG_STAMP(round, k) do { } while (0)
-#endif
-
 
 // ------------------------------------------------------------------------------------------------
 // rowgemm: persistent workgroups; the M rows are cut into 16-row tiles that are dealt evenly to the
@@ -106,9 +90,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
     brow[j] = p.bt + (size_t)br * p.ldb;
   }
 
-  int rnd_ = 0;
-  for (int tb = t0; tb < t1; tb += MT * WAVES, ++rnd_) {
-    RG_STAMP(rnd_, 0);
+  for (int tb = t0; tb < t1; tb += MT * WAVES) {
     // tiles of this round for this wave: two each when the round is full, an even split otherwise
     const int cnt = t1 - tb < MT * WAVES ? t1 - tb : MT * WAVES;
     const int base = cnt / WAVES, extra = cnt % WAVES;
@@ -144,12 +126,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
     auto issue_piece = [&](int chunk, auto bufc, int piece) {
       const int buf = bufc;
       const int kk = chunk * 16 + ((ADIRECT && piece < A_INSTR) ? q * 4 : kpiece);
-#ifdef A3VT_DBG_RG_NOA   // timing-only ablations (tools/build_variants.sh rowgemm): results are wrong by design
-      if (piece < A_INSTR) return;
-#endif
-#ifdef A3VT_DBG_RG_NOB
-      if (piece >= A_INSTR) return;
-#endif
       if (piece < A_INSTR) {
         float *sA = lds + buf * STAGE + wave * (MT * 256);
         const float *src =
@@ -213,16 +189,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
         else wait_vmcnt<0>();
       }
       __builtin_amdgcn_s_barrier();  // chunk t visible to all waves; everyone is done with chunk t-1's stage
-      if (t == 0) RG_STAMP(rnd_, 1);
-      if (t == 1) RG_STAMP(rnd_, 5);
       // Chunk t+DIST goes to stage (t-1) % NSTAGE, free since the barrier above.  With enough n-tile pairs its DMA
       // instructions are spread through the MFMA stream below so their issue cost hides under the matrix pipe.
       constexpr int NPAIR = (NT + 1) / 2;
-#ifdef A3VT_DBG_RG_NOSPREAD   // timing experiment: the whole next chunk is issued right after the barrier
-      constexpr bool SPREAD = false;
-#else
       constexpr bool SPREAD = NPAIR >= 2 * PER;
-#endif
       const bool prefetch = t + DIST < nchunks;
       auto nbuf = [&] {   // stage of chunk t + DIST = the one freed by the barrier above (a constant when buf is)
         if constexpr (ADIRECT) return RgIdx<(decltype(bufc)::value + NSTAGE - 1) % NSTAGE>{};
@@ -335,26 +305,19 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
     }
     wait_lgkm0();
     __builtin_amdgcn_s_barrier();  // all waves finished reading the ring -> reuse it for the epilogue
-    RG_STAMP(rnd_, 2);
 
     // Epilogue.  C/D layout of the 16x16 MFMA: col = lane & 15, row = (lane >> 4) * 4 + reg — a lane holds 4 rows
     // of one column, so direct stores would be 64-byte fragments.  Each wave transposes its accumulators through
     // a private slice of the idle ring and moves whole rows with 16-byte accesses; the fused ReLU / raw-Z split
     // (forward) and the ReLU-sign multiply (backward, bytes already in LDS) happen on the way out.
-#ifdef A3VT_DBG_RG_NOEPI
-    if (active && acc[0][0][0] == 1.2345e-33f) {   // never true in practice: keeps the accumulators alive, skips the epilogue
-#else
     if (active) {
-#endif
       // The epilogue's per-lane address arithmetic depends on the lane alone, so the compiler hoists it in front of the round
       // loop and spills it across the K loop (the forward instantiation sat at 256 registers with 9 spilled): the reloads
       // then sit between the epilogue's global stores, and a scratch reload waits — on the one vmcnt counter — for every
       // store issued before it (round 4: that, not the instruction mix, made the forward launch slower than dX).  An opaque
       // copy of the lane index keeps the arithmetic here, where the operand registers are free again.  Same values.
       int le = lane;
-#ifndef A3VT_DBG_RG_HOISTED_EPI   // variant build (tools/build_variants.sh epi): the round-3 code generation, for A/B timing
       asm volatile("" : "+v"(le));
-#endif
       const int l16 = le & 15, q = le >> 4;
       float *ep = lds + wave * ((NSTAGE * STAGE) / WAVES);
       constexpr int G0 = (NT + 1) / 2;  // n-tiles in the first column group (second gets NT - G0)
@@ -395,9 +358,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
               if (row >= p.m || col >= p.ldc) continue;
               f32x4 v[2] = {*reinterpret_cast<const f32x4 *>(ep + rl * stride + c8 * 8),
                             *reinterpret_cast<const f32x4 *>(ep + rl * stride + c8 * 8 + 4)};
-#ifdef A3VT_DBG_RG_NOSTORE   // timing-only: the LDS transposition runs, the global stores do not
-              if (v[0][0] != 1.2345e-33f) continue;
-#endif
               u16 *yo = reinterpret_cast<u16 *>(p.c) + (size_t)row * p.ldc + col;
               if (EPI == EPI_FWD_HIDDEN) {
                 if (p.maskb) {
@@ -465,9 +425,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
             float *qbase = p.c2 + ((size_t)bq * nqz * p.zq_nvert + (size_t)(row - bq * p.zq_nvert)) * 4;
             for (int c4 = le >> 4; c4 < nqz; c4 += 4) {
               const f32x4 v = *reinterpret_cast<const f32x4 *>(ep + rl * stride + c4 * 4);
-#ifdef A3VT_DBG_RG_NOSTORE
-              if (v[0] != 1.2345e-33f) continue;
-#endif
               if (row < p.m) *reinterpret_cast<f32x4 *>(qbase + (size_t)c4 * p.zq_nvert * 4) = v;
             }
             qlo = nqz;   // the quad-major columns [0, 4 Q) belong to the aggregation kernels alone (RowGemmArgs::zq_nvert)
@@ -488,9 +445,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
                   if (mask_rows) mslot[(i * 16 + rl) * p.mld + p.moff + c4] = (uint8_t)bits;
                   else p.maskb[(size_t)row * p.mld + p.moff + c4] = (uint8_t)bits;
                 }
-#ifdef A3VT_DBG_RG_NOSTORE
-                if (v[0] != 1.2345e-33f) continue;
-#endif
                 *reinterpret_cast<f32x4 *>(ybase + (size_t)c4 * p.zq_nvert * 4) = v;
               }
               qlo = p.yq_quads;
@@ -503,9 +457,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
             const int col = col0 + j0 * 16 + c4 * 4;
             if (row >= p.m || col >= p.n_store) continue;
             f32x4 v = *reinterpret_cast<const f32x4 *>(ep + rl * stride + c4 * 4);
-#ifdef A3VT_DBG_RG_NOSTORE
-            if (v[0] != 1.2345e-33f) continue;
-#endif
             const bool full = vec_ok && col + 3 < p.n_store;
             if (EPI == EPI_PLAIN) {
               float *dst = p.c + (size_t)row * p.ldc + col;
@@ -581,10 +532,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
           *reinterpret_cast<f32x4 *>(dstm + o) = *reinterpret_cast<const f32x4 *>(mslot + o);
       }
     }
-    RG_STAMP(rnd_, 3);
     wait_lgkm0();
     __builtin_amdgcn_s_barrier();  // epilogue slices are free again before the next round's DMA
-    RG_STAMP(rnd_, 4);
   }
   // Leftover rows of the load-balanced split (a few 16-row tiles): one 16 x 16 output tile per wave, dealt across the
   // workgroups, operands straight from global memory (rowtile_unit) — a couple of microseconds at the end of this launch
@@ -607,19 +556,9 @@ struct RowGemmCfg {
   static constexpr int BROWS = ((NT * 16 + 16 * WAVES - 1) / (16 * WAVES)) * (16 * WAVES);
 };
 
-#ifdef A3VT_DBG_RG_NSTAGE4   // timing experiment (plain epilogue only: the sign-byte slots do not fit beside a 4-stage ring)
-template <int NT, int EPI>
-struct RowGemmCfgE : RowGemmCfg<NT> {
-  static constexpr int NSTAGE = (EPI == EPI_PLAIN && NT == 19) ? 4 : RowGemmCfg<NT>::NSTAGE;
-};
-#else
-template <int NT, int EPI>
-struct RowGemmCfgE : RowGemmCfg<NT> {};
-#endif
-
 template <int NT, int EPI>
 static int launch_rowgemm_nt(const RowGemmArgs &a, int grid_y, hipStream_t s) {
-  using C = RowGemmCfgE<NT, EPI>;
+  using C = RowGemmCfg<NT>;
   constexpr size_t shmem = (C::NSTAGE * (size_t)(C::WAVES * 2 * 256 + C::BROWS * 16) +
                             (EPI != EPI_PLAIN ? C::WAVES * 1024 : 0)) * sizeof(float);   // + a sign-byte slot per wave
   static_assert(shmem * C::WG_PER_CU <= 160 * 1024, "LDS budget");
@@ -636,12 +575,7 @@ static int launch_rowgemm_nt(const RowGemmArgs &a, int grid_y, hipStream_t s) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
   });
   const int tiles = cdiv(a.m, 16);
-#ifdef A3VT_DBG_ENV   // variant builds only (tools/build_variants.sh env): the shipped library reads no environment variable
-  static const int env_wg = getenv("A3VT_RG_MAXWG") ? atoi(getenv("A3VT_RG_MAXWG")) : 0;  // developer override (experiments)
-#else
-  constexpr int env_wg = 0;
-#endif
-  const int max_wg = env_wg > 0 ? env_wg : 256 * C::WG_PER_CU;
+  const int max_wg = 256 * C::WG_PER_CU;
   // one tile per wave until every CU has a workgroup; beyond that the kernel deals tiles evenly (two per wave per round)
   const int grid = cdiv(tiles, C::WAVES) < max_wg ? cdiv(tiles, C::WAVES) : max_wg;
   if (a.mode == GEMM_BF16_STORAGE)
@@ -650,13 +584,8 @@ static int launch_rowgemm_nt(const RowGemmArgs &a, int grid_y, hipStream_t s) {
     A3VT_LAUNCH((rowgemm_kernel<NT, EPI, C::NSTAGE, C::WAVES, 1>), dim3(grid, grid_y), dim3(64 * C::WAVES), shmem, s, a);
   else {
     // the exact fp32 products of the full-width layers take their A operand straight into registers (ADIRECT)
-#ifdef A3VT_DBG_RG_ADIRECT_OFF   // variant build (tools/build_variants.sh adirect): A through the LDS ring everywhere
-    constexpr bool via_lds = true;
-#else
-    constexpr bool via_lds = false;
-#endif
-    if (NT == 19 && !via_lds) path_count(PATH_RG_ADIRECT);
-    if (NT == 19 && !via_lds)
+    if (NT == 19) path_count(PATH_RG_ADIRECT);
+    if (NT == 19)
       A3VT_LAUNCH((rowgemm_kernel<NT, EPI, C::NSTAGE, C::WAVES, 0, NT == 19>), dim3(grid, grid_y), dim3(64 * C::WAVES), shmem, s, a);
     else
       A3VT_LAUNCH((rowgemm_kernel<NT, EPI, C::NSTAGE, C::WAVES, 0>), dim3(grid, grid_y), dim3(64 * C::WAVES), shmem, s, a);
@@ -683,36 +612,10 @@ static int launch_rowgemm_cols(const RowGemmArgs &a, hipStream_t s) {
   return launch_rowgemm_nt<19, EPI>(a, cdiv(nt, 19), s);
 }
 
-// ------------------------------------------------------------------------------------------------
-// rowtile: the same product for a handful of rows (the remainder of the load-balanced split below: 128 rows at
-// bs 64).  With so little work the ring kernel is pure latency (19 dependent DMA round trips, 12.7 us per launch,
-// 111 launches per step), so here every wave owns ONE 16 x 16 output tile and pulls its operands straight from
-// global memory into registers — all loads of up to 19 K-chunks in flight at once, no LDS, no barrier — then runs
-// the MFMA chain: one round trip instead of nineteen.  Same arithmetic order along K as rowgemm_kernel.
-// grid = (column tiles, row tiles / 4), 4 waves per workgroup.
-// ------------------------------------------------------------------------------------------------
-template <int EPI, int MODE>
-__global__ __launch_bounds__(256) void rowtile_kernel(RowGemmArgs p) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mt = blockIdx.y * 4 + wave;
-  if (mt * 16 >= p.m) return;
-  rowtile_unit<EPI, MODE>(p, 0, p.m, mt, p.col0 + blockIdx.x * 16, lane);
-}
-
-template <int EPI>
-static int launch_rowtile(const RowGemmArgs &a, hipStream_t s) {
-  const dim3 grid(cdiv(a.n_store, 16), cdiv(cdiv(a.m, 16), 4));
-  if (a.mode == GEMM_BF16_STORAGE) A3VT_LAUNCH((rowtile_kernel<EPI, 2>), grid, dim3(256), 0, s, a);
-  else if (a.mode == GEMM_BF16_OPERANDS) A3VT_LAUNCH((rowtile_kernel<EPI, 1>), grid, dim3(256), 0, s, a);
-  else A3VT_LAUNCH((rowtile_kernel<EPI, 0>), grid, dim3(256), 0, s, a);
-  A3VT_CHECK_LAUNCH();
-  return 0;
-}
-
 // Load balance.  The chip runs 2048 waves of this kernel at once (256 CUs x 4 SIMDs x 2), each owning 16-row
 // tiles in pairs; M = 163,968 rows = 10,248 tiles would leave almost every SIMD idle while a few run a sixth
 // tile pair (+20 % time).  When such a small remainder exists, the tiles that fill whole rounds go to the main
-// launch and the leftover rows go to rowtile_kernel: one 16 x 16 tile per wave, operands from registers.
+// launch and the leftover rows run in its tail (rowtile_unit): one 16 x 16 tile per wave, operands from registers.
 template <int EPI>
 static int launch_rowgemm_epi(const RowGemmArgs &a0, hipStream_t s) {
   RowGemmArgs a = a0;
@@ -723,33 +626,10 @@ static int launch_rowgemm_epi(const RowGemmArgs &a0, hipStream_t s) {
   if (full == 0 || rem == 0 || rem * nt > 1024 || nt < 2) return launch_rowgemm_cols<EPI>(a, s);
   RowGemmArgs m = a;
   m.m = full * 16;
-#ifdef A3VT_DBG_ENV
-  static const bool separate = getenv("A3VT_ROWTILE_SEPARATE") != nullptr;  // developer switch: remainder as its own launch
-#else
-  constexpr bool separate = false;
-#endif
-  if (!separate) {
-    m.rem_row0 = full * 16;
-    m.rem_rows = a.m - full * 16;
-    return launch_rowgemm_cols<EPI>(m, s);
-  }
-  if (int rc = launch_rowgemm_cols<EPI>(m, s)) return rc;
-  RowGemmArgs r = a;
-  const size_t r0 = (size_t)full * 16;
-  r.m = a.m - (int)r0;
-  r.a0 = a.a0 + r0 * a.lda0;
-  r.a1 = a.a1 + r0 * a.lda1;
-  r.c = a.c + r0 * a.ldc;
-  if (a.c2) r.c2 = a.c2 + r0 * a.ldc2;
-  if (a.maskb) r.maskb = a.maskb + r0 * a.mld;
-  return launch_rowtile<EPI>(r, s);
+  m.rem_row0 = full * 16;
+  m.rem_rows = a.m - full * 16;
+  return launch_rowgemm_cols<EPI>(m, s);
 }
-
-#ifdef A3VT_DBG_RG_STAMPS
-extern "C" int a3vt_dbg_rg_stamps(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_rg_stamps), sizeof(unsigned long long) * 2 * 256 * 64);
-}
-#endif
 
 // Rows of Bt the kernel stages for a given n (must exist, zero padded, in the Bt buffer).
 int rowgemm_bt_rows(int n_store) {
@@ -792,9 +672,7 @@ int launch_rowgemm(const RowGemmArgs &a, int epi, hipStream_t s) {
     return -1;
   }
   if (rowgemmw_ok(a, epi)) return launch_rowgemmw(a, epi, s);
-#ifndef A3VT_DBG_ROWGEMM16_OFF   // (variant build, tools/build_variants.sh adirect: the bf16 storage mode on rowgemm_kernel)
   if (rowgemm16_ok(a, epi)) return launch_rowgemm16(a, epi, s);
-#endif
   switch (epi) {
     case EPI_PLAIN: return launch_rowgemm_epi<EPI_PLAIN>(a, s);
     case EPI_FWD_HIDDEN: return launch_rowgemm_epi<EPI_FWD_HIDDEN>(a, s);
@@ -924,20 +802,12 @@ __device__ __forceinline__ void dw_stage(const float *__restrict__ sb, int ldx, 
     const float *xr = sb + r * ldx + xoff;
     const int ra = z0q ? ((r + rot) & 15) * 4 : r * ldz0, rg = r * ldz1;   // z0q: blocked dZa window, see dw_kernel
     float a[DW_MAXI], b[DW_MAXO];
-#ifdef A3VT_DBG_NOLDSREAD
-#pragma unroll
-    for (int i = 0; i < DW_MAXI; ++i) a[i] = (float)(r + i);
-#pragma unroll
-    for (int j = 0; j < DW_MAXO; ++j) b[j] = (float)(ra + j);
-    (void)xr; (void)rg;
-#else
     // unconditional loads (tiles a wave does not own read a few floats past its window, inside the stage, and are
     // never multiplied): conditional ones become branches and early lgkmcnt waits, see dw_stage_fast
 #pragma unroll
     for (int i = 0; i < DW_MAXI; ++i) a[i] = xr[i * 16];
 #pragma unroll
     for (int j = 0; j < DW_MAXO; ++j) b[j] = sb[zoff[j] + (zoff[j] < offG ? ra : rg)];
-#endif
 #pragma unroll
     for (int i = 0; i < DW_MAXI; ++i) {
       if (NI >= 0 ? i < NI : i < ni) {
@@ -971,13 +841,6 @@ __device__ __forceinline__ void dw_stage_fast(const float *__restrict__ sb, int 
     const float *xr = sb + r * ldx + xoff;
     const int rq = ((r + rot) & 15) * 4;   // row term inside a 16-column block (dw_kernel: row r of quad qd at slot (r + qd) & 15)
     const int ra = HYB && z0q ? rq : r * ldz0, rg = r * ldz1;
-#ifdef A3VT_DBG_NOLDSREAD
-#pragma unroll
-    for (int i = 0; i < DW_MAXI; ++i) av[i] = (float)(r + i);
-#pragma unroll
-    for (int j = 0; j < DW_MAXO; ++j) bv[j] = (float)(ra + j);
-    (void)xr; (void)rg;
-#else
     // All five / three operand loads are unconditional: a wave without a 5th row tile or 3rd column tile reads a few
     // floats past its window (still inside the stage) and never uses them.  Selecting the address instead
     // ("i < 4 || row5 ? i : 3") made the compiler reuse the loaded a[3] through a v_mov, i.e. wait for the NEXT
@@ -993,7 +856,6 @@ __device__ __forceinline__ void dw_stage_fast(const float *__restrict__ sb, int 
     }
 #pragma unroll
     for (int j = 0; j < DW_MAXO; ++j) bv[j] = sb[zoff[j] + (zoff[j] < offG ? ra : rg)];
-#endif
   };
   load(0, a, b);
 #pragma unroll
@@ -1211,7 +1073,6 @@ __global__ __launch_bounds__(1024, 1) void dw_kernel(DwArgs p) {
   auto advance = [&](int unit) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) sp[j] += sstep[j];
-#ifndef A3VT_DBG_DW_NOWRAP   // timing-only ablation: no mesh-boundary bookkeeping (wrong addresses past the first mesh)
     if (HYB && unit * 16 + 31 >= next_mesh) {   // wave-uniform
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
@@ -1220,7 +1081,6 @@ __global__ __launch_bounds__(1024, 1) void dw_kernel(DwArgs p) {
       }
       if (unit * 16 + 16 >= next_mesh) next_mesh += qn;
     }
-#endif
   };
   auto issue = [&](int unit, int buf) {
     float *base = lds + buf * stage;
@@ -1266,12 +1126,8 @@ __global__ __launch_bounds__(1024, 1) void dw_kernel(DwArgs p) {
     else if (younger == 2) wait_vmcnt<6>();
     else if (younger == 1) wait_vmcnt<3>();
     else wait_vmcnt<0>();
-#ifndef A3VT_DBG_NOBARRIER
     __builtin_amdgcn_s_barrier();
-#endif
-#ifndef A3VT_DBG_NODMA
     if (t + nst - 1 < nu) issue(u0 + t + nst - 1, buf >= 1 ? buf - 1 : nst - 1);
-#endif
     const float *sb = lds + buf * stage;
     if constexpr (NARROW) {
       dw_stage_narrow<HYB>(sb, p.ldx, wa, wg, offG, xoff, zoff, q, no == 3, z0q, rot, acc);
@@ -1283,15 +1139,8 @@ __global__ __launch_bounds__(1024, 1) void dw_kernel(DwArgs p) {
     else if (FAST && HYB) {
       // a wave's five input tiles are all blocks or all columns of the row-major image (launch_dw): two copies of the stage
       // so that every operand read keeps an immediate tile offset
-#if defined(A3VT_DBG_DW_ARM)      // timing-only bisection: every wave reads its A operand as from the row-major image
-      dw_stage_fast<true, false>(sb, wrm, wa, wg, offG, xoff & 0xfff, zoff, q, true, no == 3, xo, z0q, rot, acc);
-#elif defined(A3VT_DBG_DW_BRM)    // timing-only bisection: B operand row term of the compact image
-      if (xo >= 0) dw_stage_fast<true, true>(sb, wrm, wa, wg, offG, xoff, zoff, q, true, no == 3, xo, false, rot, acc);
-      else dw_stage_fast<true, false>(sb, wrm, wa, wg, offG, xoff, zoff, q, true, no == 3, xo, false, rot, acc);
-#else
       if (xo >= 0) dw_stage_fast<true, true>(sb, wrm, wa, wg, offG, xoff, zoff, q, true, no == 3, xo, z0q, rot, acc);
       else dw_stage_fast<true, false>(sb, wrm, wa, wg, offG, xoff, zoff, q, true, no == 3, xo, z0q, rot, acc);
-#endif
     } else if (FAST) dw_stage_fast<false, false>(sb, p.ldx, wa, wg, offG, xoff, zoff, q, true, no == 3, xo, z0q, rot, acc);
     else dw_stage<-1, -1>(sb, p.ldx, wa, wg, offG, xoff, zoff, q, ni, no, z0q, rot, acc);
     }
@@ -1332,10 +1181,6 @@ int dw_slab_capacity(int n_out) { return dw_num_slabs(n_out) > dww_images() ? dw
 int launch_dw(const DwArgs &a0, hipStream_t s) {
   if (a0.mode == GEMM_FP32X3) return launch_dw3(a0, s);   // split-operand mode (gcn_gemm3.hip)
   DwArgs a = a0;
-#ifdef A3VT_DBG_DW_NOHYB   // timing-only: the plain kernel on the same buffers (wrong results)
-  a.xq = nullptr; a.xq_nvert = a.xq_quads = a.z0q_nvert = a.z0q_quads = 0; a.ldx_src = 0;
-  if (a.ldz0 < a.zsplit) a.ldz0 = a.zsplit;
-#endif
   if (a.ldx_src == 0) a.ldx_src = a.ldx;
   if ((a.xq_nvert > 0 && (a.xq == nullptr || a.xq_quads * 4 > a.k_in || a.m % a.xq_nvert != 0)) ||
       (a.z0q_nvert > 0 && (a.z0q_quads * 4 != a.zsplit || a.m % a.z0q_nvert != 0)) ||

@@ -72,17 +72,6 @@ __device__ __forceinline__ void wait_younger(int n) {
   }
 }
 
-#ifdef A3VT_DBG_R16_STAMPS   // diagnostic build (tools/build_variants.sh stamps16): s_memrealtime (100 MHz) at the phase boundaries
-__device__ unsigned long long g_r16_stamps[2 * 256 * 16 * 8];   // [epilogue][workgroup][block (< 16)][8]; a3vt_dbg_r16_stamps
-#define R16_STAMP(w, k)                                                                                      \
-  do {                                                                                                       \
-    if (wave == (w) && lane == 0 && blockIdx.x < 256 && b < 16)                                              \
-      g_r16_stamps[(((EPI == EPI_DX_MASK ? 1 : 0) * 256 + blockIdx.x) * 16 + b) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define R16_STAMP(w, k) do { } while (0)
-#endif
-
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -98,10 +87,6 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
   const int nt = (p.n_store + 15) >> 4;
   const bool third = wave + 16 < nt;                         // wave-uniform: this wave owns a third column tile
 
-#ifdef A3VT_DBG_R16_STAMPS
-  if (threadIdx.x == 0 && blockIdx.x < 256)   // kernel entry (block slot 15 of the stamp array)
-    g_r16_stamps[(((EPI == EPI_DX_MASK ? 1 : 0) * 256 + blockIdx.x) * 16 + 15) * 8] = __builtin_amdgcn_s_memrealtime();
-#endif
   // blocks of kRows rows, dealt evenly to the workgroups
   const int nblk_all = (p.m + kRows - 1) / kRows;
   const int bbase = nblk_all / gridDim.x, brem = nblk_all % gridDim.x;
@@ -167,11 +152,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
     const float *brow = p.bt + (size_t)br * p.ldb + q * 4;
 #pragma unroll
     for (int s = 0; s < kKS; ++s) {
-#ifdef A3VT_DBG_R16_NOB   // timing-only: what the weight loads cost the prologue (results are wrong by design)
-      bfrag[jt][s] = f32x4{1.f + s, 2.f + jt, 3.f + lane, 4.f};
-#else
       bfrag[jt][s] = *reinterpret_cast<const f32x4 *>(brow + s * 16);
-#endif
     }
   }
   // (the B loads of waves 0-3 are younger than their first two blocks' DMA: the first counted wait below covers them
@@ -182,21 +163,18 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
   u16 *z16 = reinterpret_cast<u16 *>(p.c2);
   for (int b = 0; b < nblk; ++b) {
     const int stage = b % kStages;
-    R16_STAMP(0, 0);
     if (dma_wave && b > 0) {
       // block b (its A pieces and its sign bytes) landed; the A pieces of block b + 1, issued after them, may be in flight
       // (... and so may this wave's stores of block b-1, issued after them: one counter, retired in issue order)
       if (b + 1 < nblk) wait_younger(mine_a + store_instr);
       else wait_vmcnt<0>();
     }
-    R16_STAMP(0, 1);
     __builtin_amdgcn_s_barrier();   // block b visible; everyone is done with block b-1: its ring stage, the output tile, its sign slot
     // sign bytes of block b + 1 (slot (b + 1) & 1 was block b-1's) now; the A pieces of block b + 2 (into block b-1's stage)
     // one per k-step inside the MFMA stream below, where their issue cost hides under the matrix pipe
     if (dma_wave && EPI == EPI_DX_MASK && b + 1 < nblk) issue_mask(b + 1);
     const bool feed = dma_wave && b + 2 < nblk;
 
-    R16_STAMP(0, 2);
     // ---- K phase: 3 row tiles x 10 k-steps x this wave's 2-3 column tiles ------------------------------------------
     const float *sA = lds + stage * kStage + l16 * 16 + qs * 4;
     f32x4 acc[kRT][3];
@@ -231,7 +209,6 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
 #pragma unroll
       for (int rt = 0; rt < kRT; ++rt) a[rt] = an[rt];
     }
-    R16_STAMP(0, 3);
     // ---- accumulators -> fp32 tile [48][308] (C/D layout: col = lane & 15, row = 4 (lane >> 4) + reg) ---------------
 #pragma unroll
     for (int jt = 0; jt < 3; ++jt) {
@@ -243,10 +220,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
         for (int r = 0; r < 4; ++r) ep[(rt * 16 + q * 4 + r) * kEpLd + col] = acc[rt][jt][r];
     }
     wait_lgkm0();
-    R16_STAMP(0, 4);
     __builtin_amdgcn_s_barrier();   // output tile complete
-    R16_STAMP(0, 5);
-    R16_STAMP(4, 6);
 
     // ---- store phase: every wave takes 6 rows; lane = 8-column group (38 of 64 lanes for 304 columns), so a lane's
     // column class (aggregated / straddling the cut / pass-through) is fixed and the loop body is straight-line code:
@@ -307,7 +281,6 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
         }
       }
       wait_lgkm0();   // this wave's reads of the output tile and the sign slot are done before it reaches the next barrier
-      R16_STAMP(4, 7);
     }
   }
 }
@@ -328,12 +301,6 @@ bool rowgemm16_ok(const RowGemmArgs &a, int epi) {
   }
   return true;
 }
-
-#ifdef A3VT_DBG_R16_STAMPS
-extern "C" int a3vt_dbg_r16_stamps(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_r16_stamps), sizeof(unsigned long long) * 2 * 256 * 16 * 8);
-}
-#endif
 
 int launch_rowgemm16(const RowGemmArgs &a0, int epi, hipStream_t s) {
   RowGemmArgs a = a0;

@@ -47,11 +47,8 @@ constexpr int kPieces = 3 * kNT;        // LDS-DMA pieces (1 KiB: 16 Bt rows x 6
 constexpr int kStage = kPieces * 256;   // floats per ring stage (58,368 B)
 constexpr int kStages = 2;
 constexpr int kMSlot = 1024;            // floats (4 KiB) of ReLU-sign bytes per wave
-#ifdef A3VT_DBG_RG3_DMA4   // variant (measured 5-8 % slower): waves 0-3, one per SIMD, carry all of the Bt staging
-constexpr int kDmaWaves = 4;
-#else
-constexpr int kDmaWaves = 8;            // the Bt pieces are dealt to all eight waves (8 / 7 per wave and chunk)
-#endif
+constexpr int kDmaWaves = 8;            // the Bt pieces are dealt to all eight waves (8 / 7 per wave and chunk; waves 0-3
+                                        // alone measured 5-8 % slower)
 constexpr int kBPer = (kPieces + kDmaWaves - 1) / kDmaWaves;   // Bt pieces per DMA wave and chunk
 constexpr size_t kLdsBytes = (size_t)(kStages * kStage + kWaves * kMSlot) * sizeof(float);   // 149,504 B
 static_assert(kLdsBytes <= 160 * 1024, "LDS budget");
@@ -61,10 +58,6 @@ __device__ __forceinline__ void glds16(const float *gsrc, float *lds_wave_base) 
                                    (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
 }
 __device__ __forceinline__ f32x4 mfma(f32x4 a, f32x4 b, f32x4 c) {
-#ifdef A3VT_DBG_X3_NOMFMA   // timing-only ablations of this file (tools/build_variants.sh x3): results are wrong by design
-  asm volatile("" ::"v"(a), "v"(b));
-  return c;
-#endif
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -83,10 +76,6 @@ __device__ __forceinline__ unsigned cvt_pk(float a, float b) {   // v_cvt_pk_bf1
 // down to 2^-110 qualify); below that the difference is < 2^-133.  11 VALU instructions per pair.
 __device__ __forceinline__ void split3_pair(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
   const unsigned ua = fbits(a), ub = fbits(b);
-#ifdef A3VT_DBG_X3_NOSPLIT
-  h = ua; m = ub; l = ua ^ ub;
-  return;
-#endif
   h = __builtin_amdgcn_perm(ub, ua, 0x07060302u);            // (ua >> 16) | (ub & 0xffff0000)
   const float ra = a - bfloat(ua & 0xffff0000u), rb = b - bfloat(ub & 0xffff0000u);
   m = cvt_pk(ra, rb);
@@ -197,20 +186,6 @@ __device__ __forceinline__ void rowtile3_unit(const RowGemmArgs &p, int row_base
   }
 }
 
-#ifdef A3VT_DBG_RG3_STAMPS   // diagnostic build (tools/build_variants.sh stamps3): s_memrealtime (100 MHz) + s_memtime at the phase boundaries
-__device__ unsigned long long g_rg3_stamps[2 * 2 * 256 * 4 * 8];   // [real time | shader cycles][epilogue][workgroup][round (< 4)][8]
-#define RG3_STAMP(round, k)                                                                                                  \
-  do {                                                                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x < 256 && (round) < 4) {                                                               \
-      const int i_ = (((EPI == EPI_DX_MASK ? 1 : 0) * 256 + blockIdx.x) * 4 + (round)) * 8 + (k);                            \
-      g_rg3_stamps[i_] = __builtin_amdgcn_s_memrealtime();                                                                   \
-      g_rg3_stamps[2 * 256 * 4 * 8 + i_] = __builtin_amdgcn_s_memtime();                                                     \
-    }                                                                                                                        \
-  } while (0)
-#else
-#define RG3_STAMP(round, k) do { } while (0)
-#endif
-
 template <int EPI>
 __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -266,18 +241,14 @@ __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p)
         int kk = chunk * 32 + q * 8 + h * 4;
         kk = kk < p.k ? kk : p.k - 4;
         const float *src = kk < p.ksplit ? p.a0 + (size_t)(a0off[i] + (unsigned)kk * a0mul) : p.a1 + (size_t)(a1off[i] + (unsigned)kk);
-#ifdef A3VT_DBG_RG3_NOA
-        raw[i][h] = f32x4{1.f + kk, 2.f + i, 3.f + lane, (float)(size_t)src};
-#else
         raw[i][h] = *reinterpret_cast<const f32x4 *>(src);
-#endif
       }
   };
 
-  int rnd_ = 0;
-  bool a_ahead = false;   // the first A elements of this round were requested before the previous round's epilogue
-  for (int tb = t0; tb < t1; tb += kMT * kWaves, ++rnd_) {
-    RG3_STAMP(rnd_, 0);
+  // Never set: the first A elements of the next round requested under this round's epilogue measured no faster (see behind
+  // the K loop).  The flag stays because folding it away changes the kernel's block layout.
+  bool a_ahead = false;
+  for (int tb = t0; tb < t1; tb += kMT * kWaves) {
     // tiles of this round for this wave: two each when the round is full, an even split otherwise
     const int cnt = t1 - tb < kMT * kWaves ? t1 - tb : kMT * kWaves;
     const int base = cnt / kWaves, extra = cnt % kWaves;
@@ -294,9 +265,6 @@ __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p)
 
     auto issue_b = [&](int chunk, int buf, int j) {
       if (j >= nbp) return;   // wave-uniform
-#ifdef A3VT_DBG_RG3_NOB
-      return;
-#endif
       const int pc = wave + kDmaWaves * j, img = pc / kNT, tile = pc - img * kNT;   // scalar
       glds16(p.bt + ((size_t)img * kX3ImageFloats + (size_t)tile * (16 * kX3ImageLd) + chunk * 16) + blane, lds + buf * kStage + pc * 256);
     };
@@ -370,8 +338,6 @@ __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p)
       for (int t = 0; t < nchunks; ++t) {
         wait_vm0();                       // chunk t (this wave's share) has landed
         __builtin_amdgcn_s_barrier();     // ... everyone's has; everyone is done with chunk t - 1's stage
-        if (t == 0) RG3_STAMP(rnd_, 1);
-        if (t == 1) RG3_STAMP(rnd_, 5);
         chunk_step(std::integral_constant<int, 2>{}, t);
       }
     } else if (nm == 1) {
@@ -392,33 +358,18 @@ __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p)
     }
     wait_lgkm0();
     __builtin_amdgcn_s_barrier();   // all waves finished reading the ring -> reuse it for the epilogue
-    RG3_STAMP(rnd_, 2);
-#ifdef A3VT_DBG_RG3_AHEAD
-    // Measured, not shipped: the next round's first A elements (HBM-streamed) requested here, into the
-    // free operand registers, land under the epilogue — the first-chunk wait of the next round falls from 6 to 1.2 us and
-    // its K loop grows by the same 5 us (the loads share the CU's memory path with the epilogue's stores).
-    a_ahead = tb + kMT * kWaves < t1;
-    if (a_ahead) {
-      set_rows(tb + kMT * kWaves);
-      issue_a(0);
-    }
-#endif
+    // (requesting the next round's first A elements here, under the epilogue, measured no faster: its K loop grew by what
+    // the first-chunk wait saved; a_ahead)
 
     // ---- epilogue (rowgemm_kernel's, fp32 rows; launch_rowgemm3 guarantees ldc % 4 == 0, n_store % 4 == 0 and, for the
     // forward without the quad-major side output, ldc2 % 4 == 0: every column quad leaves with one 16-byte store)
-#ifdef A3VT_DBG_RG3_NOEPI
-    if (active && acc[0][0][0] == 1.2345e-33f) {   // never true in practice: keeps the accumulators alive, skips the epilogue
-#else
     if (active) {
-#endif
       // The epilogue's per-lane address arithmetic depends on the lane alone, so the compiler hoists it in front of the round
       // loop and then spills it across the K loop (where all 256 registers are taken): the reloads sat between the
       // epilogue's global stores, and a scratch reload waits — on the one vmcnt counter — for every store issued before it.
       // An opaque copy of the lane index keeps that arithmetic here, where registers are free again.
       int le = lane;
-#ifndef A3VT_DBG_RG_HOISTED_EPI   // variant build (tools/build_variants.sh epi): without the fix, for A/B timing
       asm volatile("" : "+v"(le));
-#endif
       const int l16 = le & 15, q = le >> 4;
       float *ep = lds + wave * ((kStages * kStage) / kWaves);
       constexpr int G0 = (kNT + 1) / 2;
@@ -524,10 +475,8 @@ __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p)
           *reinterpret_cast<f32x4 *>(dstm + o) = *reinterpret_cast<const f32x4 *>(mslot + o);
       }
     }
-    RG3_STAMP(rnd_, 3);
     wait_lgkm0();
     __builtin_amdgcn_s_barrier();   // epilogue slices are free again before the next round's DMA
-    RG3_STAMP(rnd_, 4);
   }
   // Leftover rows of the load-balanced split (launch_rowgemm3): one 16 x 16 output tile per wave, dealt across the
   // workgroups, operands straight from global memory — a few microseconds at the end of this launch instead of a lone
@@ -728,9 +677,7 @@ __global__ __launch_bounds__(kDwThreads, 2) void dw3_kernel(DwArgs p) {
 #pragma unroll
       for (int j = 0; j < kDwPer; ++j) {
         if (j * kDwThreads + wave * 64 >= kDwUnits) continue;   // wave-uniform: nothing of this instruction exists
-#ifndef A3VT_DBG_DW3_NODMA
         glds16(sp[j], raw + (j * kDwThreads + wave * 64) * 4);
-#endif
       }
     } else {   // the ragged last stage of the whole problem: rows >= m contribute zeros
 #pragma unroll
@@ -786,9 +733,6 @@ __global__ __launch_bounds__(kDwThreads, 2) void dw3_kernel(DwArgs p) {
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int j = 0; j < kDwPer; ++j) {
-#ifdef A3VT_DBG_DW3_NOSPLITPHASE
-      continue;
-#endif
       if (pdst[j] >= 0) {
         const bool isx = pdst[j] < 3 * kDwXimg;
         u16 *d = pieces + pdst[j];
@@ -866,12 +810,6 @@ __global__ __launch_bounds__(kDwThreads, 2) void dw3_kernel(DwArgs p) {
 }
 
 }  // namespace
-
-#ifdef A3VT_DBG_RG3_STAMPS
-extern "C" int a3vt_dbg_rg3_stamps(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_rg3_stamps), sizeof(unsigned long long) * 2 * 2 * 256 * 4 * 8);
-}
-#endif
 
 int launch_weight_images3(const WeightImages &w, hipStream_t s) {
   A3VT_LAUNCH(weight_images3_kernel, dim3(10, 10, w.count), dim3(32, 8), 0, s, w);

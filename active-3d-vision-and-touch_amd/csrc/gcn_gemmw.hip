@@ -41,24 +41,6 @@ constexpr int kWMaskSlot = 512;              // floats (2 KiB) of sign bytes of 
 // rows ring, two staging slots, sign bytes leaving (2 slots + one nobody reads) and arriving (4 slots + one nobody reads)
 constexpr int kWLdsFloats = (kWStages + 2) * kWStage + (3 + 5) * kWMaskSlot;
 
-#ifdef A3VT_DBG_RGW_STAMPS   // diagnostic build (tools/build_variants.sh rgw): s_memtime per tile phase, [workgroup][wave][tile < 48][4]
-__device__ unsigned long long g_rgw_stamps[256 * 4 * 48 * 4];
-#define RGW_STAMP(tl, k)                                                                                       \
-  do {                                                                                                         \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 256 && (tl) < 48)                                              \
-      g_rgw_stamps[((blockIdx.x * 4 + (threadIdx.x >> 6)) * 48 + (tl)) * 4 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-// wall-clock (s_memrealtime, 100 MHz) of wave 0 at: kernel entry, first tile, behind the last tile, kernel end
-__device__ unsigned long long g_rgw_rt[256 * 4];
-#define RGW_RT(k)                                                                                              \
-  do {                                                                                                         \
-    if (threadIdx.x == 0 && blockIdx.x < 256) g_rgw_rt[blockIdx.x * 4 + (k)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define RGW_STAMP(tl, k) do { } while (0)
-#define RGW_RT(k) do { } while (0)
-#endif
-
 template <int V>
 using WIdx = std::integral_constant<int, V>;
 
@@ -120,10 +102,8 @@ __device__ __forceinline__ void rowgemmw_compute(const RowGemmArgs &p, float *ld
   wait_vmcnt<0>();
   wait_lgkm0();
   __builtin_amdgcn_s_barrier();   // (prologue barrier: the first two tiles' rows are in the ring)
-  RGW_RT(1);
   int st = 0;
   for (int tile = t0; tile < t1; ++tile) {
-    RGW_STAMP(tile - t0, 0);
     const float *sa = sA + st * kWStage + lane * 4;
     float *se = sE + ((tile - t0) & 1) * kWStage + lane * 4;
     f32x4 acc[NT];
@@ -145,15 +125,11 @@ __device__ __forceinline__ void rowgemmw_compute(const RowGemmArgs &p, float *ld
     w_mfma_done();
 #pragma unroll
     for (int t = 0; t < NT; ++t) *reinterpret_cast<f32x4 *>(se + (wave + 3 * t) * 256) = acc[t];
-    RGW_STAMP(tile - t0, 1);
     wait_lgkm0();
-    RGW_STAMP(tile - t0, 2);
     __builtin_amdgcn_s_barrier();   // this tile's results staged; the next tile's rows are in the ring
-    RGW_STAMP(tile - t0, 3);
     st = st == 2 ? 0 : st + 1;
   }
   __builtin_amdgcn_s_barrier();     // (drain barrier: wave 3 has finished the last tile's epilogue)
-  RGW_RT(2);
 }
 
 // ---- wave 3: 4 column tiles, the rows' DMA, every epilogue ------------------------------------------------------------------
@@ -341,7 +317,6 @@ __device__ __forceinline__ void rowgemmw_service(const RowGemmArgs &p, float *ld
   // (the first tile has no predecessor whose epilogue to run: its own instantiation, no branch per chunk in the others)
   auto tile_body = [&](int tile, auto firstc) {
     constexpr bool have_prev = !decltype(firstc)::value;
-    RGW_STAMP(tile - t0, 0);
     const int par = (tile - t0) & 1;
     const bool have_next = tile + 2 < t1;
     const int nst = st == 0 ? 2 : st - 1;             // (st + 2) % 3: the stage tile - 1 has just left
@@ -358,9 +333,7 @@ __device__ __forceinline__ void rowgemmw_service(const RowGemmArgs &p, float *ld
       f32x4 an = af, ev = {0.f, 0.f, 0.f, 0.f};
       unsigned eb = 0;
       if (c + 1 < kWChunks) an = *reinterpret_cast<const f32x4 *>(sa + (c + 1) * 256);
-#ifndef A3VT_DBG_RGW_NOEPI
       if (have_prev) epi_fetch(cc, par ^ 1, (tile - 1) & 3, ev, eb);
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int sidx = 0; sidx < 4; ++sidx) {
@@ -372,12 +345,8 @@ __device__ __forceinline__ void rowgemmw_service(const RowGemmArgs &p, float *ld
       }
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_mov_b32 %0, 0" : "=s"(sz));   // (per chunk: see the declaration)
-#ifndef A3VT_DBG_RGW_NODMA   // timing-only ablations (tools/build_variants.sh rgw): results are wrong by design
       a_issue(cc, nst, have_next);
-#endif
-#ifndef A3VT_DBG_RGW_NOEPI
       if (have_prev) epi(cc, ev, eb);
-#endif
       __builtin_amdgcn_sched_barrier(0);
       af = an;
     };
@@ -391,13 +360,10 @@ __device__ __forceinline__ void rowgemmw_service(const RowGemmArgs &p, float *ld
     advance(d_bq, d_vq);
     refresh_d(tile + 3, tile + 3 < t1);
     if (have_prev) advance(e_bq, e_vq);
-    RGW_STAMP(tile - t0, 1);
     // the rows of tile + 1 were requested a tile ago: everything but this tile's last 24 memory instructions has landed
     wait_vmcnt<24>();
     wait_lgkm0();
-    RGW_STAMP(tile - t0, 2);
     __builtin_amdgcn_s_barrier();
-    RGW_STAMP(tile - t0, 3);
     st = st == 2 ? 0 : st + 1;
   };
   if (t1 > t0) tile_body(t0, std::true_type{});
@@ -432,7 +398,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // the main part: the same number of 16-row tiles for every workgroup; the rest is the launch's tail (below)
   const int per = (p.m >> 4) / (int)gridDim.x;
   const int t0 = blockIdx.x * per, t1 = t0 + per;
-  RGW_RT(0);
   if (wave < 3) rowgemmw_compute<EPI>(p, lds, wave, lane, t0, t1);
   else rowgemmw_service<EPI>(p, lds, lane, t0, t1);
   // ---- leftover tiles of the even split: one 16 x 16 output tile per wave, dealt across the workgroups (rowtile_unit)
@@ -442,15 +407,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int u = wave * gridDim.x + blockIdx.x; u < units; u += 4 * gridDim.x)
       rowtile_unit<EPI, 0>(p, p.rem_row0, p.rem_row0 + p.rem_rows, u / ntl, (u % ntl) * 16, lane);
   }
-  RGW_RT(3);
 }
 
 // The shapes this kernel takes: exact fp32, a hidden layer of a stack on hybrid rows (quad-major a0 and side outputs),
 // 19 column tiles x 19 K chunks, whole meshes.
 bool rowgemmw_ok(const RowGemmArgs &a, int epi) {
-#ifdef A3VT_DBG_RGW_OFF   // variant build (tools/build_variants.sh rgw): the round-5 kernel everywhere, for A/B timing
-  return false;
-#endif
   if (a.mode != GEMM_FP32 || (epi != EPI_FWD_HIDDEN && epi != EPI_DX_MASK)) return false;
   if (a.zq_nvert <= 0 || a.a0q_nvert != a.zq_nvert || a.c2 == nullptr || a.m % a.zq_nvert != 0 || a.m % 16 != 0) return false;
   if (a.k <= 288 || a.k > 304 || a.n_store <= 288 || a.n_store > 304 || a.n_store % 4 != 0 || a.k % 4 != 0) return false;
@@ -485,17 +446,6 @@ static int launch_rowgemmw_epi(const RowGemmArgs &a0, hipStream_t s) {
   A3VT_CHECK_LAUNCH();
   return 0;
 }
-
-#ifdef A3VT_DBG_RGW_STAMPS
-}  // namespace a3vt
-extern "C" int a3vt_dbg_rgw_stamps(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(a3vt::g_rgw_stamps), sizeof(unsigned long long) * 256 * 4 * 48 * 4);
-}
-extern "C" int a3vt_dbg_rgw_rt(unsigned long long *host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(a3vt::g_rgw_rt), sizeof(unsigned long long) * 256 * 4);
-}
-namespace a3vt {
-#endif
 
 int launch_rowgemmw(const RowGemmArgs &a, int epi, hipStream_t s) {
   if (!rowgemmw_ok(a, epi)) {

@@ -38,12 +38,7 @@ __device__ __forceinline__ s16x4 cvt_bf16x4(f32x4 v) {
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u16 = unsigned short;
 __device__ __forceinline__ f32x4 mfma_bf16s(f32x4 a, f32x4 b, f32x4 c) {
-#ifdef A3VT_DBG_RG_NOMFMA
-  c[0] += a[0] * b[0];   // one VALU op instead of the matrix instruction (operands stay live)
-  return c;
-#else
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-#endif
 }
 __device__ __forceinline__ u16 to_bf16(float v) {  // round to nearest even (v_cvt_pk_bf16_f32)
   const bf16x2 r = __builtin_convertvector((f32x2){v, 0.f}, bf16x2);
@@ -64,8 +59,8 @@ __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0
 
 // One 16 x 16 output tile — rows row_base + 16 mt .., columns n0 .. — with its operands pulled straight from global
 // memory into registers: all loads of up to 19 K-chunks in flight at once, no LDS, no barrier, then the MFMA chain (one
-// round trip instead of nineteen).  Same arithmetic order along K as rowgemm_kernel.  Used for the handful of rows the
-// load-balanced split leaves over (launch_rowgemm_epi): by rowtile_kernel, and by the tail of rowgemm_kernel itself.
+// round trip instead of nineteen).  Same arithmetic order along K as rowgemm_kernel.  Used by the tail of rowgemm_kernel for
+// the handful of rows the load-balanced split leaves over (launch_rowgemm_epi).
 template <int EPI, int MODE>
 __device__ __forceinline__ void rowtile_unit(const RowGemmArgs &p, int row_base, int row_end, int mt, int n0, int lane) {
   constexpr int KB = 19;  // K-chunks (of 16) per register block: all of K = 300 in one round trip

@@ -36,7 +36,6 @@
 // vector loads + DPP row_newbcast, 17-25 % slower) or interleave clouds over CUs (persistent grid) are not faster — DESIGN.md
 // §4, §8.  All kernels are deterministic in their outputs (the order of points inside a grid cell depends on LDS atomics, the
 // minima do not).
-#include <stdlib.h>
 
 #include "common.h"
 #include "kernels.h"
@@ -225,12 +224,6 @@ __device__ inline void group_obb(const f32x4 v, bool valid, float out[kObbFloats
   A[0][0] = gsum(d[0] * d[0]), A[0][1] = A[1][0] = gsum(d[0] * d[1]), A[0][2] = A[2][0] = gsum(d[0] * d[2]);
   A[1][1] = gsum(d[1] * d[1]), A[1][2] = A[2][1] = gsum(d[1] * d[2]), A[2][2] = gsum(d[2] * d[2]);
   eig3_jacobi(A, V);
-#ifdef A3VT_DBG_NN_AABB   // A/B build: coordinate axes, i.e. the axis-aligned boxes of rounds 2-4 in this record (what the principal frame buys)
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.f : 0.f;
-#endif
   // axes = columns of V, re-orthonormalised (Gram-Schmidt; the third as the cross product of the first two)
   float a[3][3];
   {
@@ -436,21 +429,6 @@ __global__ __launch_bounds__(1024) void nn_boxes_kernel(NNClouds c, int wgs_per_
   }
 }
 
-#ifdef A3VT_DBG_NN_TRACE   // per-wave timeline only (tools/nn_trace.py): two s_memrealtime reads and one record per wave
-constexpr int kNNTraceWaves = 1 << 16;
-__device__ unsigned long long nn_trace[kNNTraceWaves][4];   // per wave: start, end (s_memrealtime, 100 MHz), pair / block, groups << 32 | tests
-__device__ unsigned nn_trace_n;
-#endif
-#ifdef A3VT_DBG_NN_STATS   // developer counters (tools/build_variants.sh nn): waves, blocks evaluated, point-box tests, slow paths
-__device__ unsigned long long nn_inflight;
-__device__ unsigned long long nn_stats[16];   // [8..13]: shader-clock cycles per phase (whole wave, seed search, tests, evaluations, tail)
-#define NN_STAT(i, v) do { if (lane == 0) atomicAdd(&nn_stats[i], (unsigned long long)(v)); } while (0)
-#define NN_CLOCK() __builtin_readcyclecounter()
-#else
-#define NN_STAT(i, v) do { } while (0)
-#define NN_CLOCK() 0ull
-#endif
-
 // Wave-uniform maximum / minimum of NON-NEGATIVE floats through their bit patterns (they order like unsigned integers):
 // four DPP steps inside each 16-lane row, then the four row results through v_readlane and scalar min / max — a dozen
 // instructions and no LDS round trip, where six __shfl_xor steps cost six dependent ds_bpermute.
@@ -526,18 +504,10 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
   const float qz = qidx < 0 ? q0z : me[2];
   const f32x4 qb0 = qbox[qblk * 2], qb1 = qbox[qblk * 2 + 1];
 
-  const unsigned long long clk0 = NN_CLOCK();
-  unsigned long long clk_test = 0, clk_eval = 0, clk_ld = 0, clk_bd = 0, clk_gr = 0;
-#ifdef A3VT_DBG_NN_STATS
-  if (lane == 0) clk_ld = atomicAdd(&nn_inflight, 1ull);   // waves of this kernel in flight when this one starts
-#endif
-#ifdef A3VT_DBG_NN_TRACE
-  const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
   float best = 3.0e38f;
   int bsub = 0;        // 16-candidate group (block * 4 + quarter) that gave `best`
   bool tie = false;    // another group reproduced `best` exactly
-  int n_grp = 0;       // (developer counter) 16-candidate groups evaluated
+  int n_grp = 0;       // (work counter) 16-candidate groups evaluated
   // Wave-uniform data (a candidate block's oriented boxes, its 64 points) comes through the scalar cache: every batch of
   // loads is issued back to back and waited for once (scalar loads return out of order).  (Delivering it through the vector
   // path instead — each lane loads element lane & 15 of a record / one candidate of a group, DPP row broadcasts folded into
@@ -617,10 +587,8 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
   }
   const int seed = min(__builtin_amdgcn_readfirstlane(sblk), ntb - 1);
   int n_eval = 1, n_test = 0;
-  const unsigned long long clk1 = NN_CLOCK();
   eval(seed);
-  float T = wave_umax(best);
-  const unsigned long long clk2 = NN_CLOCK();   // (wave-uniform) a block whose box-to-box bound exceeds this cannot help any lane
+  float T = wave_umax(best);   // (wave-uniform) a block whose box-to-box bound exceeds this cannot help any lane
 
   for (int it = 0; it < ntb; it += 64) {
     const int b = it + lane;
@@ -628,7 +596,6 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
     unsigned long long mask = __builtin_amdgcn_ballot_w64(lbb <= T && b < ntb && b != seed);
     while (mask) {
       // nearest surviving block first (box to box): the minima tighten early and the later blocks fail their tests
-      const unsigned long long ca = NN_CLOCK();
       const float mine = ((mask >> lane) & 1ull) ? lbb : 3.0e38f;
       const float nearest = wave_umin(mine);
       const unsigned long long pick = __builtin_amdgcn_ballot_w64(mine == nearest) & mask;
@@ -638,14 +605,11 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
       const float lb = point_box(blk);
       ++n_test;
       const bool skip = __builtin_amdgcn_ballot_w64(lb <= best) == 0;   // <=: a candidate that TIES must still be seen
-      const unsigned long long cb = NN_CLOCK();
-      clk_test += cb - ca;
       if (skip) continue;
       eval(blk);
       ++n_eval;
       T = wave_umax(best);
       mask &= __builtin_amdgcn_ballot_w64(lbb <= T);
-      clk_eval += NN_CLOCK() - cb;
     }
   }
 
@@ -667,28 +631,6 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
     atomicAdd(&a.work[3], (unsigned long long)n_test);
     atomicMax(&a.work[4], (unsigned long long)n_grp);
   }
-  const unsigned long long clk3 = NN_CLOCK();
-  NN_STAT(0, 1);
-  NN_STAT(1, n_eval);
-  NN_STAT(2, n_test);
-  NN_STAT(5, n_grp);
-#ifdef A3VT_DBG_NN_STATS
-  if (lane == 0) atomicMax(&nn_stats[6], (unsigned long long)n_grp);
-#endif
-#ifdef A3VT_DBG_NN_STATS
-  {   // blocks that HAD to be evaluated given the final minima (slot 3), blocks some lane needs on average (slot 2 reused below)
-    int need = 0, lane_need = 0;
-    for (int blk = 0; blk < ntb; ++blk) {
-      const float lb = point_box(blk);
-      need += __builtin_amdgcn_ballot_w64(lb <= best) != 0;
-      lane_need += lb <= best;
-    }
-    NN_STAT(3, need);
-    if (lane == 0) atomicAdd(&nn_stats[2], 0ull);
-    lane_need = (int)wave_sum((float)lane_need);
-    if (lane == 0) atomicAdd(&nn_stats[4], (unsigned long long)lane_need);
-  }
-#endif
   if (__builtin_amdgcn_ballot_w64(tie) != 0) {   // duplicates of the minimum in other groups: look everywhere it can be
     for (int blk = 0; blk < ntb; ++blk) {
       const float lb = point_box(blk);
@@ -706,33 +648,6 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
     od[qidx] = best;
     oi[qidx] = bidx;
   }
-#ifdef A3VT_DBG_NN_STATS
-  if (lane == 0) {
-    atomicMax(&nn_stats[13], clk3 - clk0);                     // slowest wave
-  }
-#endif
-#ifdef A3VT_DBG_NN_STATS
-  if (lane == 0) atomicAdd(&nn_inflight, ~0ull);
-#endif
-#ifdef A3VT_DBG_NN_TRACE
-  if (lane == 0) {
-    const unsigned slot = atomicAdd(&nn_trace_n, 1u);
-    if (slot < kNNTraceWaves) {
-      nn_trace[slot][0] = rt0;
-      nn_trace[slot][1] = __builtin_amdgcn_s_memrealtime();
-      nn_trace[slot][2] = (unsigned long long)y << 16 | (unsigned)(qblk & 0xffff);
-      nn_trace[slot][3] = ((unsigned long long)n_grp << 32) | (unsigned)n_test;
-    }
-  }
-#endif
-  NN_STAT(8, clk3 - clk0);
-  NN_STAT(14, clk_ld);
-  NN_STAT(15, clk_bd);
-  NN_STAT(7, clk_gr);
-  NN_STAT(9, clk1 - clk0);
-  NN_STAT(10, clk2 - clk1);
-  NN_STAT(11, clk_test);
-  NN_STAT(12, clk_eval);
 }
 
 // grid = ceil(query blocks / waves per workgroup) x 2 nz, flattened (the query blocks of one cloud pair are consecutive
@@ -795,14 +710,8 @@ int launch_nn_pruned(const float *x, const float *y, int draws, int batch, int p
   once.run([] {
     (void)hipFuncSetAttribute((const void *)nn_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (1 << 15) * 4);
   });
-#ifdef A3VT_DBG_NN_STATS   // diagnostic build only (tools/build_variants.sh nn): stop after the sort / box kernels — the outputs
-  static const int stages = getenv("A3VT_NN_STAGES") ? atoi(getenv("A3VT_NN_STAGES")) : 3;   // are then NOT written
-#else
-  constexpr int stages = 3;
-#endif
   A3VT_LAUNCH(nn_sort_kernel, dim3(c.nx + c.ny), dim3(kSortThreads), shmem, s, c);
   A3VT_CHECK_LAUNCH();
-  if (stages < 2) return 0;
   const int nbmax = (c.npx > c.npy ? c.npx : c.npy) / kPB;
   const long long box_wgs = (long long)cdiv(nbmax, 16) * (c.nx + c.ny);
   const int wg_waves_q = 4;
@@ -813,7 +722,6 @@ int launch_nn_pruned(const float *x, const float *y, int draws, int batch, int p
   }
   A3VT_LAUNCH(nn_boxes_kernel, dim3((unsigned)box_wgs), dim3(1024), 0, s, c, cdiv(nbmax, 16));
   A3VT_CHECK_LAUNCH();
-  if (stages < 3) return 0;
   unsigned long long *work = nullptr;
   if (g_nn_work_on) {
     void *sym = nullptr;
@@ -827,16 +735,6 @@ int launch_nn_pruned(const float *x, const float *y, int draws, int batch, int p
 
 }  // namespace a3vt
 
-#ifdef A3VT_DBG_NN_STATS
-#endif
-#ifdef A3VT_DBG_NN_TRACE
-extern "C" int a3vt_dbg_nn_trace(unsigned long long *out, unsigned *n) {   // per-wave records of the last query launches; clears
-  unsigned zero = 0;
-  if (hipMemcpyFromSymbol(n, HIP_SYMBOL(a3vt::nn_trace_n), sizeof(unsigned)) != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(a3vt::nn_trace), sizeof(unsigned long long) * 4 * a3vt::kNNTraceWaves) != hipSuccess) return -1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(a3vt::nn_trace_n), &zero, sizeof(unsigned)) == hipSuccess ? 0 : -1;
-}
-#endif
 extern "C" int a3vt_dbg_nn_work(int enable, unsigned long long *out8) {
   // Synchronises the device (a test hook).  out8 != NULL: receives the counters accumulated so far; enable != 0: counters
   // cleared and switched on for the searches that follow, enable == 0: switched off.
@@ -847,10 +745,3 @@ extern "C" int a3vt_dbg_nn_work(int enable, unsigned long long *out8) {
   a3vt::g_nn_work_on = enable != 0;
   return 0;
 }
-#ifdef A3VT_DBG_NN_STATS
-extern "C" int a3vt_dbg_nn_stats(unsigned long long *out5) {   // reads and clears the counters
-  unsigned long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyFromSymbol(out5, HIP_SYMBOL(a3vt::nn_stats), sizeof(z)) != hipSuccess) return -1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(a3vt::nn_stats), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-#endif

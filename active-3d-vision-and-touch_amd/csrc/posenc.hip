@@ -344,9 +344,6 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
   int tile = blockIdx.x * kPEBwdWaves + wave;
   Inputs in;
   if (tile < ntile) in = fetch(tile);
-#ifdef A3VT_DBG_PE_NOLOOP   // timing-only: set-up and the final reduction alone
-  tile = ntile;
-#endif
   for (; tile < ntile; tile += nwave) {
     // ---- park the inputs: G rows, the embedding E (lane = vertex l16, a quarter of the 30 (frequency, axis) pairs), token
 #pragma unroll
@@ -364,13 +361,8 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
           // pe_freq(i) for a runtime i: the same double product, rounded once
           const float f = i == 0 ? (float)3.141592653589793 : (float)(3.141592653589793 * 2.0 * (double)i);
           const float pc = c == 0 ? in.p[0] : c == 1 ? in.p[1] : in.p[2];
-#ifdef A3VT_DBG_PE_NOSINCOS   // timing-only
-          myE[6 * i + c] = f * pc;
-          myE[6 * i + 3 + c] = f + pc;
-#else
           myE[6 * i + c] = sinf(f * pc);
           myE[6 * i + 3 + c] = cosf(f * pc);
-#endif
         }
       }
       if (kq < 3) myE[60 + kq] = kq == 0 ? in.p[0] : kq == 1 ? in.p[1] : in.p[2];
@@ -417,7 +409,6 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
     // The outer products run over the tile's vertices as (kq, st) -> vertex 4 kq + st: operand rows 4 kq + st of G / H2 /
     // H1 / E from LDS, dh2 / dh1 straight from the registers above.
     // ---- dW3 | db3 | dE += G^T . [H2 | 1 | one-hot]
-#ifndef A3VT_DBG_PE_NOOUTER
     {
       float hb[2][4];
 #pragma unroll
@@ -435,7 +426,6 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
           for (int st = 0; st < 4; ++st) aW3[a][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[st], hb[n][st], aW3[a][n], 0, 0, 0);
       }
     }
-#endif
     // ---- dh1 = (D2 . W2) * (h1 > 0)
     f32x4 d1;
     {
@@ -447,7 +437,6 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
       }
     }
     // ---- dW2 | db2 += D2^T . [H1 | 1]
-#ifndef A3VT_DBG_PE_NOOUTER
     {
       float hb[4];
 #pragma unroll
@@ -457,7 +446,6 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
 #pragma unroll
         for (int st = 0; st < 4; ++st) aW2[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(d2[a][st], hb[st], aW2[a], 0, 0, 0);
     }
-#endif
     pe_wave_sync();
     // ---- de = D1 . W1 (into G's rows: every product on G has been issued, LDS runs in order)
 #pragma unroll
@@ -467,7 +455,6 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
       for (int r = 0; r < 4; ++r) sDE[(kq * 4 + r) * B::LG + n * 16 + l16] = acc[r];
     }
     // ---- dW1 | db1 += D1^T . [E | 1]
-#ifndef A3VT_DBG_PE_NOOUTER
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       float eb[4];
@@ -476,7 +463,6 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
 #pragma unroll
       for (int st = 0; st < 4; ++st) aW1[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(d1[st], eb[st], aW1[n], 0, 0, 0);
     }
-#endif
     pe_wave_sync();
     // ---- gradient w.r.t. the position (lane = vertex l16, axis kq).  d sin(f p)/dp = f cos(f p) = f e[6i+3+c],
     // d cos(f p)/dp = -f e[6i+c]

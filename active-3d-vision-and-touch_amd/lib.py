@@ -9,7 +9,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT_LIB: developer override (variant builds)
+LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT_LIB: another build of the library (tools/asan_host.sh)
 SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
            "pooling.hip"]
 # Per-file extra flags (none at present; sample.hip / gcn_csr.hip rely on IEEE NaN semantics — the reference's NaN
@@ -108,17 +108,12 @@ SIGNATURES = {
 _LIB = None
 
 
-def build(force=False, verbose=False, defines=(), out=None):
-    """hipcc --offload-arch=gfx950 -shared → liba3vt.so next to this file (cross-compiles without a GPU).
-
-    ``defines`` / ``out``: developer variants (tools/build_variants.sh) — the same per-file flags as the shipped
-    library plus ``-D`` switches, written to another path (always rebuilt, objects in their own directory)."""
-    if out is not None:
-        return _build(True, verbose, list(defines), out, os.path.join(_HERE, "build", "variant_" + os.path.basename(out)))
-    return _build(force, verbose, [], LIB_PATH, os.path.join(_HERE, "build"))
+def build(force=False, verbose=False):
+    """hipcc --offload-arch=gfx950 -shared → liba3vt.so next to this file (cross-compiles without a GPU)."""
+    return _build(force, verbose, LIB_PATH, os.path.join(_HERE, "build"))
 
 
-def _build(force, verbose, defines, lib_path, objdir):
+def _build(force, verbose, lib_path, objdir):
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     deps = srcs + [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "gemm_tile.h")] + \
         [os.path.join(_HERE, "..", "include", "a3vt.h")]
@@ -129,7 +124,7 @@ def _build(force, verbose, defines, lib_path, objdir):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         hipcc = "hipcc"
-    common = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", *[f"-D{d}" for d in defines]]
+    common = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
     os.makedirs(objdir, exist_ok=True)
     procs = []
     for name in SOURCES:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Developer aid (GPU box): the fused vertex-feature encoder (csrc/posenc.hip, I = 50) at the benchmark's 64 x 2562 rows:
-microseconds per forward and backward call (HIP events around 50 calls each).  A3VT_LIB selects a variant build."""
+microseconds per forward and backward call (HIP events around 50 calls each)."""
 import os
 import sys
 

@@ -28,4 +28,4 @@ for _ in range(reps):
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / reps
-print(f"{os.environ.get('A3VT_LIB', 'default')} zero={zero} reps={reps}: rowgemm {ms * 1e3:.1f} us  {2.0 * M * K * N / ms / 1e9:.1f} TFLOP/s")
+print(f"zero={zero} reps={reps}: rowgemm {ms * 1e3:.1f} us  {2.0 * M * K * N / ms / 1e9:.1f} TFLOP/s")
