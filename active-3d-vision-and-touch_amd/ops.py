@@ -626,6 +626,7 @@ class ConvNHWCFn(torch.autograd.Function):
         if ctx.own:
             y = conv5_nhwc(xb, _conv5_image(weight, 0), _req(bias.detach(), "conv bias") if add_bias else None,
                            int(weight.shape[0]), int(stride[0]), 1)
+            STATS["conv5_fwd"] = STATS.get("conv5_fwd", 0) + 1
             ctx.weight = weight
         else:
             y = torch.ops.aten.convolution(xb, wb, _bf16_copy(bias, False) if add_bias else None, stride, padding, [1, 1], False, [0, 0], 1)
@@ -646,6 +647,7 @@ class ConvNHWCFn(torch.autograd.Function):
             if need_gx and list(stride) == [1, 1] and ctx.weight.shape[1] != 3:
                 # the input gradient is the same convolution on gy with the weights transposed and flipped, padding 3
                 gx = conv5_nhwc(gy, _conv5_image(ctx.weight, 1), None, int(ctx.weight.shape[1]), 1, 3)
+                STATS["conv5_input_grad"] = STATS.get("conv5_input_grad", 0) + 1
             elif (need_gx and list(stride) == [2, 2] and tuple(ctx.weight.shape[:2]) == (16, 3)
                   and xb.shape[2] == 2 * gy.shape[2] + 2 and xb.shape[3] == 2 * gy.shape[3] + 2):
                 # layer 1 (3 -> 16, stride 2): its input gradient as a stride-1 convolution of gy read as if upsampled with zeros
@@ -653,6 +655,7 @@ class ConvNHWCFn(torch.autograd.Function):
                 gx = torch.empty_like(xb, memory_format=torch.channels_last)
                 _lib.check(L.a3vt_conv5_input_grad_3x16s2(_lib.ptr(gy), gy.shape[0], gy.shape[2], gy.shape[3],
                                                           _lib.ptr(_conv5_image(ctx.weight, 1)), _lib.ptr(gx), _stream()), "conv5_input_grad_3x16s2")
+                STATS["conv5_input_grad_3x16s2"] = STATS.get("conv5_input_grad_3x16s2", 0) + 1
             elif need_gx:      # (16 -> 32 at stride 2, 3 -> 3: MIOpen)
                 gx = torch.ops.aten.convolution_backward(gy, xb, wb, None, stride, padding, [1, 1], False, [0, 0], 1, [True, False, False])[0]
             else:

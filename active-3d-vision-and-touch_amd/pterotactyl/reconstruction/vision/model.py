@@ -122,9 +122,11 @@ class Image_Encoder(nn.Module):
 
     @staticmethod
     def _bn_fusable(m, x):
-        """A training-mode BatchNorm2d the library's BatchNorm + ReLU operator takes (csrc/bnrelu.hip)."""
+        """A training-mode BatchNorm2d the library's BatchNorm + ReLU operator takes (csrc/bnrelu.hip): what ``BNReLUFn``
+        would refuse (more than ``_BNRELU_MAX_C`` channels, statistics not in fp32) stays on the MIOpen branch."""
         return (Image_Encoder.fused_bn_relu and isinstance(m, nn.BatchNorm2d) and m.training and m.affine and m.track_running_stats
-                and m.momentum is not None and x.dtype == torch.bfloat16 and m.running_mean.dtype == torch.float32
+                and m.momentum is not None and x.dtype == torch.bfloat16 and m.num_features <= _ops._BNRELU_MAX_C
+                and m.running_mean.dtype == torch.float32 and m.running_var.dtype == torch.float32
                 and m.num_batches_tracked.dtype == torch.int64)
 
     @staticmethod

@@ -563,3 +563,20 @@ def test_library_adam_on_cpu_tensors_is_torch_adam():
     sa, sb = oa.state_dict(), ob.state_dict()
     assert sa["param_groups"][0].keys() == sb["param_groups"][0].keys() and sa["state"].keys() == sb["state"].keys()
     assert all(sa["state"][k].keys() == sb["state"][k].keys() for k in sa["state"])
+
+
+def test_bn_fusable_refuses_what_bnrelu_refuses():
+    """Image_Encoder._bn_fusable: more than ops._BNRELU_MAX_C channels or non-fp32 statistics stay on the MIOpen branch
+    (BNReLUFn would raise on them, and a convolution in front would have left its bias to it)."""
+    import torch
+    from torch import nn
+    from a3vt_amd import ops
+    from a3vt_amd.pterotactyl.reconstruction.vision import model
+    x = torch.empty(0, dtype=torch.bfloat16)
+    fus = model.Image_Encoder._bn_fusable
+    assert fus(nn.BatchNorm2d(16).train(), x) and fus(nn.BatchNorm2d(ops._BNRELU_MAX_C).train(), x)
+    assert not fus(nn.BatchNorm2d(ops._BNRELU_MAX_C + 16).train(), x)
+    bn = nn.BatchNorm2d(16).train()
+    bn.running_var = bn.running_var.double()
+    assert not fus(bn, x)
+    assert not fus(nn.BatchNorm2d(16).train(), x.float())
