@@ -34,6 +34,7 @@ def install_as_pterotactyl():
         # consumers of the same kernels
         "pterotactyl.utility.data_loaders": ".pterotactyl.utility.data_loaders",
         "pterotactyl.reconstruction.autoencoder.model": ".pterotactyl.reconstruction.autoencoder.model",
+        "pterotactyl.reconstruction.autoencoder.train": ".pterotactyl.reconstruction.autoencoder.train",
         "pterotactyl.policies.DDQN.model": ".pterotactyl.policies.DDQN.model",
         "pterotactyl.policies.scoring": ".pterotactyl.policies.scoring",
     }

@@ -1279,6 +1279,42 @@ int a3vt_gcn_layer_bwd(const float *x, int ld_x, int in_features, const float *w
   return launch_rowgemm(r, EPI_PLAIN, s);
 }
 
+// ---- FoldingNet fold (fold.hip) ----------------------------------------------------------------------------------------------
+static bool fold_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static bool fold_al4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+size_t a3vt_fold_workspace_bytes(int batch, int points, int backward) { return fold_workspace_bytes(batch, points, backward); }
+
+int a3vt_fold_fwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
+                  const float *b3, int batch, int points, int width, float *y, void *workspace, size_t workspace_bytes, void *stream) {
+  A3VT_CHECK_ARG(width == 512);
+  A3VT_CHECK_ARG(k == 2 || k == 3);
+  A3VT_CHECK_ARG(batch > 0 && points > 0 && (long long)batch * points <= 16000000);
+  A3VT_CHECK_ARG(bias_s && g && w1g && w2 && b2 && w3 && b3 && y && workspace);
+  A3VT_CHECK_ARG(fold_al16(bias_s) && fold_al16(w2) && fold_al16(b2) && fold_al16(w3) && fold_al16(workspace));
+  A3VT_CHECK_ARG(fold_al4(g) && fold_al4(w1g) && fold_al4(b3) && fold_al4(y));
+  A3VT_CHECK_ARG(workspace_bytes >= fold_workspace_bytes(batch, points, 0));
+  return launch_fold_fwd(bias_s, g, k, w1g, w2, b2, w3, b3, batch, points, y, static_cast<float *>(workspace),
+                         static_cast<hipStream_t>(stream));
+}
+
+int a3vt_fold_bwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
+                  const float *dy, int batch, int points, int width, float *d_bias_s, float *dg, float *dw1g, float *dw2, float *db2,
+                  float *dw3, float *db3, void *workspace, size_t workspace_bytes, void *stream) {
+  A3VT_CHECK_ARG(width == 512);
+  A3VT_CHECK_ARG(k == 2 || k == 3);
+  A3VT_CHECK_ARG(batch > 0 && points > 0 && (long long)batch * points <= 16000000);
+  A3VT_CHECK_ARG(bias_s && g && w1g && w2 && b2 && w3 && dy && workspace);
+  A3VT_CHECK_ARG(d_bias_s && dw1g && dw2 && db2 && dw3 && db3);
+  A3VT_CHECK_ARG(dg == nullptr || k == 3);   // the lattice of fold 1 has no gradient
+  A3VT_CHECK_ARG(fold_al16(bias_s) && fold_al16(w2) && fold_al16(b2) && fold_al16(w3) && fold_al16(workspace) && fold_al16(dw2));
+  A3VT_CHECK_ARG(fold_al4(g) && fold_al4(w1g) && fold_al4(dy) && fold_al4(d_bias_s) && fold_al4(dg) && fold_al4(dw1g) && fold_al4(db2) &&
+                 fold_al4(dw3) && fold_al4(db3));
+  A3VT_CHECK_ARG(workspace_bytes >= fold_workspace_bytes(batch, points, 1));
+  return launch_fold_bwd(bias_s, g, k, w1g, w2, b2, w3, dy, batch, points, d_bias_s, dg, dw1g, dw2, db2, dw3, db3,
+                         static_cast<float *>(workspace), static_cast<hipStream_t>(stream));
+}
+
 int a3vt_wt_rows(int n_out) { return rowgemm_bt_rows(n_out); }
 int a3vt_wt_ld(int k) { return pad16(k); }
 

@@ -375,4 +375,12 @@ int launch_nn_pruned(const float *x, const float *y, int draws, int batch, int p
 int launch_chamfer_bwd(const float *x, const float *y, int draws, int batch, int p, int q, const int32_t *ixy,
                        const int32_t *iyx, const float *gcd, float *gx, float *gy, hipStream_t s);
 
+// fold.hip: one FoldingNet fold (512 wide, k = 2 or 3 point coordinates) without an M x 512 tensor in memory
+size_t fold_workspace_bytes(int batch, int points, int bwd);
+int launch_fold_fwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
+                    const float *b3, int batch, int points, float *y, float *ws, hipStream_t s);
+int launch_fold_bwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
+                    const float *dy, int batch, int points, float *dbias_s, float *dg, float *dw1g, float *dw2, float *db2,
+                    float *dw3, float *db3, float *ws, hipStream_t s);
+
 }  // namespace a3vt

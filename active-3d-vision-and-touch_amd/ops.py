@@ -90,7 +90,8 @@ def _ptr_array(tensors):
 GEMM_MODES = {"fp32": 0, "bf16": 1, "bf16s": 2, "fp32x3": 3}
 
 
-PATH_NAMES = ("stack_quad", "stack_rows", "rowgemm_adirect", "rowgemm3", "dw3", "dw_hybrid", "rowgemm16", "stack16_quad", "rowgemm_w", "dw_w", "stack_split", "csr16_tiles")
+PATH_NAMES = ("stack_quad", "stack_rows", "rowgemm_adirect", "rowgemm3", "dw3", "dw_hybrid", "rowgemm16", "stack16_quad", "rowgemm_w", "dw_w", "stack_split", "csr16_tiles",
+              "fold_fwd", "fold_bwd")
 
 
 def path_counts(reset=False):
@@ -900,6 +901,59 @@ def chamfer_nn(x, y, single_pass=True, algo=None):
                                          _lib.ptr(dyx), _lib.ptr(iyx), _lib.ptr(cd), _lib.ptr(ws), nbytes, NN_ALGOS[algo],
                                          _stream()), "chamfer_fwd")
     return dxy, ixy, dyx, iyx, cd
+
+
+class FoldFn(torch.autograd.Function):
+    """One FoldingNet fold, conv3(relu(conv2(relu(bias_s + W1g g)))), on ``a3vt_fold_fwd/bwd`` (csrc/fold.hip): no
+    (B * P) x 512 tensor exists in memory, forward or backward.  ``bias_s`` (B, 512) is conv1's code part, computed by torch
+    outside (autograd carries its gradient on to the code and to that slice of the weight); ``g`` (B, P, k), k = 2 or 3;
+    ``w1g`` (512, k), ``w2`` (512, 512), ``b2`` (512,), ``w3`` (3, 512), ``b3`` (3,) -> y (B, P, 3)."""
+
+    @staticmethod
+    def forward(ctx, bias_s, g, w1g, w2, b2, w3, b3):
+        L = _lib.load()
+        bias_s, g, w1g, w2, b2, w3, b3 = (_req(t, n) for t, n in ((bias_s, "bias_s"), (g, "g"), (w1g, "w1g"), (w2, "w2"), (b2, "b2"),
+                                                                  (w3, "w3"), (b3, "b3")))
+        B, P, k = g.shape
+        width = w2.shape[0]
+        if bias_s.shape != (B, width) or w1g.shape != (width, k) or w2.shape != (width, width) or b2.shape != (width,) or \
+                w3.shape != (3, width) or b3.shape != (3,):
+            raise RuntimeError("a3vt: fold operand shapes disagree")
+        y = torch.empty((B, P, 3), dtype=torch.float32, device=g.device)
+        need = L.a3vt_fold_workspace_bytes(B, P, 0)
+        ws = workspace("fold", need, g.device)
+        _lib.check(L.a3vt_fold_fwd(_lib.ptr(bias_s), _lib.ptr(g), k, _lib.ptr(w1g), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(w3), _lib.ptr(b3),
+                                   B, P, width, _lib.ptr(y), _lib.ptr(ws), need, _stream()), "fold_fwd")
+        ctx.save_for_backward(bias_s, g, w1g, w2, b2, w3)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _lib.load()
+        bias_s, g, w1g, w2, b2, w3 = ctx.saved_tensors
+        B, P, k = g.shape
+        width = w2.shape[0]
+        dy = _req(dy, "grad_y")
+        dev = g.device
+        dbias = torch.empty_like(bias_s)
+        dg = torch.empty_like(g) if k == 3 and ctx.needs_input_grad[1] else None
+        dw1g, dw2, db2, dw3 = torch.empty_like(w1g), torch.empty_like(w2), torch.empty_like(b2), torch.empty_like(w3)
+        db3 = torch.empty((3,), dtype=torch.float32, device=dev)
+        need = L.a3vt_fold_workspace_bytes(B, P, 1)
+        ws = workspace("fold", need, dev)
+        _lib.check(L.a3vt_fold_bwd(_lib.ptr(bias_s), _lib.ptr(g), k, _lib.ptr(w1g), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(w3), _lib.ptr(dy),
+                                   B, P, width, _lib.ptr(dbias), _lib.ptr(dg), _lib.ptr(dw1g), _lib.ptr(dw2), _lib.ptr(db2), _lib.ptr(dw3),
+                                   _lib.ptr(db3), _lib.ptr(ws), need, _stream()), "fold_bwd")
+        return dbias, dg, dw1g, dw2, db2, dw3, db3
+
+
+def fold(code, g, conv1, conv2, conv3):
+    """A fold of ``FoldingNetDec`` on the fused kernels: ``code`` (B, 512), ``g`` (B, P, k), the fold's three ``Conv1d`` modules
+    (their parameters stay whole: conv1.weight is sliced here) -> (B, P, 3)."""
+    width = conv2.weight.shape[0]
+    w1 = conv1.weight.squeeze(-1)
+    bias_s = torch.addmm(conv1.bias, code, w1[:, :width].t())
+    return FoldFn.apply(bias_s, g, w1[:, width:], conv2.weight.squeeze(-1), conv2.bias, conv3.weight.squeeze(-1), conv3.bias)
 
 
 def rowgemm(a, w, bf16=False):

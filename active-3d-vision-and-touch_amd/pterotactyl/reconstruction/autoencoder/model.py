@@ -8,8 +8,10 @@ the FoldingNet folds (:141-208).  What runs where:
 * the encoder's graph layers: one ``a3vt_gcn_layer_fwd/bwd`` call per layer through ``vision.model.GCN_layer`` — every
   layer is hidden -> hidden here, the last one without the cut and without ReLU (:57-64, 87-89), shapes the stack
   entry points do not cover;
-* vertex max-pool, the latent MLP and the FoldingNet decoder (1x1 convolutions on an 80x80 grid): torch ops on the
-  GPU — they are not on the north_star path.
+* vertex max-pool and the latent MLP: torch ops on the GPU;
+* the FoldingNet decoder (1x1 convolutions on an 80x80 grid): torch ops by default; with ``args.fused_decoder`` (this
+  package's knob, off unless set) each fold is one ``a3vt_fold_fwd/bwd`` call (``ops.fold``, csrc/fold.hip), which keeps no
+  (B * 6400) x 512 tensor.  Parameters, state-dict keys and the (B, 3, 6400) result are the same either way.
 """
 import numpy as np
 import torch
@@ -75,7 +77,7 @@ def _identity(x):
 class Decoder(nn.Module):
     def __init__(self, args, rank=0):
         super().__init__()
-        self.model = FoldingNetDec(rank=rank)
+        self.model = FoldingNetDec(rank=rank, fused=bool(getattr(args, "fused_decoder", False)))
         self.initial = nn.Linear(args.encoding_size, 512)
 
     def forward(self, features):
@@ -114,14 +116,22 @@ def GridSamplingLayer(batch_size, meshgrid):
 class FoldingNetDec(nn.Module):
     """Two folds of an 80 x 80 lattice in [-0.5, 0.5]^2 conditioned on the 512-d code (:188-208) -> (B, 3, 6400)."""
 
-    def __init__(self, rank=0):
+    def __init__(self, rank=0, fused=False):
         super().__init__()
         self.rank = rank
+        self.fused = fused
         self.fold1 = FoldingNetDecFold1()
         self.fold2 = FoldingNetDecFold2()
 
+    def _fused_ok(self, x):
+        return self.fused and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(1) == 512
+
     def forward(self, x):
         b = x.size(0)
+        if self._fused_ok(x):
+            grid = torch.from_numpy(GridSamplingLayer(b, [[-0.5, 0.5, 80], [-0.5, 0.5, 80]])).to(x.device)
+            folded = _ops.fold(x, grid, self.fold1.conv1, self.fold1.conv2, self.fold1.conv3)
+            return _ops.fold(x, folded, self.fold2.conv1, self.fold2.conv2, self.fold2.conv3).transpose(2, 1)
         code = x.unsqueeze(2).expand(b, 512, 80 * 80)
         grid = torch.from_numpy(GridSamplingLayer(b, [[-0.5, 0.5, 80], [-0.5, 0.5, 80]])).to(x.device)
         folded = self.fold1(torch.cat((code, grid.transpose(2, 1)), dim=1))

@@ -433,6 +433,7 @@ int a3vt_dbg_csr_algo(int algo);
  *   [8] rowgemmw_kernel launches  [9] dww_kernel launches (exact fp32 hidden-layer products, round 6)
  *   [10] stack forward calls that aggregated through the P + bipartite split (struct a3vt_adj_split)
  *   [11] csr16t forward launches (bf16 storage: aggregation from LDS tiles)
+ *   [12] a3vt_fold_fwd calls  [13] a3vt_fold_bwd calls
  * Returns the number of counters the library keeps (entries beyond it are written as 0); reset != 0 clears them. */
 int a3vt_dbg_path_counts(long long *counts, int n, int reset);
 
@@ -451,6 +452,26 @@ int a3vt_dbg_nn_work(int enable, unsigned long long *out8);
  * (all normal floats down to 2^-110; FLT_MAX included: hi is a truncation and cannot overflow); smaller magnitudes
  * differ by < 2^-133.  Device pointers, n elements each. */
 int a3vt_split3_bf16(const float *x, size_t n, uint16_t *hi, uint16_t *mid, uint16_t *lo, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * One FoldingNet fold of the auto-encoder's decoder (reconstruction/autoencoder/model.py: FoldingNetDecFold1 / Fold2,
+ * conv3(relu(conv2(relu(conv1(cat(code, g))))))) over batch * points rows, without any (batch * points) x 512 tensor in
+ * memory.  conv1 of the concatenated input is split by the caller: bias_s (batch, 512) = W1[:, :512] code_b + b1, and
+ * w1g (512, k) = W1[:, 512:], k = 2 (fold 1: the lattice) or 3 (fold 2: fold 1's output).  g (batch, points, k),
+ * w2 (512, 512), b2 (512), w3 (3, 512), b3 (3), y / dy (batch, points, 3): all fp32, row-major, device pointers.
+ * Exact fp32 (v_mfma_f32_32x32x2_f32); every sum over rows has a fixed order, so two calls give the same bits, and a
+ * sample's forward does not depend on the batch around it.  width is the layer width and must be 512 (the compiled
+ * shape).  bias_s, w2, b2, w3, dw2 and the workspace are 16-byte aligned.  The workspace (a3vt_fold_workspace_bytes;
+ * backward != 0 for a3vt_fold_bwd) holds the operand images of w2, the sign bits of the second activation (64 bytes per
+ * row) and the partial sums; nothing in it survives a call.
+ * a3vt_fold_bwd: d_bias_s (batch, 512), dg (batch, points, 3; NULL when k = 2 or not wanted), dw1g (512, k),
+ * dw2, db2, dw3, db3 are overwritten.  Returns 0, or non-zero with a message in a3vt_last_error. */
+size_t a3vt_fold_workspace_bytes(int batch, int points, int backward);
+int a3vt_fold_fwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
+                  const float *b3, int batch, int points, int width, float *y, void *workspace, size_t workspace_bytes, void *stream);
+int a3vt_fold_bwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
+                  const float *dy, int batch, int points, int width, float *d_bias_s, float *dg, float *dw1g, float *dw2, float *db2,
+                  float *dw3, float *db3, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Deferred finite check (replaces the blocking NaN trap of model.py:326-329): sets *flag (device
