@@ -37,9 +37,13 @@ def install_as_pterotactyl():
         "pterotactyl.reconstruction.autoencoder.train": ".pterotactyl.reconstruction.autoencoder.train",
         "pterotactyl.policies.DDQN.model": ".pterotactyl.policies.DDQN.model",
         "pterotactyl.policies.scoring": ".pterotactyl.policies.scoring",
+        "pterotactyl.policies.baselines.baselines": ".pterotactyl.policies.baselines.baselines",
+        "pterotactyl.policies.replay": ".pterotactyl.policies.replay",
+        "pterotactyl.policies.DDQN.ddqn": ".pterotactyl.policies.DDQN.ddqn",
     }
     for parent in ("pterotactyl", "pterotactyl.reconstruction", "pterotactyl.reconstruction.vision",
                    "pterotactyl.reconstruction.autoencoder", "pterotactyl.policies", "pterotactyl.policies.DDQN",
+                   "pterotactyl.policies.baselines",
                    "pterotactyl.utility"):
         if parent not in sys.modules:
             try:

@@ -33,6 +33,7 @@ struct AdamArgs {
   const long long *chunk_off;  // [chunks]: first element of the chunk in its tensor (a multiple of 4096)
   int n_chunks;
   float one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps, weight_decay;
+  float grad_clamp;            // adam_kernel<true>: every gradient element is clamped to [-grad_clamp, grad_clamp] and written back
 };
 
 __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, const AdamArgs &a) {
@@ -43,12 +44,17 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
   p = p - a.step_size * (m / denom);
 }
 
+// CLAMP: the reference's `param.grad.data.clamp_(-1, 1)` before the step (policies/DDQN/ddqn.py:120-122) inside the same launch: the
+// clamped gradient is what the step uses and what is left in the gradient tensor (4 more bytes written per parameter).
+__device__ __forceinline__ float clamp_grad(float g, float c) { return fminf(fmaxf(g, -c), c); }
+
+template <bool CLAMP>
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
     const int t = a.chunk_tensor[c];
     const long long off = a.chunk_off[c], n = a.numel[t];
     float *__restrict__ p = a.param[t] + off;
-    const float *__restrict__ g = a.grad[t] + off;
+    float *__restrict__ g = const_cast<float *>(a.grad[t]) + off;
     float *__restrict__ m = a.exp_avg[t] + off;
     float *__restrict__ v = a.exp_avg_sq[t] + off;
     const long long left = n - off;      // > 0
@@ -59,7 +65,12 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
         const int i = (k * 256 + threadIdx.x) * 4;
         f32x4 pv = *reinterpret_cast<const f32x4 *>(p + i), mv = *reinterpret_cast<const f32x4 *>(m + i);
         f32x4 vv = *reinterpret_cast<const f32x4 *>(v + i);
-        const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(g + i));
+        f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(g + i));
+        if (CLAMP) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) gv[e] = clamp_grad(gv[e], a.grad_clamp);
+          *reinterpret_cast<f32x4 *>(g + i) = gv;
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float pe = pv[e], me = mv[e], ve = vv[e];
@@ -75,8 +86,9 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
     } else {      // a tensor's last chunk, or a tensor that does not start on a 16-byte boundary
       const int cnt = left < kAdamChunk ? (int)left : kAdamChunk;
       for (int i = threadIdx.x; i < cnt; i += 256) {
-        float pv = p[i], mv = m[i], vv = v[i];
-        adam_one(pv, g[i], mv, vv, a);
+        float pv = p[i], mv = m[i], vv = v[i], gv = g[i];
+        if (CLAMP) g[i] = gv = clamp_grad(gv, a.grad_clamp);
+        adam_one(pv, gv, mv, vv, a);
         p[i] = pv;
         m[i] = mv;
         v[i] = vv;
@@ -91,7 +103,7 @@ int adam_chunk_elems() { return kAdamChunk; }
 
 int launch_adam(void *const *param, const void *const *grad, void *const *exp_avg, void *const *exp_avg_sq,
                 const long long *numel, const int *chunk_tensor, const long long *chunk_off, int n_chunks, double lr, double beta1,
-                double beta2, double eps, double weight_decay, long long step, hipStream_t s) {
+                double beta2, double eps, double weight_decay, long long step, hipStream_t s, double grad_clamp) {
   if (n_chunks == 0) return 0;
   AdamArgs a{};
   a.param = reinterpret_cast<float *const *>(param);
@@ -112,7 +124,11 @@ int launch_adam(void *const *param, const void *const *grad, void *const *exp_av
   a.eps = (float)eps;
   a.weight_decay = (float)weight_decay;
   const int grid = n_chunks < kAdamMaxWgs ? n_chunks : kAdamMaxWgs;
-  A3VT_LAUNCH(adam_kernel, dim3(grid), dim3(256), 0, s, a);
+  a.grad_clamp = (float)grad_clamp;
+  if (grad_clamp > 0.0)
+    A3VT_LAUNCH(adam_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+  else
+    A3VT_LAUNCH(adam_kernel<false>, dim3(grid), dim3(256), 0, s, a);
   A3VT_CHECK_LAUNCH();
   return 0;
 }

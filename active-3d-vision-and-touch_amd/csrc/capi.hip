@@ -1279,6 +1279,133 @@ int a3vt_gcn_layer_bwd(const float *x, int ld_x, int in_features, const float *w
   return launch_rowgemm(r, EPI_PLAIN, s);
 }
 
+// ---- the DDQN learner: TD target + loss (ddqn.hip), the graph model's fused input layer (qnet_input.hip) ------------------------
+int a3vt_ddqn_td(const float *q_cur, const float *q_next_online, const float *q_next_target, const float *mask, const float *actions,
+                 const float *rewards, const float *denom, int batch, int num_actions, int budget, float gamma, float *loss,
+                 float *diff, int32_t *best_next, float *target, void *stream) {
+  A3VT_CHECK_ARG(batch >= 1 && batch <= kTdMaxBatch && num_actions >= 1 && num_actions <= kTdMaxActions);
+  A3VT_CHECK_ARG(q_cur && q_next_online && q_next_target && mask && actions && rewards);
+  A3VT_CHECK_ARG(loss && diff && best_next && target);
+  return launch_ddqn_td(q_cur, q_next_online, q_next_target, mask, actions, rewards, denom, batch, num_actions, budget, gamma, loss,
+                        diff, best_next, target, static_cast<hipStream_t>(stream));
+}
+
+int a3vt_ddqn_td_bwd(const float *diff, const float *actions, const float *grad_loss, int batch, int num_actions, float *dq_cur,
+                     void *stream) {
+  A3VT_CHECK_ARG(batch >= 1 && batch <= kTdMaxBatch && num_actions >= 1 && num_actions <= kTdMaxActions);
+  A3VT_CHECK_ARG(diff && actions && grad_loss && dq_cur);
+  return launch_ddqn_td_bwd(diff, actions, grad_loss, batch, num_actions, dq_cur, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+struct QnetLayout {
+  size_t za, heavy, ga, dz, db_slab, slab, total;
+};
+QnetLayout qnet_layout(int batch, int n_vert, int hidden, int cut_len, int backward) {
+  QnetLayout L{};
+  const size_t m = (size_t)batch * n_vert;
+  const int cw = pad4(cut_len) > 4 ? pad4(cut_len) : 4, npad = pad4(hidden);
+  size_t off = 0;
+  auto take = [&](size_t nfloats) {
+    const size_t o = off;
+    off = align_up(off + nfloats, 64);
+    return o;
+  };
+  L.za = take(m * cw);
+  L.heavy = take(csr_heavy_scratch_ints(n_vert));
+  if (backward) {
+    L.ga = take(m * cw);
+    L.dz = take(m * npad);
+    L.db_slab = take((size_t)csr_bwd_num_slabs(batch, n_vert) * cw);
+    L.slab = take((size_t)qnet_bwd_wgs(batch, n_vert) * qnet_slab_floats(hidden));
+  }
+  L.total = off;
+  return L;
+}
+int check_qnet_dims(int hidden, int cut_len, int n_vert, int batch) {
+  if (hidden < 1 || hidden > 304 || cut_len < 0 || cut_len > hidden) {
+    set_error("qnet_input: hidden=%d (1..304) cut_len=%d unsupported", hidden, cut_len);
+    return -1;
+  }
+  if (n_vert < 1 || batch < 1 || (long long)batch * ((n_vert + 63) / 64) > 0x7fffffffll) {
+    set_error("qnet_input: batch=%d n_vert=%d unsupported", batch, n_vert);
+    return -1;
+  }
+  return 0;
+}
+bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+}  // namespace
+
+size_t a3vt_qnet_input_scratch_bytes(int batch, int n_vert, int hidden, int cut_len, int backward) {
+  if (batch < 1 || n_vert < 1 || hidden < 1 || hidden > 304 || cut_len < 0 || cut_len > hidden) return 0;
+  return qnet_layout(batch, n_vert, hidden, cut_len, backward).total * sizeof(float);
+}
+
+int a3vt_qnet_input_fwd(const float *mesh, const float *w1, const float *b1, const float *w2, const float *b2, const float *comp_s,
+                        const float *comp_t, const float *comp_c, const float *bias, int hidden, int cut_len, const int32_t *rowptr,
+                        const int32_t *col, const float *val, int max_degree, int n_vert, int batch, float *y, int ld_y,
+                        float *scratch, void *stream) {
+  if (int rc = check_qnet_dims(hidden, cut_len, n_vert, batch)) return rc;
+  A3VT_CHECK_ARG(mesh && w1 && b1 && w2 && b2 && comp_s && comp_t && comp_c && bias && rowptr && col && val && y && scratch);
+  A3VT_CHECK_ARG(ld_y % 4 == 0 && ld_y >= hidden);
+  A3VT_CHECK_ARG(al16(mesh) && al16(comp_s) && al16(comp_t) && al16(comp_c) && al16(scratch));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const QnetLayout L = qnet_layout(batch, n_vert, hidden, cut_len, 0);
+  QnetArgs a{};
+  a.mesh = mesh;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+  a.comp_s = comp_s; a.comp_t = comp_t; a.comp_c = comp_c;
+  a.batch = batch; a.n_vert = n_vert; a.hidden = hidden; a.cut_len = cut_len;
+  a.za = scratch + L.za;
+  a.ldza = pad4(cut_len) > 4 ? pad4(cut_len) : 4;
+  a.y = y;
+  a.ldy = ld_y;
+  path_count(PATH_QNET_FWD);
+  if (int rc = launch_qnet_fwd(a, s)) return rc;
+  if (cut_len > 0) {   // the rest of the layer, as a3vt_gcn_layer_fwd finishes one
+    int32_t *heavy;
+    if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
+    if (int rc = launch_csr_fwd(a.za, a.ldza, bias, cut_len, rowptr, col, val, heavy, n_vert, batch, y, ld_y, nullptr, 0, 1, s))
+      return rc;
+  }
+  return 0;
+}
+
+int a3vt_qnet_input_bwd(const float *mesh, const float *w1, const float *b1, const float *w2, const float *b2, const float *comp_c,
+                        int hidden, int cut_len, const int32_t *rowptrT, const int32_t *colT, const float *valT, int max_degreeT,
+                        int n_vert, int batch, const float *y, int ld_y, const float *grad_y, int ld_gy, float *d_s, float *d_t,
+                        float *d_c, float *dw1, float *db1, float *dw2, float *db2, float *grad_bias, float *scratch, void *stream) {
+  if (int rc = check_qnet_dims(hidden, cut_len, n_vert, batch)) return rc;
+  A3VT_CHECK_ARG(mesh && w1 && b1 && w2 && b2 && comp_c && rowptrT && colT && valT && y && grad_y && scratch);
+  A3VT_CHECK_ARG(d_s && d_t && d_c && dw1 && db1 && dw2 && db2 && grad_bias);
+  A3VT_CHECK_ARG(ld_y >= hidden && ld_gy >= hidden);
+  A3VT_CHECK_ARG(al16(mesh) && al16(comp_c) && al16(scratch));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const QnetLayout L = qnet_layout(batch, n_vert, hidden, cut_len, 1);
+  const size_t m = (size_t)batch * n_vert;
+  const int cpad = pad4(cut_len), npad = pad4(hidden);
+  float *ga = scratch + L.ga, *dz = scratch + L.dz;
+  path_count(PATH_QNET_BWD);
+  // the layer's own backward up to dZ, as a3vt_gcn_layer_bwd: activation mask, then A^T on the aggregated columns + bias gradient
+  if (int rc = launch_relu_split(grad_y, ld_gy, y, ld_y, 1, hidden, cpad, npad, (long long)m, ga, dz, s)) return rc;
+  if (int rc = launch_fill_zero(grad_bias, hidden, s)) return rc;
+  if (cut_len > 0) {
+    int32_t *heavyT;
+    if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
+    if (int rc = launch_csr_bwd(ga, cpad, cut_len, rowptrT, colT, valT, heavyT, n_vert, batch, dz, npad, scratch + L.db_slab, s))
+      return rc;
+    if (int rc = launch_slab_reduce(scratch + L.db_slab, csr_bwd_num_slabs(batch, n_vert), cpad, cut_len, grad_bias, s)) return rc;
+  }
+  QnetArgs a{};
+  a.mesh = mesh;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+  a.comp_c = comp_c;
+  a.batch = batch; a.n_vert = n_vert; a.hidden = hidden; a.cut_len = cut_len;
+  a.dz = dz;
+  a.slab = scratch + L.slab;
+  return launch_qnet_bwd(a, d_s, d_t, d_c, dw1, db1, dw2, db2, s);
+}
+
 // ---- FoldingNet fold (fold.hip) ----------------------------------------------------------------------------------------------
 static bool fold_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool fold_al4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
@@ -1662,6 +1789,17 @@ int a3vt_adam_step(void *const *param, const void *const *grad, void *const *exp
   ProfScope psc(PROF_OPT, static_cast<hipStream_t>(stream));
   return launch_adam(param, grad, exp_avg, exp_avg_sq, numel, chunk_tensor, chunk_off, n_chunks, lr, beta1, beta2, eps, weight_decay, step,
                      static_cast<hipStream_t>(stream));
+}
+
+int a3vt_adam_step_clamp(void *const *param, void *const *grad, void *const *exp_avg, void *const *exp_avg_sq, const long long *numel,
+                         const int *chunk_tensor, const long long *chunk_off, int n_chunks, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, long long step, double grad_clamp, void *stream) {
+  A3VT_CHECK_ARG(n_chunks >= 0 && step >= 1 && grad_clamp > 0.0);
+  A3VT_CHECK_ARG(n_chunks == 0 || (param && grad && exp_avg && exp_avg_sq && numel && chunk_tensor && chunk_off));
+  A3VT_CHECK_ARG(lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0);
+  ProfScope psc(PROF_OPT, static_cast<hipStream_t>(stream));
+  return launch_adam(param, const_cast<const void *const *>(grad), exp_avg, exp_avg_sq, numel, chunk_tensor, chunk_off, n_chunks, lr, beta1,
+                     beta2, eps, weight_decay, step, static_cast<hipStream_t>(stream), grad_clamp);
 }
 
 int a3vt_profile_enable(int on) {

@@ -69,6 +69,8 @@ enum PathCount {
   PATH_DWW,              // dww_kernel launches (exact fp32 dW on specialised waves; round 6)
   PATH_STACK_SPLIT,      // stack forward calls whose hidden layers aggregated with the P + bipartite split (gcn_csrqs.hip / csr16 split)
   PATH_CSR16T,           // csr16t_fwd_kernel launches (bf16 storage: tiled aggregation, neighbour rows from LDS; round 6)
+  PATH_QNET_FWD,         // a3vt_qnet_input_fwd calls (qnet_input.hip: the DDQN graph model's features + layer 0)
+  PATH_QNET_BWD,         // a3vt_qnet_input_bwd calls
   PATH_FOLD_FWD,         // a3vt_fold_fwd calls (fold.hip: one FoldingNet fold, forward)
   PATH_FOLD_BWD,         // a3vt_fold_bwd calls
   PATH_COUNT

@@ -357,7 +357,35 @@ int launch_conv5_wrw(const void *x, const void *gy, int batch, int h, int w, int
 int adam_chunk_elems();
 int launch_adam(void *const *param, const void *const *grad, void *const *exp_avg, void *const *exp_avg_sq,
                 const long long *numel, const int *chunk_tensor, const long long *chunk_off, int n_chunks, double lr, double beta1,
-                double beta2, double eps, double weight_decay, long long step, hipStream_t s);
+                double beta2, double eps, double weight_decay, long long step, hipStream_t s,
+                double grad_clamp = 0.0 /* > 0: clamp every gradient element to +-grad_clamp first, in place (grad is then written) */);
+
+// ddqn.hip: the double-DQN target, loss and loss gradient (policies/DDQN/ddqn.py:100-115)
+constexpr int kTdMaxBatch = 4096, kTdMaxActions = 304;
+int launch_ddqn_td(const float *q_cur, const float *q_next_online, const float *q_next_target, const float *mask, const float *actions,
+                   const float *rewards, const float *denom, int batch, int num_actions, int budget, float gamma, float *loss,
+                   float *diff, int32_t *best_next, float *target, hipStream_t s);
+int launch_ddqn_td_bwd(const float *diff, const float *actions, const float *grad_loss, int batch, int num_actions, float *dq_cur,
+                       hipStream_t s);
+
+// qnet_input.hip: features + product of the DDQN graph model's layer 0 without the (B N) x 300 feature rows
+struct QnetArgs {
+  const float *mesh;                  // [B][N][4]: x, y, z, mask token (0..3 as a float)
+  const float *w1, *b1, *w2, *b2;     // positional encoder: Linear(63, 25), Linear(25, 50)
+  const float *comp_s, *comp_t, *comp_c;   // composites [B][npad], [4][npad], [50][npad] (pad columns zero)
+  int batch, n_vert, hidden, cut_len;
+  float *za;                          // forward: raw Z of columns [0, pad4(cut_len)), [M][ldza]
+  int ldza;
+  float *y;                           // forward: relu(Z) of columns [cut_len, hidden), [M][ldy]
+  int ldy;
+  const float *dz;                    // backward: dZ [M][npad]
+  float *slab;                        // backward: per-workgroup partial sums, qnet_bwd_wgs() x qnet_slab_floats()
+};
+size_t qnet_slab_floats(int hidden);
+int qnet_bwd_wgs(int batch, int n_vert);
+int launch_qnet_fwd(const QnetArgs &a, hipStream_t s);
+// partial sums into a.slab, then one fixed-order reduce into the outputs ([B][npad], [4][npad], [50][npad], the encoder's shapes)
+int launch_qnet_bwd(const QnetArgs &a, float *d_s, float *d_t, float *d_c, float *dw1, float *db1, float *dw2, float *db2, hipStream_t s);
 
 // chamfer.hip
 size_t chamfer_scratch_bytes(int draws, int batch, int q);

@@ -91,7 +91,7 @@ GEMM_MODES = {"fp32": 0, "bf16": 1, "bf16s": 2, "fp32x3": 3}
 
 
 PATH_NAMES = ("stack_quad", "stack_rows", "rowgemm_adirect", "rowgemm3", "dw3", "dw_hybrid", "rowgemm16", "stack16_quad", "rowgemm_w", "dw_w", "stack_split", "csr16_tiles",
-              "fold_fwd", "fold_bwd")
+              "qnet_input_fwd", "qnet_input_bwd", "fold_fwd", "fold_bwd")
 
 
 def path_counts(reset=False):
@@ -954,6 +954,140 @@ def fold(code, g, conv1, conv2, conv3):
     w1 = conv1.weight.squeeze(-1)
     bias_s = torch.addmm(conv1.bias, code, w1[:, :width].t())
     return FoldFn.apply(bias_s, g, w1[:, width:], conv2.weight.squeeze(-1), conv2.bias, conv3.weight.squeeze(-1), conv3.bias)
+
+
+class DDQNTDFn(torch.autograd.Function):
+    """The double-DQN target, loss and loss gradient on ``a3vt_ddqn_td`` / ``a3vt_ddqn_td_bwd`` (csrc/ddqn.hip): one launch each,
+    no host sync.  Only ``q_cur`` carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, q_cur, q_next_online, q_next_target, mask, actions, rewards, denom, budget, gamma):
+        L = _lib.load()
+        q_cur, q_no, q_nt, mask = (_req(t, n) for t, n in ((q_cur, "q_cur"), (q_next_online, "q_next_online"),
+                                                           (q_next_target, "q_next_target"), (mask, "mask")))
+        actions, rewards = _req(actions, "actions"), _req(rewards, "rewards")
+        denom = None if denom is None else _req(denom, "denom")
+        B, A = q_cur.shape
+        if q_no.shape != (B, A) or q_nt.shape != (B, A) or mask.shape != (B, A) or actions.shape != (B,) or rewards.shape != (B,) or \
+                (denom is not None and denom.shape != (B,)):
+            raise RuntimeError("a3vt: ddqn_td operand shapes disagree")
+        dev = q_cur.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        diff, target = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+        best = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(L.a3vt_ddqn_td(_lib.ptr(q_cur), _lib.ptr(q_no), _lib.ptr(q_nt), _lib.ptr(mask), _lib.ptr(actions), _lib.ptr(rewards),
+                                  _lib.ptr(denom), B, A, int(budget), float(gamma), _lib.ptr(loss), _lib.ptr(diff), _lib.ptr(best),
+                                  _lib.ptr(target), _stream()), "ddqn_td")
+        ctx.save_for_backward(diff, actions)
+        ctx.shape = (B, A)
+        ctx.mark_non_differentiable(best, target)
+        return loss, best, target
+
+    @staticmethod
+    def backward(ctx, gloss, _gbest, _gtarget):
+        L = _lib.load()
+        diff, actions = ctx.saved_tensors
+        B, A = ctx.shape
+        gloss = _req(gloss, "grad_loss")
+        dq = torch.empty((B, A), dtype=torch.float32, device=diff.device)
+        _lib.check(L.a3vt_ddqn_td_bwd(_lib.ptr(diff), _lib.ptr(actions), _lib.ptr(gloss), B, A, _lib.ptr(dq), _stream()), "ddqn_td_bwd")
+        return dq, None, None, None, None, None, None, None, None
+
+
+def _ddqn_td_torch(q_cur, q_next_online, q_next_target, mask, actions, rewards, denom, budget, gamma):
+    """The same rule on torch ops (CPU tensors: the latent model, the host tests)."""
+    not_done = mask.sum(dim=1) < budget - 1
+    if denom is not None:
+        rewards = rewards / denom
+    act = actions.long().clamp(0, q_cur.shape[1] - 1)      # as the kernel: an action outside the table stays inside the row
+    q = q_cur.gather(1, act.unsqueeze(1)).squeeze(1)
+    with torch.no_grad():
+        best = q_next_online.detach().masked_fill(mask > 0, -1e10).max(1)[1]
+        nxt = q_next_target.detach().gather(1, best.unsqueeze(1)).squeeze(1)
+        target = gamma * torch.where(not_done, nxt, torch.zeros_like(nxt)) + rewards
+    return ((q - target) ** 2).mean(), best.to(torch.int32), target
+
+
+def ddqn_td(q_cur, q_next_online, q_next_target, mask, actions, rewards, denom, budget, gamma):
+    """The reference's double-DQN update rule (policies/DDQN/ddqn.py:88-115) -> (loss, best_next int32 [B], target [B]).
+    ``q_next_online`` is the UNPENALISED online next-state output: the ``-1e10`` where ``mask > 0`` is applied here.
+    ``denom``: ``first_score`` / ``score`` for the reference's reward normalisations, or None.  GPU tensors run one launch
+    (B <= 4096, A <= 304); CPU tensors take the same rule on torch ops."""
+    if not q_cur.is_cuda:
+        return _ddqn_td_torch(q_cur, q_next_online, q_next_target, mask, actions, rewards, denom, budget, gamma)
+    return DDQNTDFn.apply(q_cur, q_next_online.detach(), q_next_target.detach(), mask, actions, rewards, denom, budget, gamma)
+
+
+class QnetInputFn(torch.autograd.Function):
+    """Features + layer 0 of the DDQN graph model on ``a3vt_qnet_input_fwd/bwd`` (csrc/qnet_input.hip).  ``mesh`` (B, N, 4);
+    the composites ``comp_s`` (B, npad), ``comp_t`` (4, npad), ``comp_c`` (50, npad) come padded to npad = pad4(h) columns."""
+
+    @staticmethod
+    def forward(ctx, mesh, w1, b1, w2, b2, comp_s, comp_t, comp_c, bias, adj, cut_len, need_bwd):
+        L = _lib.load()
+        mesh, w1, b1, w2, b2, comp_s, comp_t, comp_c, bias = (
+            _req(t, n) for t, n in ((mesh, "mesh"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2"), (comp_s, "comp_s"),
+                                    (comp_t, "comp_t"), (comp_c, "comp_c"), (bias, "bias")))
+        B, N, _ = mesh.shape
+        h = bias.shape[0]
+        npad = (h + 3) // 4 * 4
+        if N != adj.n:
+            raise RuntimeError(f"a3vt: the mesh has {N} vertices but the adjacency has {adj.n}")
+        if mesh.shape[2] != 4 or w1.shape != (25, 63) or b1.shape != (25,) or w2.shape != (50, 25) or b2.shape != (50,) or \
+                comp_s.shape != (B, npad) or comp_t.shape != (4, npad) or comp_c.shape != (50, npad):
+            raise RuntimeError("a3vt: qnet_input operand shapes disagree")
+        y = torch.empty((B, N, npad), dtype=torch.float32, device=mesh.device)
+        scratch = workspace("qnet", L.a3vt_qnet_input_scratch_bytes(B, N, h, cut_len, 1 if need_bwd else 0), mesh.device)
+        _lib.check(L.a3vt_qnet_input_fwd(_lib.ptr(mesh), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(comp_s),
+                                         _lib.ptr(comp_t), _lib.ptr(comp_c), _lib.ptr(bias), h, cut_len, _lib.ptr(adj.rowptr),
+                                         _lib.ptr(adj.col), _lib.ptr(adj.val), adj.max_degree, N, B, _lib.ptr(y), npad,
+                                         _lib.ptr(scratch), _stream()), "qnet_input_fwd")
+        ctx.adj, ctx.dims = adj, (h, npad, cut_len)
+        ctx.save_for_backward(mesh, w1, b1, w2, b2, comp_c, y)
+        return y[..., :h] if npad != h else y
+
+    @staticmethod
+    def backward(ctx, gy):
+        L = _lib.load()
+        mesh, w1, b1, w2, b2, comp_c, y = ctx.saved_tensors
+        h, npad, cut_len = ctx.dims
+        adj = ctx.adj
+        B, N, _ = mesh.shape
+        gy = _req(gy, "grad_output")
+        dev = mesh.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        d_s, d_t, d_c = new(B, npad), new(4, npad), new(50, npad)
+        dw1, db1, dw2, db2, gb = new(25, 63), new(25), new(50, 25), new(50), new(h)
+        scratch = workspace("qnet", L.a3vt_qnet_input_scratch_bytes(B, N, h, cut_len, 1), dev)
+        _lib.check(L.a3vt_qnet_input_bwd(_lib.ptr(mesh), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(comp_c), h,
+                                         cut_len, _lib.ptr(adj.t_rowptr), _lib.ptr(adj.t_col), _lib.ptr(adj.t_val), adj.t_max_degree,
+                                         N, B, _lib.ptr(y), npad, _lib.ptr(gy), gy.shape[-1], _lib.ptr(d_s), _lib.ptr(d_t),
+                                         _lib.ptr(d_c), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2), _lib.ptr(gb),
+                                         _lib.ptr(scratch), _stream()), "qnet_input_bwd")
+        return None, dw1, db1, dw2, db2, d_s, d_t, d_c, gb, None, None, None
+
+
+def qnet_input_supported(hidden):
+    return 1 <= hidden <= 304
+
+
+def qnet_input(mesh, action, pos_enc, mask_table, weight, bias, adj, cut_len):
+    """``relu(layer0([action | PE(p) | E[token]]))`` of ``Graph_Model`` without the feature rows: ``mesh`` (B, N, 4) = positions
+    and mask tokens, ``action`` (B, 100) the action embedding, ``pos_enc`` the ``Positional_Encoder(100)`` module, ``mask_table``
+    (4, 100), ``weight`` (300, h) / ``bias`` (h,) of layer 0 -> (B, N, h).  The composites S = a Wa + b3 Wp, T = E Wm and
+    C = W3^T Wp are formed here on torch ops, so autograd carries their gradients to the action model, the table, the encoder's
+    last layer and the three row blocks of the weight; the kernel returns the gradients of the encoder's first two layers and of
+    the bias.  No position gradient."""
+    l1, l2, l3 = pos_enc.model[0], pos_enc.model[2], pos_enc.model[4]
+    wa, wp, wm = weight[:100], weight[100:200], weight[200:300]
+    comp_s = torch.addmm(l3.bias @ wp, action, wa)
+    comp_t = mask_table @ wm
+    comp_c = l3.weight.t() @ wp
+    pad = (-weight.shape[1]) % 4
+    if pad:
+        comp_s, comp_t, comp_c = (torch.nn.functional.pad(t, (0, pad)) for t in (comp_s, comp_t, comp_c))
+    params = (l1.weight, l1.bias, l2.weight, l2.bias, comp_s, comp_t, comp_c, bias)
+    return QnetInputFn.apply(mesh, *params, adj, cut_len, _wants_grad(*params))
 
 
 def rowgemm(a, w, bf16=False):

@@ -16,10 +16,15 @@ from .ops import _stream
 
 
 class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False, grad_clamp=None):
         # the plain (single-tensor) flavour: `step` counters live on the host, as in the reference's optimizer
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                          foreach=False, fused=False)
+        if grad_clamp is not None and not grad_clamp > 0:
+            raise ValueError(f"a3vt: grad_clamp={grad_clamp!r} must be positive (or None)")
+        # new (no torch counterpart): every gradient element is clamped to +-grad_clamp, in place, before the step — the reference
+        # learner's `param.grad.data.clamp_(-1, 1)` loop (policies/DDQN/ddqn.py:120-122) inside the a3vt_adam_step_clamp launch
+        self.grad_clamp = None if grad_clamp is None else float(grad_clamp)
         self._tables = {}        # group index -> (key, device tables)
         self.library_steps = 0   # steps taken by a3vt_adam_step (tests, bench)
 
@@ -88,6 +93,11 @@ class Adam(torch.optim.Adam):
                 break
             plans.append(got)
         if plans is None:
+            if self.grad_clamp is not None:
+                for group in self.param_groups:
+                    for p in group["params"]:
+                        if p.grad is not None:
+                            p.grad.clamp_(-self.grad_clamp, self.grad_clamp)
             # everything the kernel does not take: torch's own step on the same state (the function under the step-hook wrapper: this
             # call is already inside that wrapper, and the hooks must fire once)
             getattr(torch.optim.Adam.step, "__wrapped__", torch.optim.Adam.step)(self)
@@ -110,6 +120,12 @@ class Adam(torch.optim.Adam):
             for count, (p_, g_, m_, v_) in parts:
                 ptrs, numel, ct, co, n_chunks = self._table(gi if len(parts) == 1 else (gi, count), p_, g_, m_, v_)
                 with torch.cuda.device(p_[0].device):
+                    if self.grad_clamp is not None:
+                        _lib.check(L.a3vt_adam_step_clamp(_lib.ptr(ptrs[0]), _lib.ptr(ptrs[1]), _lib.ptr(ptrs[2]), _lib.ptr(ptrs[3]),
+                                                          _lib.ptr(numel), _lib.ptr(ct), _lib.ptr(co), n_chunks, float(group["lr"]),
+                                                          float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
+                                                          count, self.grad_clamp, _stream()), "adam_step_clamp")
+                        continue
                     _lib.check(L.a3vt_adam_step(_lib.ptr(ptrs[0]), _lib.ptr(ptrs[1]), _lib.ptr(ptrs[2]), _lib.ptr(ptrs[3]), _lib.ptr(numel),
                                                 _lib.ptr(ct), _lib.ptr(co), n_chunks, float(group["lr"]), float(beta1), float(beta2),
                                                 float(group["eps"]), float(group["weight_decay"]), count, _stream()), "adam_step")

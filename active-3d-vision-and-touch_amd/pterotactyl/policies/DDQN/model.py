@@ -6,12 +6,16 @@
 layers run as ``a3vt_gcn_layer_fwd/bwd`` calls through ``vision.model.GCN_layer``; the adjacency is the dense
 ``adj['adj']`` the reference keeps (:68), converted to CSR once.  ``Latent_Model`` (:15-61) is a plain MLP over
 auto-encoder latents and stays on torch ops.
+
+``args.fused_q_input`` (new, no reference counterpart; off unless set; ``DDQN.get_model`` sets it): the features and layer 0 run
+as ``ops.qnet_input`` (csrc/qnet_input.hip), which never forms the (B N) x 300 feature rows.  Same parameters, same state dict.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ...reconstruction.vision.model import GCN_layer, Mask_Encoder, Positional_Encoder, _csr_of  # noqa: F401
+from .... import ops as _ops
+from ...reconstruction.vision.model import GCN_layer, Mask_Encoder, Positional_Encoder, _csr_of, _cut_len  # noqa: F401
 from ...utility import utils
 
 
@@ -53,6 +57,7 @@ class Graph_Model(nn.Module):
         super().__init__()
         self.args = args
         self.num_layers = args.layers
+        self.fused_q_input = bool(getattr(args, "fused_q_input", False))
         input_size = 100
         self.adj = adj["adj"]      # dense (N,N), as the reference keeps it (:68)
         self._adj_info = adj       # the CSR handle is taken from / cached in this dict
@@ -68,14 +73,29 @@ class Graph_Model(nn.Module):
         sfx = "_n" if next else ""
         action = self.action_model(_dev(obs["mask" + sfx], dev))
         mesh_all = _dev(obs["mesh" + sfx], dev)
-        mesh, mask = mesh_all[:, :, :3], mesh_all[:, :, 3:]
-        feats = torch.cat((action.unsqueeze(1).expand(-1, mesh.shape[1], -1), self.positional_embedding(mesh),
-                           self.mask_embedding(mask)), dim=-1)
         adj = _csr_of(self._adj_info, "adj")
-        x = feats
-        for i, layer in enumerate(self.layers):   # layer 0 always takes the ReLU, also when it is the only layer (:118)
+        first = 0
+        if self._fused_input_ok(mesh_all):
+            l0 = self.layers[0]
+            nout = l0.weight.shape[-1]
+            x = _ops.qnet_input(mesh_all, action, self.positional_embedding, self.mask_embedding.model[0].weight, l0.weight[0], l0.bias,
+                                adj, _cut_len(nout, l0.cut_size) if l0.do_cut else nout)
+            first = 1
+        else:
+            mesh, mask = mesh_all[:, :, :3], mesh_all[:, :, 3:]
+            x = torch.cat((action.unsqueeze(1).expand(-1, mesh.shape[1], -1), self.positional_embedding(mesh),
+                           self.mask_embedding(mask)), dim=-1)
+        for i, layer in enumerate(self.layers[first:], first):   # layer 0 always takes the ReLU, also when it is the only layer (:118)
             x = layer(x, adj, F.relu if i == 0 or i != self.num_layers - 1 else _identity)
         return torch.max(x, dim=1)[0]
+
+    def _fused_input_ok(self, mesh_all):
+        """The fused input layer takes fp32 observations on the GPU that need no gradient, exact products and h <= 304; every
+        other call runs the unfused layer."""
+        l0 = self.layers[0]
+        return (self.fused_q_input and mesh_all.is_cuda and mesh_all.dim() == 3 and mesh_all.shape[-1] == 4 and not mesh_all.requires_grad
+                and l0.weight.shape[1] == 300 and _ops.qnet_input_supported(l0.weight.shape[-1])
+                and not _ops.gemm_mode(getattr(l0, "gemm_bf16", False)))
 
 
 def _identity(x):

@@ -351,6 +351,12 @@ int a3vt_adam_chunk_elems(void);
 int a3vt_adam_step(void *const *param, const void *const *grad, void *const *exp_avg, void *const *exp_avg_sq,
                    const long long *numel, const int *chunk_tensor, const long long *chunk_off, int n_chunks, double lr, double beta1,
                    double beta2, double eps, double weight_decay, long long step, void *stream);
+/* The same step with the reference learner's gradient clamp in front of it (policies/DDQN/ddqn.py:120-122, `param.grad.data.clamp_(-1, 1)`)
+ * inside the same launch: every gradient element is clamped to [-grad_clamp, grad_clamp] (grad_clamp > 0), the clamped value is what
+ * the step uses AND what is left in the gradient tensor, as the in-place clamp leaves it. */
+int a3vt_adam_step_clamp(void *const *param, void *const *grad, void *const *exp_avg, void *const *exp_avg_sq, const long long *numel,
+                         const int *chunk_tensor, const long long *chunk_off, int n_chunks, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, long long step, double grad_clamp, void *stream);
 
 /* Vertex update, model.py:250,270,283:  out[b][v] = in[b][v] + (v < n_vision ? update[b][v] : 0). */
 int a3vt_vertex_update(const float *verts_in, const float *update, int batch, int n_vert, int n_vision,
@@ -433,7 +439,7 @@ int a3vt_dbg_csr_algo(int algo);
  *   [8] rowgemmw_kernel launches  [9] dww_kernel launches (exact fp32 hidden-layer products, round 6)
  *   [10] stack forward calls that aggregated through the P + bipartite split (struct a3vt_adj_split)
  *   [11] csr16t forward launches (bf16 storage: aggregation from LDS tiles)
- *   [12] a3vt_fold_fwd calls  [13] a3vt_fold_bwd calls
+ *   [12] a3vt_qnet_input_fwd calls  [13] a3vt_qnet_input_bwd calls  [14] a3vt_fold_fwd calls  [15] a3vt_fold_bwd calls
  * Returns the number of counters the library keeps (entries beyond it are written as 0); reset != 0 clears them. */
 int a3vt_dbg_path_counts(long long *counts, int n, int reset);
 
@@ -472,6 +478,45 @@ int a3vt_fold_fwd(const float *bias_s, const float *g, int k, const float *w1g, 
 int a3vt_fold_bwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
                   const float *dy, int batch, int points, int width, float *d_bias_s, float *dg, float *dw1g, float *dw2, float *db2,
                   float *dw3, float *db3, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The double-DQN learner (policies/DDQN/ddqn.py:81-125).
+ *
+ * a3vt_ddqn_td: target, loss and what the loss gradient needs in one launch, from the three Q-network outputs of an update.
+ * q_cur, q_next_online, q_next_target, mask: [batch][num_actions] fp32; actions [batch] fp32 (the replay memory stores them as
+ * floats; values outside [0, num_actions) are clamped into it); rewards [batch]; denom [batch] or NULL (rewards / denom: the
+ * reference's "first" / "current" normalisation).  Per sample: not_done = sum(mask) < budget - 1 (the CURRENT mask, as the
+ * reference); best_next = argmax of q_next_online with -1e10 where mask > 0, the lowest index on a tie;
+ * target = gamma * (not_done ? q_next_target[best_next] : 0) + reward; diff = q_cur[action] - target; loss[0] = mean(diff^2),
+ * summed in a fixed order (no atomics: the same bits on every call).  batch <= 4096, num_actions <= 304; anything else is
+ * an argument error.  No host sync.
+ * a3vt_ddqn_td_bwd: dq_cur[b][a] = grad_loss[0] * 2 * diff[b] / batch at a = actions[b], 0 elsewhere (grad_loss: device). */
+int a3vt_ddqn_td(const float *q_cur, const float *q_next_online, const float *q_next_target, const float *mask, const float *actions,
+                 const float *rewards, const float *denom, int batch, int num_actions, int budget, float gamma, float *loss,
+                 float *diff, int32_t *best_next, float *target, void *stream);
+int a3vt_ddqn_td_bwd(const float *diff, const float *actions, const float *grad_loss, int batch, int num_actions, float *dq_cur,
+                     void *stream);
+
+/* Graph_Model's features and layer 0 (policies/DDQN/model.py:100-118) without the (batch * n_vert) x 300 feature rows:
+ *   y = relu(layer0([a_b | PE(p) | E[token]])) = relu(agg(S[b] + T[token] + relu(L2(relu(L1(nerf(p) ++ p)))) C))
+ * with the composites S = a Wa + b3 Wp [batch][npad], T = E Wm [4][npad], C = W3^T Wp [50][npad] formed by the caller
+ * (npad = hidden rounded up to 4, pad columns zero; Wa / Wp / Wm = the three 100-row blocks of the layer's weight, L3 = (W3,
+ * b3) the positional encoder's last Linear).  mesh [batch][n_vert][4] = x, y, z and the mask token (0..3) as a float, the
+ * observation's layout; w1 [25][63], b1 [25], w2 [50][25], b2 [50] the encoder's first two Linear layers.  "agg": the first
+ * cut_len columns are aggregated over the CSR and take `bias`, the rest pass through, then the ReLU — a3vt_gcn_layer_fwd with
+ * relu = 1.  Exact fp32 throughout.  y [batch * n_vert][ld_y], ld_y % 4 == 0.  hidden <= 304.  mesh, the composites and the
+ * scratch (a3vt_qnet_input_scratch_bytes, backward != 0 for _bwd) are 16-byte aligned.
+ * a3vt_qnet_input_bwd: from grad_y and the forward's y, writes d_s [batch][npad], d_t [4][npad], d_c [50][npad], dw1, db1, dw2,
+ * db2 and grad_bias [hidden]; every sum has a fixed order (same bits on every call).  There is no position gradient. */
+size_t a3vt_qnet_input_scratch_bytes(int batch, int n_vert, int hidden, int cut_len, int backward);
+int a3vt_qnet_input_fwd(const float *mesh, const float *w1, const float *b1, const float *w2, const float *b2, const float *comp_s,
+                        const float *comp_t, const float *comp_c, const float *bias, int hidden, int cut_len, const int32_t *rowptr,
+                        const int32_t *col, const float *val, int max_degree, int n_vert, int batch, float *y, int ld_y,
+                        float *scratch, void *stream);
+int a3vt_qnet_input_bwd(const float *mesh, const float *w1, const float *b1, const float *w2, const float *b2, const float *comp_c,
+                        int hidden, int cut_len, const int32_t *rowptrT, const int32_t *colT, const float *valT, int max_degreeT,
+                        int n_vert, int batch, const float *y, int ld_y, const float *grad_y, int ld_gy, float *d_s, float *d_t,
+                        float *d_c, float *dw1, float *db1, float *dw2, float *db2, float *grad_bias, float *scratch, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Deferred finite check (replaces the blocking NaN trap of model.py:326-329): sets *flag (device

@@ -1,0 +1,166 @@
+#!/usr/bin/env python
+"""One DDQN update and one action choice at the reference's defaults (t_g: N = 2324, train_batch_size 16, 4 layers x 200, 50
+actions), ALTERNATING in one process between
+
+* new:    ``DDQN.update_parameters`` with ``fused_q_input=True`` — fused Q-network input layer, ``a3vt_ddqn_td``, the clamp
+          inside the optimizer launch, a device-resident replay memory; and
+* parent: the same step from what the parent commit had — ``Graph_Model`` with the knob off, the reference's TD lines on torch
+          ops (its Python loop over the batch included), torch's ``clamp_`` per parameter, the unclamped one-launch Adam, a host
+          replay memory.
+
+After warm-up every call is bracketed by device events on the stream; medians with p10 / p90 over ``--calls`` calls per round,
+``--rounds`` rounds per path, in turn.  ``--launches`` instead counts kernel launches per update for both paths: it starts
+``rocprofv3 --kernel-trace --stats`` on this tool (``--only PATH --updates K``) for two values of K in fresh child processes and
+divides the difference of the launch totals by the difference of K (no counters are collected).
+Run on the GPU box:  python tools/ddqn_bench.py [--launches]"""
+import argparse
+import csv
+import glob
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--calls", type=int, default=60, help="timed calls per round and path")
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--warmup", type=int, default=10)
+ap.add_argument("--launches", action="store_true", help="count kernel launches per update with rocprofv3 (child processes)")
+ap.add_argument("--only", choices=("new", "parent"), help="run --updates updates of one path and exit (what --launches profiles)")
+ap.add_argument("--updates", type=int, default=10)
+a = ap.parse_args()
+
+
+def launches_per_update():
+    out = {}
+    for path in ("new", "parent"):
+        totals = []
+        for k in (5, 25):
+            with tempfile.TemporaryDirectory() as d:
+                cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable,
+                       os.path.abspath(__file__), "--only", path, "--updates", str(k)]
+                subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+                stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
+                totals.append(sum(int(r["Calls"]) for f in stats for r in csv.DictReader(open(f))))
+        out[path] = (totals[1] - totals[0]) / 20.0
+        print(f"kernel launches per update, {path:6s}: {out[path]:7.1f}   (rocprofv3 --kernel-trace --stats: {totals[1]} launches over 25 "
+              f"updates, {totals[0]} over 5)")
+    print(f"launches new / parent = {out['new'] / out['parent']:.3f}")
+
+
+if a.launches:
+    launches_per_update()
+    sys.exit(0)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from a3vt_amd import optim  # noqa: E402
+from a3vt_amd.pterotactyl.policies import replay  # noqa: E402
+from a3vt_amd.pterotactyl.policies.DDQN import ddqn  # noqa: E402
+from a3vt_amd.pterotactyl.utility import utils  # noqa: E402
+from a3vt_amd.synthetic import make_args  # noqa: E402
+
+dev = torch.device("cuda", 0)
+N, B = 2324, 16
+
+
+def make(fused, device_replay):
+    args = make_args(use_touch=True, num_grasps=5, finger=False, layers=4, hidden_dim=200, num_actions=50, mem_capacity=300, burn_in=20,
+                     train_batch_size=B, pretrained=False, lr=1e-3, gamma=0.9, budget=5, use_recon=True, use_latent=False,
+                     normalization="first", fused_q_input=fused)
+    info, verts = utils.load_mesh_vision(args, "vision_charts")
+    torch.manual_seed(0)
+    memory = replay.ReplayMemory(args, device=dev if device_replay else None)
+    learner = ddqn.DDQN(args, info, memory).to(dev)
+    target = ddqn.DDQN(args, info, None).to(dev)
+    target.load_state_dict(learner.state_dict())
+    g = torch.Generator().manual_seed(1)
+    n = 64
+    mesh = torch.zeros(n, N, 4)
+    mesh[:, :1824, :3] = verts.cpu() + 0.01 * torch.randn(n, 1824, 3, generator=g)
+    mesh[:, :1824, 3] = 3
+    mesh[:, 1824:, :3] = (torch.rand(n, N - 1824, 3, generator=g) - 0.5) * 0.3
+    mesh[:, 1824:, 3] = torch.randint(0, 3, (n, N - 1824), generator=g).float()
+    mask = (torch.rand(n, 50, generator=g) < 0.04).float()
+    obs = {"mesh": mesh, "mask": mask, "score": 1.0 + torch.rand(n, generator=g), "first_score": 2.0 + torch.rand(n, generator=g)}
+    nxt = {"mesh": mesh.roll(1, 0), "mask": mask, "score": torch.rand(n, generator=g)}
+    learner.add_experience(np.arange(n) % 50, obs, nxt, 0.1 * torch.rand(n, generator=g))
+    act_obs = {"mesh": mesh[:B].to(dev), "mask": mask[:B].to(dev)}
+    return learner, target, act_obs
+
+
+def parent_update(learner, target, optimizer):
+    """policies/DDQN/ddqn.py:81-125 as the parent commit could run it."""
+    args = learner.args
+    learner.model.train()
+    batch = learner.replay.sample()
+    not_done = batch["mask"].to(dev).sum(dim=1) < args.budget - 1
+    actions, rewards = batch["actions"].to(dev), batch["rewards"].to(dev) / batch["first_score"].to(dev)
+    q = learner.forward(batch, penalize=False).gather(1, actions.unsqueeze(1).long()).squeeze()
+    with torch.no_grad():
+        best = learner.forward(batch, next=True).detach().max(1)[1]
+        values = target.forward(batch, next=True, penalize=False).detach()
+        nxt = torch.zeros(q.shape[0], device=dev)
+        for i in range(q.shape[0]):
+            if not_done[i]:
+                nxt[i] = values[i][best[i]]
+        tgt = args.gamma * nxt + rewards
+    loss = ((q - tgt) ** 2).mean()
+    optimizer.zero_grad()
+    loss.backward()
+    for p in learner.parameters():
+        if p.grad is not None:
+            p.grad.data.clamp_(-1, 1)
+    optimizer.step()
+    return loss.item()
+
+
+def paths():
+    new, new_t, new_obs = make(True, True)
+    old, old_t, old_obs = make(False, False)
+    old_opt = optim.Adam(old.model.parameters(), lr=old.args.lr)
+    return {"new": (lambda: new.update_parameters(new_t), lambda: new.get_action(new_obs, 0.0)),
+            "parent": (lambda: parent_update(old, old_t, old_opt), lambda: old.get_action(old_obs, 0.0))}
+
+
+def timed(fn, calls):
+    ms = []
+    for _ in range(calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+if a.only:
+    np.random.seed(0)
+    update = paths()[a.only][0]
+    for _ in range(a.updates):
+        update()
+    torch.cuda.synchronize()
+    sys.exit(0)
+
+np.random.seed(0)
+fns = paths()
+for what, idx in (("update_parameters", 0), ("get_action", 1)):
+    for k in fns:
+        for _ in range(a.warmup):
+            fns[k][idx]()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(a.rounds):
+        for k in fns:
+            ms[k] += timed(fns[k][idx], a.calls)
+    pct = {k: np.percentile(v, [10, 50, 90]) for k, v in ms.items()}
+    for k in fns:
+        print(f"{what:17s} {k:6s}: median {pct[k][1]:7.3f} ms  p10 {pct[k][0]:7.3f}  p90 {pct[k][2]:7.3f}   ({len(ms[k])} calls, "
+              f"B = {B}, N = {N}, 4 x 200)")
+    print(f"{what:17s} new / parent = {pct['new'][1] / pct['parent'][1]:.3f} (medians); new p90 {'<' if pct['new'][2] < pct['parent'][0] else '>='} "
+          f"parent p10")
