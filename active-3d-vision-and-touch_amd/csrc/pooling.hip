@@ -13,6 +13,8 @@
 // Backward: map gradients are accumulated per (sample, map, channel block) in LDS over all vertices of the sample
 // (ds_add_f32); a sample's vertices are split over a few workgroups whose images are then added to global memory
 // (one atomic per pixel-channel per workgroup); the position gradient is a wave reduction per vertex.
+#include <float.h>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -33,8 +35,10 @@ __device__ __forceinline__ Bilinear bilinear_setup(float gx, float gy, int H, in
   b.ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
   b.iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
   const float fx = floorf(b.ix), fy = floorf(b.iy);
-  b.x0 = (int)fx;
-  b.y0 = (int)fy;
+  // clamped to [-2, size] before the conversion (every such corner is out of range either way): past 2^31 the conversion
+  // saturates, x0 + 1 wraps to INT_MIN and passes `< W`, and the corner of a vertex far off screen would be read
+  b.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W);
+  b.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H);
   const float x1 = fx + 1.f, y1 = fy + 1.f;
   b.wnw = (x1 - b.ix) * (y1 - b.iy);
   b.wne = (b.ix - fx) * (y1 - b.iy);
@@ -305,16 +309,20 @@ __device__ __forceinline__ void pool_bwd_maps_body(const PoolArgs &a, int k, int
   const int cl = (threadIdx.x % lanes_c) * 4, vs = threadIdx.x / lanes_c;
   const bool lane_on = cl < cb && vs < vpar;
   float mx = 0.f;
+  bool bad = false;  // a NaN or an infinity among this thread's gradients
   for (int v = vs; v < a.n_vert && lane_on; v += vpar) {
     const f32x4 gv = *reinterpret_cast<const f32x4 *>(a.gfeats + ((long long)b * a.n_vert + v) * a.ld + a.off[k] + c0 + cl);
     mx = fmaxf(fmaxf(mx, fmaxf(fabsf(gv[0]), fabsf(gv[1]))), fmaxf(fabsf(gv[2]), fabsf(gv[3])));
+    // fmaxf returns its other operand for a NaN: a NaN would leave mx finite and be lost in the integer conversion below
+    if (!(fabsf(gv[0]) <= FLT_MAX && fabsf(gv[1]) <= FLT_MAX && fabsf(gv[2]) <= FLT_MAX && fabsf(gv[3]) <= FLT_MAX)) bad = true;
   }
+  if (bad) mx = __builtin_inff();  // an infinity survives every fmaxf of the reductions
   mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   for (int i = threadIdx.x; i < H * W * CB; i += 256) img[i] = 0;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const bool finite = mx < 3.0e38f;
+  const bool finite = mx <= FLT_MAX;
   const FixScale fs = fix_scale(finite ? mx : 0.f, a.n_vert);
   for (int v = vs; v < a.n_vert && lane_on; v += vpar) {
     const long long row = (long long)b * a.n_vert + v;

@@ -247,10 +247,11 @@ def image_encoder(img, state, prefix, ker=5, num_blocks=6, layers_per_block=3, t
     return maps
 
 
-def image_pooling(maps, verts):
-    """Image_Encoder.pooling (model.py:70-103)."""
+def image_pooling(maps, verts, matrix=None):
+    """Image_Encoder.pooling (model.py:70-103); ``matrix``: another 3 x 4 projection than the camera's (tests)."""
+    matrix = projection_matrix() if matrix is None else torch.as_tensor(matrix)
     ext = torch.cat((verts, torch.ones_like(verts[..., :1])), dim=-1)
-    ext = torch.matmul(ext, projection_matrix().to(verts.dtype).permute(1, 0)).clone()
+    ext = torch.matmul(ext, matrix.to(verts.dtype).permute(1, 0)).clone()
     ext[:, :, 2][ext[:, :, 2] == 0] = 0.1
     xs = ext[:, :, 1] / ext[:, :, 2] / 256.0
     xs[torch.isinf(xs)] = 0.5
