@@ -1542,7 +1542,8 @@ int a3vt_sample_points_fwd(const float *verts, const int32_t *faces, const float
 int a3vt_sample_points_bwd(const int32_t *faces, int batch, int n_vert, int n_faces, int draws, int num,
                            const int32_t *face_idx, const float *u, const float *v, const float *grad_points,
                            float *grad_verts, void *stream) {
-  A3VT_CHECK_ARG(faces && face_idx && u && v && grad_points && grad_verts && batch > 0 && draws > 0 && num > 0);
+  A3VT_CHECK_ARG(faces && face_idx && u && v && grad_points && grad_verts && batch > 0 && n_vert > 0 && n_faces > 0 &&
+                 draws > 0 && num > 0);
   ProfScope psc(PROF_LOSS, static_cast<hipStream_t>(stream));
   return launch_sample_bwd(faces, batch, n_vert, n_faces, draws, num, face_idx, u, v, grad_points, grad_verts,
                            static_cast<hipStream_t>(stream));

@@ -21,11 +21,21 @@ __device__ __forceinline__ float tri_area(const float *__restrict__ vb, const in
   return 0.5f * sqrtf(nx * nx + ny * ny + nz * nz);
 }
 
-// One workgroup per mesh: total area, then inclusive scan of p_f = |a_f / total| (NaN -> 1).
+// One workgroup per mesh: total area, then inclusive scan of p_f = |a_f / total| (NaN -> 1).  Thread t owns the chunk of
+// `per` consecutive faces [t * per, (t + 1) * per) and scans it serially from base_t, the serial sum of the chunk sums
+// before t.  base_{t+1} and the last entry of chunk t are two fp32 roundings of one sum and may differ by a few ulp either
+// way, so the chunks are then joined: carry_t is the entry actually written for the last face before chunk t, and
+//   * a chunk that starts with a zero-area face (p == 0) is scanned from 0 and written as carry_t + local sum: its
+//     leading faces repeat carry_t bit for bit;
+//   * every other chunk keeps its scan from base_t, raised to carry_t where it lies below.
+// The CDF therefore never steps down and a zero-area face repeats its predecessor's bits, at a chunk start as anywhere
+// else, so sample_fwd_kernel's search can never return it; on a mesh whose chunk starts all have p well above an ulp the
+// join changes no bit of the plain scan.
 __global__ __launch_bounds__(256) void face_cdf_kernel(const float *__restrict__ verts,
                                                        const int32_t *__restrict__ faces, int n_vert, int n_faces,
                                                        float *__restrict__ cdf) {
   __shared__ float part[256];
+  __shared__ bool join_add[256];
   __shared__ float total_s;
   const int b = blockIdx.x, t = threadIdx.x;
   const float *vb = verts + (long long)b * n_vert * 3;
@@ -66,15 +76,41 @@ __global__ __launch_bounds__(256) void face_cdf_kernel(const float *__restrict__
     }
   }
   __syncthreads();
-  float run = part[t];
+  const float base = part[t];
   float *cb = cdf + (long long)b * n_faces;
+  bool add = true;  // the chunk starts with a zero-area face (or is empty): scanned from 0, joined by addition
+  float run = 0.f, first = 0.f;
   for (int f = f0; f < f1; ++f) {
     float a = tri_area(vb, faces + 3 * f);
     if (a != a) a = 0.f;
     float p = fabsf(a / total);
     if (p != p) p = 1.f;
+    if (f == f0 && p != 0.f) {
+      add = false;
+      run = base;
+    }
     run += p;
     cb[f] = run;
+    if (f == f0) first = run;
+  }
+  __syncthreads();  // every base has been read
+  part[t] = run;
+  join_add[t] = add;
+  __syncthreads();
+  if (t == 0) {
+    float carry = 0.f;
+    for (int i = 0; i < 256; ++i) {
+      const float v = part[i];
+      part[i] = carry;
+      carry = join_add[i] ? carry + v : fmaxf(v, carry);
+    }
+  }
+  __syncthreads();
+  const float carry = part[t];
+  if (add) {
+    for (int f = f0; f < f1; ++f) cb[f] = carry + cb[f];
+  } else if (first < carry) {
+    for (int f = f0; f < f1 && cb[f] < carry; ++f) cb[f] = carry;
   }
 }
 
@@ -179,11 +215,15 @@ __global__ __launch_bounds__(1024) void sample_bwd_kernel(const int32_t *__restr
   const int b = blockIdx.x, tid = threadIdx.x;
   const int tile = (n_vert + gridDim.y - 1) / gridDim.y;
   const int v0 = blockIdx.y * tile, v1 = min(n_vert, v0 + tile);
-  // bound on |w_k * g| (0 <= w_k <= 1): the largest |grad_points| component of this mesh's samples
+  // bound on |w_k * g| (0 <= w_k <= 1): the largest |grad_points| component of this mesh's samples.  fmaxf drops a NaN
+  // operand, so a NaN component enters the maximum as +inf: NaN and inf alike make the mesh's whole gradient NaN.
   float mx = 0.f;
   for (int d = 0; d < draws; ++d) {
     const float *g = gp + ((long long)d * batch + b) * num * 3;
-    for (int i = tid; i < num * 3; i += 1024) mx = fmaxf(mx, fabsf(g[i]));
+    for (int i = tid; i < num * 3; i += 1024) {
+      const float a = fabsf(g[i]);
+      mx = fmaxf(mx, a != a ? __builtin_inff() : a);
+    }
   }
   mx = wave_max(mx);
   if ((tid & 63) == 0) red[tid >> 6] = mx;

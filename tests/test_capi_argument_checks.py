@@ -155,3 +155,33 @@ def test_conv5_and_adam_entry_points_refuse_bad_arguments(L):
     assert L.a3vt_adam_step(*ad(b1=1.0)) != 0 and L.a3vt_adam_step(*ad(b2=-0.1)) != 0 and L.a3vt_adam_step(*ad(lr=-1.0)) != 0
     assert L.a3vt_adam_step(*ad(n=-1)) != 0
     assert L.a3vt_adam_chunk_elems() == 4096
+
+
+def test_sampling_entry_points_refuse_bad_arguments(L):
+    """a3vt_face_cdf, a3vt_sample_points_fwd and a3vt_sample_points_bwd: an empty mesh, an empty draw or a NULL operand is
+    refused by the argument check (the backward would otherwise divide by n_vert's tile count on the host); the forward also
+    refuses injected faces without their u / v, and a missing CDF when nothing is injected."""
+    u64 = ctypes.c_uint64
+    cdf = lambda **kw: [kw.get("verts", FAKE), kw.get("faces", FAKE), kw.get("b", 2), kw.get("nv", 162), kw.get("nf", 320),   # noqa: E731
+                        kw.get("cdf", FAKE), None]
+    fwd = lambda **kw: [kw.get("verts", FAKE), kw.get("faces", FAKE), kw.get("cdf", FAKE), kw.get("b", 2), kw.get("nv", 162),   # noqa: E731
+                        kw.get("nf", 320), kw.get("draws", 3), kw.get("num", 100), kw.get("fi", None), kw.get("u", None),
+                        kw.get("v", None), u64(1), u64(0), kw.get("pts", FAKE), FAKE, FAKE, FAKE, None]
+    bwd = lambda **kw: [kw.get("faces", FAKE), kw.get("b", 2), kw.get("nv", 162), kw.get("nf", 320), kw.get("draws", 3),   # noqa: E731
+                        kw.get("num", 100), kw.get("fi", FAKE), kw.get("u", FAKE), kw.get("v", FAKE), kw.get("gp", FAKE),
+                        kw.get("gv", FAKE), None]
+    for fn, args, sizes, operands in ((L.a3vt_face_cdf, cdf, ("b", "nv", "nf"), ("verts", "faces", "cdf")),
+                                      (L.a3vt_sample_points_fwd, fwd, ("b", "nv", "nf", "draws", "num"), ("verts", "faces", "pts")),
+                                      (L.a3vt_sample_points_bwd, bwd, ("b", "nv", "nf", "draws", "num"),
+                                       ("faces", "fi", "u", "v", "gp", "gv"))):
+        for name in sizes:
+            for bad in (0, -1):
+                assert fn(*args(**{name: bad})) != 0, (fn.__name__, name, bad)
+                assert "argument check failed" in _err(L)
+        for name in operands:
+            assert fn(*args(**{name: None})) != 0, (fn.__name__, name)
+            assert "argument check failed" in _err(L)
+    assert L.a3vt_sample_points_fwd(*fwd(fi=FAKE)) != 0 and "without u_in/v_in" in _err(L)
+    assert L.a3vt_sample_points_fwd(*fwd(fi=FAKE, u=FAKE)) != 0 and "without u_in/v_in" in _err(L)
+    assert L.a3vt_sample_points_fwd(*fwd(fi=FAKE, v=FAKE)) != 0 and "without u_in/v_in" in _err(L)
+    assert L.a3vt_sample_points_fwd(*fwd(cdf=None)) != 0 and "cdf required" in _err(L)
