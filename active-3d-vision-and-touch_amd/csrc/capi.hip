@@ -43,6 +43,17 @@ static const float *zero_page() {  // the symbol has one address per device
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Bump allocator of the scratch layouts below: float offsets, every region 64 floats (256 B) aligned
+struct Arena {
+  size_t off = 0;
+  size_t take(size_t nfloats) {
+    const size_t o = off;
+    off = align_up(off + nfloats, 64);
+    return o;
+  }
+  size_t take16(size_t nelems) { return take((nelems + 1) / 2 + 64); }   // bf16 region (+ slack for 16-byte tails)
+};
+
 // ---- optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg).
 // Off by default; when on, every MFMA launch of the GCN stack is bracketed by an event pair.
 enum { PROF_GEMM_FWD = 0, PROF_GEMM_DX = 1, PROF_DW = 2, PROF_AGG = 3, PROF_OUT = 4, PROF_SEARCH = 5, PROF_LOSS = 6, PROF_ENC = 7,
@@ -59,8 +70,8 @@ static Prof g_prof;
 struct ProfScope {
   int slot = -1;
   hipStream_t s;
-  ProfScope(int cls, hipStream_t stream) : s(stream) {
-    if (!g_prof.on || g_prof.used >= Prof::kMax) return;
+  ProfScope(int cls, hipStream_t stream, bool timed = true) : s(stream) {
+    if (!timed || !g_prof.on || g_prof.used >= Prof::kMax) return;
     slot = g_prof.used++;
     if (slot >= g_prof.created) {
       (void)hipEventCreate(&g_prof.ev[slot][0]);
@@ -78,13 +89,15 @@ struct ProfScope {
 // Scratch layout of a GCN stack call (float offsets, every region 256-B aligned).
 struct StackLayout {
   size_t wt, wt_stride;  // per hidden layer: transposed (fwd) or padded (bwd) weight image
-  size_t za;             // [M][cpad]
+  size_t za;             // [M][ldza]
+  int ldza;              // row stride of za and gq: cpad, or 4 (dummy rows) without aggregated channels
   size_t z3;             // [2][M][4]
   size_t ping[2];        // [M][hidden] each (fwd without acts: layer outputs; bwd: gradients)
   size_t panel;          // bwd, inputs wider than 304 columns only: [M][300] contiguous column block of X_0 for dW_0
   size_t dw_slab, db_slab, thin_dw_slab, thin_db_slab;
+  size_t db_layer_stride;   // db_slab: one block of bias-partial rows per hidden layer
   size_t heavy;          // int32 list of hub rows (csr_heavy_scratch_ints)
-  size_t gq;             // bwd: quad-major gradient columns [0, cpad) for the channel-sliced aggregation, [M][cpad]
+  size_t gq;             // bwd: quad-major gradient columns [0, cpad) for the channel-sliced aggregation, [M][ldza]
   size_t ell;            // slot-major index image of the adjacency (csrq_ell_ints)
   size_t total;
 };
@@ -138,10 +151,6 @@ static int stash_layout_lookup(const void *masks) {   // 1 / 0, or -1 when this 
   auto it = g_stash_layout.find(masks);
   return it == g_stash_layout.end() ? -1 : it->second;
 }
-// sign bytes of the aggregated channels, quad-major [batch][Q][n_vert] per hidden layer, kept behind the row-major
-// sign bytes in the caller's `masks` buffer
-static inline size_t signq_stride(size_t m, int cut_len) { return align_up(m * (size_t)(pad4(cut_len) / 4), 256); }
-
 // bias gradients of the hidden layers [0, last) from per-layer blocks of partial rows (layer i at slab + i * layer_stride)
 static int reduce_bias_partials(const float *slab, size_t layer_stride, int nslab, int cpad, int cut_len, int hidden, int last,
                                 float *const *grad_biases, int acc, hipStream_t s) {
@@ -263,37 +272,63 @@ static StackLayout stack_layout(int batch, int n_vert, int in_features, int hidd
   StackLayout L{};
   const size_t m = (size_t)batch * n_vert;
   const int cpad = pad4(cut_len);
-  size_t off = 0;
-  auto take = [&](size_t nfloats) {
-    const size_t o = off;
-    off = align_up(off + nfloats, 64);
-    return o;
-  };
+  Arena a;
   const int kmax = hidden > pad4(in_features) ? hidden : pad4(in_features);
   L.wt_stride = align_up((size_t)rowgemm_bt_rows(kmax) * pad16(kmax), 64);
   if (gemm_mode == GEMM_FP32X3 && L.wt_stride < 3 * (size_t)kX3ImageFloats) L.wt_stride = 3 * (size_t)kX3ImageFloats;   // hi / mid / lo images (gcn_gemm3.hip)
-  L.wt = take(L.wt_stride * (num_layers > 1 ? num_layers - 1 : 1));
-  L.za = take(m * (cpad > 4 ? cpad : 4));
-  L.z3 = take(2 * m * 4);
-  L.ping[0] = take(m * hidden);
-  L.ping[1] = take(m * hidden);
-  L.heavy = take(csr_heavy_scratch_ints(n_vert));
-  L.ell = take(csrq_ell_ints(n_vert));
+  L.wt = a.take(L.wt_stride * (num_layers > 1 ? num_layers - 1 : 1));
+  L.ldza = cpad > 4 ? cpad : 4;
+  L.za = a.take(m * L.ldza);
+  L.z3 = a.take(2 * m * 4);
+  L.ping[0] = a.take(m * hidden);
+  L.ping[1] = a.take(m * hidden);
+  L.heavy = a.take(csr_heavy_scratch_ints(n_vert));
+  L.ell = a.take(csrq_ell_ints(n_vert));
   if (need_backward) {
     const size_t kin = kmax;
     // its own region: with hidden < 300 a ping buffer ([M][hidden]) is smaller than a 300-column block of X_0
-    L.panel = take(pad4(in_features) > 304 ? m * 300 : 0);
-    L.dw_slab = take((size_t)dw_slab_capacity(hidden) * kin * hidden);
+    L.panel = a.take(pad4(in_features) > 304 ? m * 300 : 0);
+    L.dw_slab = a.take((size_t)dw_slab_capacity(hidden) * kin * hidden);
     const size_t nslab = (size_t)csr_bwd_num_slabs(batch, n_vert) > (size_t)batch ? csr_bwd_num_slabs(batch, n_vert) : batch;
-    // one block of partial rows PER LAYER ([batch][cpad] on the channel-sliced path, [row-walk workgroups][cpad] otherwise),
-    // reduced by one launch at the end of the backward
-    L.db_slab = take(align_up(nslab * cpad, 64) * (num_layers > 1 ? num_layers - 1 : 1));
-    L.gq = take(m * (cpad > 4 ? cpad : 4));
-    L.thin_dw_slab = take((size_t)thin_num_slabs() * kin * 3);
-    L.thin_db_slab = take((size_t)thin_num_slabs() * 3);
+    // one block of partial rows PER LAYER ([batch][cpad] on the channel-sliced path, [row-walk workgroups][cpad] otherwise:
+    // the stride holds either), reduced by one launch at the end of the backward
+    L.db_layer_stride = align_up(nslab * cpad, 64);
+    L.db_slab = a.take(L.db_layer_stride * (num_layers > 1 ? num_layers - 1 : 1));
+    L.gq = a.take(m * L.ldza);
+    L.thin_dw_slab = a.take((size_t)thin_num_slabs() * kin * 3);
+    L.thin_db_slab = a.take((size_t)thin_num_slabs() * 3);
   }
-  L.total = off;
+  L.total = a.off;
   return L;
+}
+
+// dW = X^T dZ of one layer into grad [kin][d.n_out] (+= when acc).  `d` comes filled in except for x, ldx and k_in; x, ldx:
+// the layer's input rows.  The kernel covers up to 304 input channels per pass; wider inputs (the 448-wide image model's
+// first layer) go in column blocks of <= 300, each first copied into the contiguous `panel` ([M][300]).  Up to 304 channels
+// are ONE pass: only the panels start at column c0 (a second pass over 301..304 channels would read X from column 0).
+// Hybrid rows (d.xq_nvert > 0) are never wider than that; their ldx is the width of the staged image.
+static int dw_panels(DwArgs d, const float *x, int ldx, int kin, float *panel, float *grad, int acc, bool timed, hipStream_t s) {
+  const int cblk = kin > 304 ? 300 : kin;
+  for (int c0 = 0; c0 < kin; c0 += cblk) {
+    const int w = kin - c0 < cblk ? kin - c0 : cblk;
+    d.x = x;
+    d.ldx = ldx;
+    if (kin > 304) {
+      // (the stack's own check: check_layer_dims refuses such a width before a3vt_gcn_layer_bwd gets here)
+      if (pad4(w) != w) { set_error("gcn_stack: in_features=%d needs a multiple of 4 past 300", kin); return -1; }
+      if (int rc = launch_copy_cols(x, ldx, c0, w, panel, (long long)d.m, s)) return rc;
+      d.x = panel;
+      d.ldx = w;
+    }
+    d.k_in = w;
+    {
+      ProfScope ps(PROF_DW, s, timed);
+      if (int rc = launch_dw(d, s)) return rc;
+    }
+    const size_t n = (size_t)w * d.n_out;
+    if (int rc = launch_slab_reduce_za(d.slab, dw_images(d), n, n, n, grad + (size_t)c0 * d.n_out, acc, s)) return rc;
+  }
+  return 0;
 }
 
 static int check_stack_dims(int ld_feats, int in_features, int num_layers, int hidden, int cut_len) {
@@ -321,15 +356,51 @@ static inline int pad8(int n) { return (n + 7) & ~7; }
 static inline int mask_ld16(int hidden, int cut_len) { return (pad8(cut_len) / 4 + (hidden + 3) / 4 + 1) & ~1; }
 
 constexpr int kStashInputLd = 608;   // pad8 of the widest stack input (check_stack16_dims: in_features <= 600)
+
+// The stash of a stack call: what the forward leaves in the caller's `acts` and `masks` buffers for the backward.  The size
+// queries, the forward and the backward of every mode take their offsets from here.
+//   acts   modes 0, 1, 3: fp32 rows [M][hidden] per hidden layer (row-major or hybrid: StackPlan).  Mode 2: bf16 rows
+//          [M][pad8(hidden)] per hidden layer, then the stack's INPUT rows in bf16 (the backward needs them for dW_0 and would
+//          otherwise convert the fp32 features a second time): addressed with row stride pad8(in_features), reserved for the
+//          widest input a stack accepts, + slack for 16-byte reads of the last row's tail.
+//   masks  row-major ReLU-sign bytes [pad32(M)][mld] per hidden layer; modes 0, 1, 3: behind ALL of them the sign bytes of the
+//          aggregated channels, quad-major [batch][pad4(cut_len) / 4][n_vert] per hidden layer (channel-sliced aggregation).
+struct StackStash {
+  size_t act_stride;           // a layer's rows in `acts`: floats, or bf16 elements in mode 2
+  size_t input16;              // mode 2: where the bf16 input rows start (bf16 elements)
+  int mld;                     // sign bytes per row (the kernels' mld argument)
+  size_t sign_stride;          // a layer's row-major sign bytes
+  size_t signq0, signq_stride; // the quad-major sign planes: start, bytes per layer
+  size_t acts_bytes, mask_bytes;
+  size_t act(int i) const { return (size_t)i * act_stride; }
+  size_t signs(int i) const { return (size_t)i * sign_stride; }
+  size_t signq(int i) const { return signq0 + (size_t)i * signq_stride; }
+};
+static StackStash stack_stash(int batch, int n_vert, int hidden, int num_layers, int cut_len, int gemm_mode) {
+  StackStash S{};
+  const bool s16 = gemm_mode == GEMM_BF16_STORAGE;
+  const size_t m = (size_t)batch * n_vert, mpad = (m + 31) / 32 * 32, nh = num_layers > 1 ? num_layers - 1 : 0;
+  S.act_stride = m * (s16 ? pad8(hidden) : hidden);
+  S.input16 = nh * S.act_stride;
+  S.mld = s16 ? mask_ld16(hidden, cut_len) : mask_ld(hidden, cut_len);
+  S.sign_stride = mpad * S.mld;
+  S.signq0 = nh * S.sign_stride;
+  S.signq_stride = s16 ? 0 : align_up(m * (size_t)(pad4(cut_len) / 4), 256);
+  S.acts_bytes = s16 ? (S.input16 + m * (size_t)kStashInputLd) * 2 + 256 : nh * S.act_stride * sizeof(float);
+  S.mask_bytes = nh * (S.sign_stride + S.signq_stride);
+  return S;
+}
 struct Stack16Layout {
   size_t wt, wt_stride;   // bf16 weight images (offsets / stride in floats)
   size_t feats16;         // [M][ld0] bf16: the stack's fp32 input features, converted
-  size_t za;              // [M][cpad] bf16
+  size_t za;              // [M][ldza] bf16
   size_t z3;              // [2][M][4] fp32
   size_t ping[2];         // [M][ldh] bf16 each
   size_t dw_slab, db_slab, thin_dw_slab, thin_db_slab, heavy, total;
+  size_t db_layer_stride; // db_slab: one block of bias-partial rows per hidden layer
   size_t tplan;           // the tiled aggregation's plan (csr16t_plan_ints)
   int ld0, ldh, cpad;
+  int ldza;               // row stride of za: cpad, at least one 8-column group
 };
 
 static Stack16Layout stack16_layout(int batch, int n_vert, int in_features, int hidden, int num_layers, int cut_len,
@@ -339,34 +410,30 @@ static Stack16Layout stack16_layout(int batch, int n_vert, int in_features, int 
   L.ld0 = pad8(in_features);
   L.ldh = pad8(hidden);
   L.cpad = pad8(cut_len);
-  size_t off = 0;
-  auto take = [&](size_t nfloats) {
-    const size_t o = off;
-    off = align_up(off + nfloats, 64);
-    return o;
-  };
-  auto take16 = [&](size_t nelems) { return take((nelems + 1) / 2 + 64); };  // bf16 region (+ slack for 16-byte tails)
+  L.ldza = L.cpad > 8 ? L.cpad : 8;
+  Arena a;
   // images: forward W_i^T [bt_rows(hidden)][2 pad16(k_i / 2)], backward W_i [bt_rows(n_store_i)][2 pad16(ldh / 2)]
   const int kmax = L.ld0 > L.ldh ? L.ld0 : L.ldh;
   const int rows_f = rowgemm_bt_rows(hidden), rows_b = rowgemm_bt_rows(kmax);
   const size_t img_f = (size_t)rows_f * pad16(kmax / 2), img_b = (size_t)rows_b * pad16(L.ldh / 2);
   L.wt_stride = align_up(img_f > img_b ? img_f : img_b, 64);
-  L.wt = take(L.wt_stride * (num_layers > 1 ? num_layers - 1 : 1));
-  L.feats16 = take16(m * L.ld0);
-  L.za = take16(m * (L.cpad > 8 ? L.cpad : 8));
-  L.z3 = take(2 * m * 4);
-  L.ping[0] = take16(m * L.ldh);
-  L.ping[1] = take16(m * L.ldh);
-  L.heavy = take(csr_heavy_scratch_ints(n_vert));
-  L.tplan = take(csr16t_plan_ints(n_vert));
+  L.wt = a.take(L.wt_stride * (num_layers > 1 ? num_layers - 1 : 1));
+  L.feats16 = a.take16(m * L.ld0);
+  L.za = a.take16(m * L.ldza);
+  L.z3 = a.take(2 * m * 4);
+  L.ping[0] = a.take16(m * L.ldh);
+  L.ping[1] = a.take16(m * L.ldh);
+  L.heavy = a.take(csr_heavy_scratch_ints(n_vert));
+  L.tplan = a.take(csr16t_plan_ints(n_vert));
   if (need_backward) {
     const size_t kin = in_features > hidden ? in_features : hidden;
-    L.dw_slab = take((size_t)dw16_num_slabs(hidden) * (kin > 304 ? 304 : kin) * hidden);
-    L.db_slab = take(align_up((size_t)csr_bwd_num_slabs(batch, n_vert) * (L.cpad > 8 ? L.cpad : 8), 64) * (num_layers > 1 ? num_layers - 1 : 1));
-    L.thin_dw_slab = take((size_t)thin_num_slabs() * hidden * 3);
-    L.thin_db_slab = take((size_t)thin_num_slabs() * 3);
+    L.dw_slab = a.take((size_t)dw16_num_slabs(hidden) * (kin > 304 ? 304 : kin) * hidden);
+    L.db_layer_stride = align_up((size_t)csr_bwd_num_slabs(batch, n_vert) * L.ldza, 64);
+    L.db_slab = a.take(L.db_layer_stride * (num_layers > 1 ? num_layers - 1 : 1));
+    L.thin_dw_slab = a.take((size_t)thin_num_slabs() * hidden * 3);
+    L.thin_db_slab = a.take((size_t)thin_num_slabs() * 3);
   }
-  L.total = off;
+  L.total = a.off;
   return L;
 }
 
@@ -390,9 +457,8 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
   const Stack16Layout L = stack16_layout(batch, n_vert, in_features, hidden, num_layers, cut_len, 0);
+  const StackStash S = stack_stash(batch, n_vert, hidden, num_layers, cut_len, GEMM_BF16_STORAGE);
   const size_t m = (size_t)batch * n_vert;
-  const int mld = mask_ld16(hidden, cut_len);
-  const size_t mpad = (m + 31) / 32 * 32;
   using u16 = unsigned short;
   int32_t *heavy;
   if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
@@ -400,7 +466,7 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
                                    scratch + L.wt, L.wt_stride, s))
     return rc;
   // the input rows in bf16: behind the hidden layers' rows in the stash when there is one (the backward reads them there)
-  u16 *f16 = acts ? static_cast<u16 *>(acts) + (size_t)(num_layers - 1) * m * L.ldh : reinterpret_cast<u16 *>(scratch + L.feats16);
+  u16 *f16 = acts ? static_cast<u16 *>(acts) + S.input16 : reinterpret_cast<u16 *>(scratch + L.feats16);
   if (int rc = launch_cvt_rows(feats, ld_feats, in_features, f16, L.ld0, (long long)m, s)) return rc;
   // bounded-degree graphs: the aggregation reads its neighbour rows from LDS tiles (gcn_bf16s.hip, csr16t); plan per call
   const bool tiled = heavy == nullptr && cut_len > 0 && g_csr_algo != 1 && csr16t_ok(n_vert, cut_len, max_degree, (long long)m);
@@ -412,7 +478,7 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
   int ldx = L.ld0;
   u16 *za = reinterpret_cast<u16 *>(scratch + L.za);
   for (int i = 0; i + 1 < num_layers; ++i) {
-    u16 *y = acts ? static_cast<u16 *>(acts) + (size_t)i * m * L.ldh : reinterpret_cast<u16 *>(scratch + L.ping[i & 1]);
+    u16 *y = acts ? static_cast<u16 *>(acts) + S.act(i) : reinterpret_cast<u16 *>(scratch + L.ping[i & 1]);
     RowGemmArgs g{};
     g.a0 = g.a1 = reinterpret_cast<const float *>(x);
     g.lda0 = g.lda1 = ldx / 2;
@@ -425,11 +491,11 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
     g.c = reinterpret_cast<float *>(y);
     g.ldc = L.ldh;
     g.c2 = reinterpret_cast<float *>(za);
-    g.ldc2 = L.cpad > 8 ? L.cpad : 8;
+    g.ldc2 = L.ldza;
     g.csplit = cut_len;
-    uint8_t *mk = masks ? masks + (size_t)i * mpad * mld : nullptr;
+    uint8_t *mk = masks ? masks + S.signs(i) : nullptr;
     g.maskb = mk;
-    g.mld = mld;
+    g.mld = S.mld;
     g.moff = L.cpad / 4;
     g.mode = GEMM_BF16_STORAGE;
     {
@@ -439,9 +505,9 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
     if (cut_len > 0) {
       ProfScope psa(PROF_AGG, s);
       if (tiled) {
-        if (int rc = launch_csr16t_fwd(za, g.ldc2, biases[i], cut_len, tplan, rowptr, col, val, n_vert, batch, y, L.ldh, mk, mld, 1, s))
+        if (int rc = launch_csr16t_fwd(za, g.ldc2, biases[i], cut_len, tplan, rowptr, col, val, n_vert, batch, y, L.ldh, mk, S.mld, 1, s))
           return rc;
-      } else if (int rc = launch_csr16_fwd(za, g.ldc2, biases[i], cut_len, rowptr, col, val, heavy, n_vert, batch, y, L.ldh, mk, mld, 1, s)) {
+      } else if (int rc = launch_csr16_fwd(za, g.ldc2, biases[i], cut_len, rowptr, col, val, heavy, n_vert, batch, y, L.ldh, mk, S.mld, 1, s)) {
         return rc;
       }
     }
@@ -465,16 +531,15 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
   const Stack16Layout L = stack16_layout(batch, n_vert, in_features, hidden, num_layers, cut_len, 1);
+  const StackStash S = stack_stash(batch, n_vert, hidden, num_layers, cut_len, GEMM_BF16_STORAGE);
   const size_t m = (size_t)batch * n_vert;
-  const int mld = mask_ld16(hidden, cut_len);
-  const size_t mpad = (m + 31) / 32 * 32;
   const int last = num_layers - 1;
   using u16 = unsigned short;
   const u16 *acts16 = static_cast<const u16 *>(acts);
   int32_t *heavyT;
   if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
-  // the stack's input in bf16: the forward left it behind the hidden layers' rows in the stash (a3vt_gcn_stack_stash_bytes)
-  const u16 *f16 = acts16 + (size_t)last * m * L.ldh;
+  // the stack's input in bf16: the forward left it behind the hidden layers' rows in the stash (StackStash)
+  const u16 *f16 = acts16 + S.input16;
   (void)feats;
   (void)ld_feats;
   // the tiled aggregation's plan for A^T (see stack_fwd16)
@@ -492,7 +557,7 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
     const SplitRef sref = split_ref(split);
     if (int rc = launch_csr3(du4, nullptr, rowptrT, colT, valT, heavyT, n_vert, batch, res, 4, s, split ? &sref : nullptr, true))
       return rc;
-    const u16 *x = acts16 + (size_t)(last - 1) * m * L.ldh;
+    const u16 *x = acts16 + S.act(last - 1);
     if (int rc = launch_thin16_bwd_main(x, L.ldh, hidden, weights[last], res, grad_update, (long long)m, 1, ping[0], L.ldh,
                                         scratch + L.thin_dw_slab, scratch + L.thin_db_slab, s))
       return rc;
@@ -505,22 +570,21 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
                                    L.wt_stride, s))
     return rc;
   u16 *dza = reinterpret_cast<u16 *>(scratch + L.za);
-  const int cpad = L.cpad, ldza = cpad > 8 ? cpad : 8;
-  const size_t db_layer_stride = align_up((size_t)csr_bwd_num_slabs(batch, n_vert) * (cpad > 8 ? cpad : 8), 64);
+  const int cpad = L.cpad, ldza = L.ldza;
   int cur = 0;
   for (int i = last - 1; i >= 0; --i) {
     u16 *g = ping[cur];
-    const u16 *x = i == 0 ? f16 : acts16 + (size_t)(i - 1) * m * L.ldh;
+    const u16 *x = i == 0 ? f16 : acts16 + S.act(i - 1);
     const int ldx = i == 0 ? L.ld0 : L.ldh;
     const int kin = i == 0 ? in_features : hidden;
     if (cut_len > 0) {
       ProfScope psa(PROF_AGG, s);
       if (tiled) {
         if (int rc = launch_csr16t_bwd(g, L.ldh, cut_len, cpad, tplan, rowptrT, colT, valT, n_vert, batch, dza, ldza,
-                                       scratch + L.db_slab + (size_t)i * db_layer_stride, s))
+                                       scratch + L.db_slab + (size_t)i * L.db_layer_stride, s))
           return rc;
       } else if (int rc = launch_csr16_bwd(g, L.ldh, cut_len, cpad, rowptrT, colT, valT, heavyT, n_vert, batch, dza, ldza,
-                                           scratch + L.db_slab + (size_t)i * db_layer_stride, s)) {
+                                           scratch + L.db_slab + (size_t)i * L.db_layer_stride, s)) {
         return rc;
       }
     } else if (!acc) {
@@ -574,8 +638,8 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
       r.n_store = hidden;
       r.c = reinterpret_cast<float *>(ping[cur ^ 1]);
       r.ldc = L.ldh;
-      r.maskb = const_cast<uint8_t *>(masks) + (size_t)(i - 1) * mpad * mld;
-      r.mld = mld;
+      r.maskb = const_cast<uint8_t *>(masks) + S.signs(i - 1);
+      r.mld = S.mld;
       r.moff = cpad / 4;
       r.csplit = cut_len;
       {
@@ -586,7 +650,7 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
     }
   }
   if (cut_len > 0)   // bias gradients of all hidden layers: one launch (as the fp32 stack)
-    if (int rc = reduce_bias_partials(scratch + L.db_slab, db_layer_stride, csr_bwd_num_slabs(batch, n_vert), cpad, cut_len, hidden,
+    if (int rc = reduce_bias_partials(scratch + L.db_slab, L.db_layer_stride, csr_bwd_num_slabs(batch, n_vert), cpad, cut_len, hidden,
                                       last, grad_biases, acc, s))
       return rc;
   return 0;
@@ -695,13 +759,10 @@ int a3vt_adj_split_validate(const int32_t *rowptr, const int32_t *col, const flo
   return rc;
 }
 
-// ReLU-sign bytes saved by the forward pass for the backward pass: [num_layers-1][pad32(M)][mld],
-// mld = pad4(cut_len)/4 + ceil(hidden/4).  (mask_ld: defined with stack_x3 above)
+// ReLU-sign bytes saved by the forward pass for the backward pass in modes 0, 1 and 3 (StackStash)
 size_t a3vt_gcn_stack_mask_bytes(int batch, int n_vert, int hidden, int num_layers, int cut_len) {
   if (num_layers < 2 || batch <= 0 || n_vert <= 0 || hidden <= 0 || cut_len < 0) return 0;
-  const size_t mpad = ((size_t)batch * n_vert + 31) / 32 * 32;
-  // row-major sign bytes, then the quad-major signs of the aggregated channels (channel-sliced aggregation)
-  return (size_t)(num_layers - 1) * (mpad * mask_ld(hidden, cut_len) + signq_stride((size_t)batch * n_vert, cut_len));
+  return stack_stash(batch, n_vert, hidden, num_layers, cut_len, GEMM_FP32).mask_bytes;
 }
 
 size_t a3vt_gcn_stack_scratch_bytes(int batch, int n_vert, int in_features, int hidden, int num_layers, int cut_len,
@@ -732,17 +793,9 @@ int a3vt_gcn_stack_stash_bytes(int batch, int n_vert, int hidden, int num_layers
   A3VT_CHECK_ARG(acts_bytes && mask_bytes && batch > 0 && n_vert > 0 && hidden > 0 && cut_len >= 0);
   *acts_bytes = *mask_bytes = 0;
   if (num_layers < 2) return 0;
-  const size_t m = (size_t)batch * n_vert, mpad = (m + 31) / 32 * 32;
-  if (gemm_bf16 == GEMM_BF16_STORAGE) {
-    // the hidden layers' bf16 rows, then the stack's INPUT rows in bf16 (the backward needs them for dW_0 and would otherwise
-    // convert the fp32 features a second time; sized for the widest input a stack accepts: in_features <= 600), + slack for
-    // 16-byte reads of the last row's tail
-    *acts_bytes = (size_t)(num_layers - 1) * m * pad8(hidden) * 2 + m * (size_t)kStashInputLd * 2 + 256;
-    *mask_bytes = (size_t)(num_layers - 1) * mpad * mask_ld16(hidden, cut_len);
-  } else {
-    *acts_bytes = (size_t)(num_layers - 1) * m * hidden * sizeof(float);
-    *mask_bytes = a3vt_gcn_stack_mask_bytes(batch, n_vert, hidden, num_layers, cut_len);
-  }
+  const StackStash S = stack_stash(batch, n_vert, hidden, num_layers, cut_len, gemm_bf16);
+  *acts_bytes = S.acts_bytes;
+  *mask_bytes = S.mask_bytes;
   return 0;
 }
 
@@ -774,10 +827,9 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
   const StackLayout L = stack_layout(batch, n_vert, in_features, hidden, num_layers, cut_len, 0, gemm_bf16);
+  const StackStash S = stack_stash(batch, n_vert, hidden, num_layers, cut_len, gemm_bf16);
   const size_t m = (size_t)batch * n_vert;
   const int cpad = pad4(cut_len);
-  const int mld = mask_ld(hidden, cut_len);
-  const size_t mpad = (m + 31) / 32 * 32;
 
   int32_t *heavy;
   if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
@@ -803,7 +855,7 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
   for (int i = 0; i + 1 < num_layers; ++i) {
     const int k = i == 0 ? ld_feats : hidden;       // K walked by the kernel (pad columns of feats are zero)
     const bool l3 = P.x3 && i > 0;   // this layer's product on the split-operand kernel
-    float *y = acts ? acts + (size_t)i * m * hidden : scratch + L.ping[i & 1];
+    float *y = acts ? acts + S.act(i) : scratch + L.ping[i & 1];
     RowGemmArgs g{};
     g.a0 = g.a1 = x;
     g.lda0 = g.lda1 = ldx;
@@ -823,11 +875,11 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
     g.c = y + rm_off - qcols;
     g.ldc = rm_ld;
     g.c2 = scratch + L.za;
-    g.ldc2 = cpad;
+    g.ldc2 = cpad;   // (not L.ldza: 0 without aggregated channels, nothing goes to c2 then)
     g.csplit = cut_len;
-    uint8_t *mk = masks ? masks + (size_t)i * mpad * mld : nullptr;
+    uint8_t *mk = masks ? masks + S.signs(i) : nullptr;
     g.maskb = mk;
-    g.mld = mld;
+    g.mld = S.mld;
     g.moff = cpad / 4;
     g.mode = l3 ? GEMM_FP32X3 : P.omode;
     if (P.quad) {   // raw columns [0, cpad) leave the product quad-major, for the channel-sliced aggregation;
@@ -842,7 +894,7 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
       if (int rc = launch_rowgemm(g, EPI_FWD_HIDDEN, s)) return rc;
     }
     if (P.quad) {
-      uint8_t *sq = masks ? masks + (size_t)(num_layers - 1) * mpad * mld + (size_t)i * signq_stride(m, cut_len) : nullptr;
+      uint8_t *sq = masks ? masks + S.signq(i) : nullptr;
       ProfScope psa(PROF_AGG, s);
       if (P.qsplit) {
         if (int rc = launch_csrqs_fwd(scratch + L.za, biases[i], cut_len, ell, n_vert, batch, y, qcols / 4, sq, 1, s)) return rc;
@@ -852,7 +904,7 @@ int a3vt_gcn_stack_fwd_adj(const float *feats, int ld_feats, int in_features, co
       xq = y;
     } else if (cut_len > 0) {
       ProfScope psa(PROF_AGG, s);
-      if (int rc = launch_csr_fwd(scratch + L.za, cpad, biases[i], cut_len, rowptr, col, val, heavy, n_vert, batch, y, hidden, mk, mld, 1, s))
+      if (int rc = launch_csr_fwd(scratch + L.za, L.ldza, biases[i], cut_len, rowptr, col, val, heavy, n_vert, batch, y, hidden, mk, S.mld, 1, s))
         return rc;
     }
     x = y + rm_off - qcols;
@@ -914,10 +966,9 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
   const StackLayout L = stack_layout(batch, n_vert, in_features, hidden, num_layers, cut_len, 1, gemm_bf16);
+  const StackStash S = stack_stash(batch, n_vert, hidden, num_layers, cut_len, gemm_bf16);
   const size_t m = (size_t)batch * n_vert;
   const int cpad = pad4(cut_len);
-  const int mld = mask_ld(hidden, cut_len);
-  const size_t mpad = (m + 31) / 32 * 32;
   const int last = num_layers - 1;
 
   const SplitRef sref = split_ref(split);
@@ -933,7 +984,7 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
   if (int rc = launch_stack_ell(P, split, rowptrT, colT, valT, n_vert, ellT, s)) return rc;
   // ---- output layer
   {
-    const float *xl = num_layers == 1 ? feats : acts + (size_t)(last - 1) * m * hidden;
+    const float *xl = num_layers == 1 ? feats : acts + S.act(last - 1);
     const float *x = xl + rm_off - qcols;                 // hybrid rows: see a3vt_gcn_stack_fwd (qcols = 0: plain rows)
     const int ldx = num_layers == 1 ? ld_feats : rm_ld;
     const int k = num_layers == 1 ? in_features : hidden;
@@ -961,13 +1012,12 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
     return rc;
 
   // ---- hidden layers, last to first.  g = dL/dY_i already multiplied by the ReLU mask of layer i.
-  const int db_rows = quad ? batch : csr_bwd_num_slabs(batch, n_vert);
-  const size_t db_layer_stride = align_up((size_t)(csr_bwd_num_slabs(batch, n_vert) > batch ? csr_bwd_num_slabs(batch, n_vert) : batch) * cpad, 64);
+  const int db_rows = quad ? batch : csr_bwd_num_slabs(batch, n_vert);   // partial rows per layer (L.db_layer_stride holds either)
   int cur = 0;
   for (int i = last - 1; i >= 0; --i) {
     float *g = scratch + L.ping[cur];
     float *dza = scratch + L.za;
-    const float *xl = i == 0 ? feats : acts + (size_t)(i - 1) * m * hidden;
+    const float *xl = i == 0 ? feats : acts + S.act(i - 1);
     const bool xhyb = quad && i > 0;                  // X_i = output of layer i-1: hybrid rows on the channel-sliced path
     const float *x = xhyb ? xl + rm_off - qcols : xl;
     const int ldx = i == 0 ? ld_feats : (xhyb ? rm_ld : hidden);
@@ -975,86 +1025,63 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
 
     // bias gradient + A^T gather on the aggregated channels
     if (cut_len > 0 && quad) {
-      const uint8_t *sq = masks + (size_t)(num_layers - 1) * mpad * mld + (size_t)i * signq_stride(m, cut_len);
+      const uint8_t *sq = masks + S.signq(i);
       ProfScope psa(PROF_AGG, s);
       // the (mesh, channel) partials of this layer: summed over the meshes by ONE launch for all layers behind the loop
       if (P.qsplit) {
         if (int rc = launch_csrqs_bwd(scratch + L.gq, cut_len, ellT, n_vert, batch, dza, sq,
-                                      scratch + L.db_slab + (size_t)i * db_layer_stride, s))
+                                      scratch + L.db_slab + (size_t)i * L.db_layer_stride, s))
           return rc;
       } else if (int rc = launch_csrq_bwd(scratch + L.gq, cut_len, rowptrT, colT, valT, heavyT, ellT, n_vert, batch, dza, sq,
-                                          scratch + L.db_slab + (size_t)i * db_layer_stride, s)) {
+                                          scratch + L.db_slab + (size_t)i * L.db_layer_stride, s)) {
         return rc;
       }
     } else if (cut_len > 0) {
       ProfScope psa(PROF_AGG, s);
-      if (int rc = launch_csr_bwd(g, hidden, cut_len, rowptrT, colT, valT, heavyT, n_vert, batch, dza, cpad,
-                                  scratch + L.db_slab + (size_t)i * db_layer_stride, s))
+      if (int rc = launch_csr_bwd(g, hidden, cut_len, rowptrT, colT, valT, heavyT, n_vert, batch, dza, L.ldza,
+                                  scratch + L.db_slab + (size_t)i * L.db_layer_stride, s))
         return rc;
       // (channels >= cut_len are dead bias parameters (model.py:358): written as exact zeros by the reduce behind the loop)
     } else if (!acc) {
       if (int rc = launch_fill_zero(grad_biases[i], hidden, s)) return rc;
     }
 
-    // dW_i = X_i^T dZ.  The kernel covers up to 304 input channels per pass; wider inputs (the 448-wide image
-    // model's first layer) go in column blocks of <= 300, each first copied into a contiguous panel (StackLayout::panel).
-    // Up to 304 channels are ONE pass: only the panels start at column c0 (a second pass over 301..304 channels would read
-    // X from column 0).
-    const int cblk = kin > 304 ? 300 : kin;
-    for (int c0 = 0; c0 < kin; c0 += cblk) {
-      const int w = kin - c0 < cblk ? kin - c0 : cblk;
-      const float *xs = x;
-      int ldxs = ldx;
-      if (kin > 304) {
-        float *panel = scratch + L.panel;
-        const int wp = pad4(w);
-        if (wp != w) { set_error("gcn_stack: in_features=%d needs a multiple of 4 past 300", kin); return -1; }
-        if (int rc = launch_copy_cols(x, ldx, c0, w, panel, (long long)m, s)) return rc;
-        xs = panel;
-        ldxs = w;
-      }
-      DwArgs d{};
-      d.x = xs;
-      d.ldx = ldxs;
-      if (xhyb) {   // (kin = hidden <= 304 here: no panels) staged image [16][hidden], sources: quad-major + row-major parts
-        d.ldx = hidden;
-        d.ldx_src = rm_ld;
-        d.xq = xl;
-        d.xq_nvert = n_vert;
-        d.xq_quads = qcols / 4;
-      }
-      if (quad) {
-        d.z0q_nvert = n_vert;
-        d.z0q_quads = cpad / 4;
-      }
-      d.z0 = dza;
-      d.ldz0 = cpad > 0 ? cpad : 4;
-      d.z1 = g;
-      d.ldz1 = hidden;
-      d.zsplit = cpad;
-      d.zeros = zeros;
-      d.slab = scratch + L.dw_slab;
-      d.m = (int)m;
-      d.k_in = w;
-      d.n_out = hidden;
-      d.mode = P.omode;
-      if (P.x3 && i > 0) {   // hidden layer of a mode-3 stack: the split-operand kernel when it takes the shape
-        d.mode = GEMM_FP32X3;
-        if (!dw3_ok(d)) d.mode = P.omode;
-      }
-      {
-        ProfScope ps(PROF_DW, s);
-        if (int rc = launch_dw(d, s)) return rc;
-      }
-      if (int rc = launch_slab_reduce_za(scratch + L.dw_slab, dw_images(d), (size_t)w * hidden, (size_t)w * hidden,
-                                         (size_t)w * hidden, grad_weights[i] + (size_t)c0 * hidden, acc, s))
-        return rc;
+    // dW_i = X_i^T dZ
+    DwArgs d{};
+    if (xhyb) {   // staged image [16][hidden], sources: quad-major + row-major parts
+      d.ldx_src = rm_ld;
+      d.xq = xl;
+      d.xq_nvert = n_vert;
+      d.xq_quads = qcols / 4;
     }
+    if (quad) {
+      d.z0q_nvert = n_vert;
+      d.z0q_quads = cpad / 4;
+    }
+    d.z0 = dza;
+    d.ldz0 = L.ldza;
+    d.z1 = g;
+    d.ldz1 = hidden;
+    d.zsplit = cpad;
+    d.zeros = zeros;
+    d.slab = scratch + L.dw_slab;
+    d.m = (int)m;
+    d.n_out = hidden;
+    d.mode = P.omode;
+    const int ldxw = xhyb ? hidden : ldx;   // width of the rows the kernel stages
+    if (P.x3 && i > 0) {   // hidden layer of a mode-3 stack: the split-operand kernel when it takes the shape (one pass of kin columns)
+      d.mode = GEMM_FP32X3;
+      d.x = x;
+      d.ldx = ldxw;
+      d.k_in = kin;
+      if (!dw3_ok(d)) d.mode = P.omode;
+    }
+    if (int rc = dw_panels(d, x, ldxw, kin, scratch + L.panel, grad_weights[i], acc, true, s)) return rc;
 
     // dX_i = dZ W_i^T  (masked by the ReLU of layer i-1, whose output is X_i)
     RowGemmArgs r{};
     r.a0 = dza;
-    r.lda0 = cpad > 0 ? cpad : 4;
+    r.lda0 = L.ldza;
     if (quad) {   // dZa is quad-major (csrq_kernel<1>)
       r.a0q_nvert = n_vert;
       r.a0q_quads = cpad / 4;
@@ -1077,8 +1104,8 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
       r.c = scratch + L.ping[cur ^ 1];
       r.ldc = hidden;
       // X_i is the output of layer i-1: its ReLU signs were saved by that layer's forward launches
-      r.maskb = const_cast<uint8_t *>(masks) + (size_t)(i - 1) * mpad * mld;
-      r.mld = mld;
+      r.maskb = const_cast<uint8_t *>(masks) + S.signs(i - 1);
+      r.mld = S.mld;
       r.moff = cpad / 4;
       r.csplit = cut_len;
       if (quad) {   // gradient columns [0, cpad) go quad-major (unmasked below cut_len) to the next aggregation
@@ -1097,7 +1124,7 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
   // bias gradients of all hidden layers from their partial rows (one per mesh on the channel-sliced path, one per row-walk
   // workgroup otherwise): one launch instead of one per layer (19 x 3.8-5.5 us per stack call)
   if (cut_len > 0)
-    if (int rc = reduce_bias_partials(scratch + L.db_slab, db_layer_stride, db_rows, cpad, cut_len, hidden, last, grad_biases, acc, s))
+    if (int rc = reduce_bias_partials(scratch + L.db_slab, L.db_layer_stride, db_rows, cpad, cut_len, hidden, last, grad_biases, acc, s))
       return rc;
   return 0;
 }
@@ -1106,31 +1133,28 @@ int a3vt_gcn_stack_bwd_adj(const float *feats, int ld_feats, int in_features, co
 namespace {
 struct LayerLayout {
   size_t wt, za, ga, dz, panel, dw_slab, db_slab, heavy, total;
+  int ldza;   // row stride of za: cpad, or 4 (dummy rows) without aggregated channels
 };
 LayerLayout layer_layout(int batch, int n_vert, int ld_x, int n_out, int cut_len, int need_backward) {
   LayerLayout L{};
   const size_t m = (size_t)batch * n_vert;
   const int cpad = pad4(cut_len), npad = pad4(n_out);
-  size_t off = 0;
-  auto take = [&](size_t nfloats) {
-    const size_t o = off;
-    off = align_up(off + nfloats, 64);
-    return o;
-  };
+  L.ldza = cpad > 4 ? cpad : 4;
+  Arena a;
   const size_t wt_fwd = (size_t)rowgemm_bt_rows(n_out) * pad16(ld_x);
   const size_t wt_bwd = (size_t)rowgemm_bt_rows(ld_x) * pad16(npad);
-  L.wt = take(wt_fwd > wt_bwd ? wt_fwd : wt_bwd);
-  L.za = take(m * (cpad > 4 ? cpad : 4));  // forward: raw Z of the aggregated channels; backward: 4-float dummy rows
-  L.heavy = take(csr_heavy_scratch_ints(n_vert));
+  L.wt = a.take(wt_fwd > wt_bwd ? wt_fwd : wt_bwd);
+  L.za = a.take(m * L.ldza);  // forward: raw Z of the aggregated channels; backward: 4-float dummy rows
+  L.heavy = a.take(csr_heavy_scratch_ints(n_vert));
   if (need_backward) {
-    L.ga = take(m * (cpad > 4 ? cpad : 4));
-    L.dz = take(m * npad);
-    L.panel = take(ld_x > 304 ? m * 300 : 0);
+    L.ga = a.take(m * L.ldza);
+    L.dz = a.take(m * npad);
+    L.panel = a.take(ld_x > 304 ? m * 300 : 0);
     const int kin = ld_x > 304 ? 300 : ld_x;
-    L.dw_slab = take((size_t)dw_num_slabs(n_out) * kin * n_out);
-    L.db_slab = take((size_t)csr_bwd_num_slabs(batch, n_vert) * (cpad > 4 ? cpad : 4));
+    L.dw_slab = a.take((size_t)dw_num_slabs(n_out) * kin * n_out);
+    L.db_slab = a.take((size_t)csr_bwd_num_slabs(batch, n_vert) * L.ldza);
   }
-  L.total = off;
+  L.total = a.off;
   return L;
 }
 int check_layer_dims(int ld_x, int in_features, int n_out, int cut_len) {
@@ -1147,6 +1171,29 @@ int check_layer_dims(int ld_x, int in_features, int n_out, int cut_len) {
     return -1;
   }
   return 0;
+}
+// What a3vt_gcn_layer_* and a3vt_qnet_input_* share: a single layer behind its product, and its backward up to dZ.
+// Forward: y[:, :c] = act(A za[:, :c] + bias) on the aggregated channels (heavy_slot: the layout's hub-row region)
+int layer_fwd_tail(const float *za, int ldza, const float *bias, int cut_len, int relu, const int32_t *rowptr, const int32_t *col,
+                   const float *val, int max_degree, int n_vert, int batch, float *y, int ld_y, float *heavy_slot, hipStream_t s) {
+  if (cut_len <= 0) return 0;
+  int32_t *heavy;
+  if (int rc = hub_rows(rowptr, n_vert, max_degree, heavy_slot, &heavy, s)) return rc;
+  return launch_csr_fwd(za, ldza, bias, cut_len, rowptr, col, val, heavy, n_vert, batch, y, ld_y, nullptr, 0, relu, s);
+}
+// Backward: the gradient through the activation, aggregated columns to `ga`, the rest straight into the merged dZ rows `dz`
+// [M][pad4(n_out)]; then dZ[:, :c] = A^T G[:, :c] (columns c..cpad pass through), bias gradient = column sums of G[:, :c]
+int layer_bwd_tail(const float *grad_y, int ld_gy, const float *y, int ld_y, int relu, int n_out, int cut_len,
+                   const int32_t *rowptrT, const int32_t *colT, const float *valT, int max_degreeT, int n_vert, int batch, float *ga,
+                   float *dz, float *db_slab, float *heavy_slot, float *grad_bias, hipStream_t s) {
+  const int cpad = pad4(cut_len), npad = pad4(n_out);
+  if (int rc = launch_relu_split(grad_y, ld_gy, y, ld_y, relu, n_out, cpad, npad, (long long)batch * n_vert, ga, dz, s)) return rc;
+  if (int rc = launch_fill_zero(grad_bias, n_out, s)) return rc;
+  if (cut_len <= 0) return 0;
+  int32_t *heavyT;
+  if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, heavy_slot, &heavyT, s)) return rc;
+  if (int rc = launch_csr_bwd(ga, cpad, cut_len, rowptrT, colT, valT, heavyT, n_vert, batch, dz, npad, db_slab, s)) return rc;
+  return launch_slab_reduce(db_slab, csr_bwd_num_slabs(batch, n_vert), cpad, cut_len, grad_bias, s);
 }
 }  // namespace
 
@@ -1166,7 +1213,6 @@ int a3vt_gcn_layer_fwd(const float *x, int ld_x, int in_features, const float *w
   A3VT_CHECK_ARG(zeros != nullptr);
   const LayerLayout L = layer_layout(batch, n_vert, ld_x, out_features, cut_len, 0);
   const size_t m = (size_t)batch * n_vert;
-  const int cpad = pad4(cut_len);
   float *wt = scratch + L.wt;
   if (int rc = launch_transpose_pad(weight, in_features, out_features, wt, rowgemm_bt_rows(out_features), pad16(ld_x), s))
     return rc;
@@ -1183,19 +1229,13 @@ int a3vt_gcn_layer_fwd(const float *x, int ld_x, int in_features, const float *w
   g.c = y;
   g.ldc = ld_y;
   g.c2 = scratch + L.za;
-  g.ldc2 = cpad > 4 ? cpad : 4;
+  g.ldc2 = L.ldza;
   g.csplit = cut_len;
   g.no_relu = relu ? 0 : 1;
   g.mode = gemm_bf16 == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;   // (mode 3 is a stack mode: a lone layer runs exact)
   if (int rc = launch_rowgemm(g, EPI_FWD_HIDDEN, s)) return rc;
-  if (cut_len > 0) {
-    int32_t *heavy;
-    if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
-    if (int rc = launch_csr_fwd(scratch + L.za, g.ldc2, bias, cut_len, rowptr, col, val, heavy, n_vert, batch, y, ld_y,
-                                nullptr, 0, relu ? 1 : 0, s))
-      return rc;
-  }
-  return 0;
+  return layer_fwd_tail(scratch + L.za, L.ldza, bias, cut_len, relu ? 1 : 0, rowptr, col, val, max_degree, n_vert, batch, y, ld_y,
+                        scratch + L.heavy, s);
 }
 
 int a3vt_gcn_layer_bwd(const float *x, int ld_x, int in_features, const float *weight, int out_features, int cut_len,
@@ -1210,54 +1250,24 @@ int a3vt_gcn_layer_bwd(const float *x, int ld_x, int in_features, const float *w
   A3VT_CHECK_ARG(zeros != nullptr);
   const LayerLayout L = layer_layout(batch, n_vert, ld_x, out_features, cut_len, 1);
   const size_t m = (size_t)batch * n_vert;
-  const int cpad = pad4(cut_len), npad = pad4(out_features);
-  float *ga = scratch + L.ga, *dz = scratch + L.dz;
-
-  // gradient through the activation; aggregated columns to `ga`, the rest straight into the merged dZ rows
-  if (int rc = launch_relu_split(grad_y, ld_gy, y, ld_y, relu ? 1 : 0, out_features, cpad, npad, (long long)m, ga, dz, s))
+  const int npad = pad4(out_features);
+  float *dz = scratch + L.dz;
+  if (int rc = layer_bwd_tail(grad_y, ld_gy, y, ld_y, relu ? 1 : 0, out_features, cut_len, rowptrT, colT, valT, max_degreeT, n_vert,
+                              batch, scratch + L.ga, dz, scratch + L.db_slab, scratch + L.heavy, grad_bias, s))
     return rc;
-  if (int rc = launch_fill_zero(grad_bias, out_features, s)) return rc;
-  if (cut_len > 0) {
-    // dZ[:, :c] = A^T G[:, :c] (columns c..cpad pass through), bias gradient = column sums of G[:, :c]
-    int32_t *heavyT;
-    if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
-    if (int rc = launch_csr_bwd(ga, cpad, cut_len, rowptrT, colT, valT, heavyT, n_vert, batch, dz, npad,
-                                scratch + L.db_slab, s))
-      return rc;
-    if (int rc = launch_slab_reduce(scratch + L.db_slab, csr_bwd_num_slabs(batch, n_vert), cpad, cut_len, grad_bias, s))
-      return rc;
-  }
-  // dW = X^T dZ, in column panels of <= 300 input channels when the input is wider than the kernel covers
-  for (int c0 = 0; c0 < in_features; c0 += 300) {
-    const int w = in_features > 304 ? (in_features - c0 < 300 ? in_features - c0 : 300) : in_features;
-    const float *xs = x;
-    int ldxs = ld_x;
-    if (in_features > 304) {
-      float *panel = scratch + L.panel;
-      if (int rc = launch_copy_cols(x, ld_x, c0, w, panel, (long long)m, s)) return rc;
-      xs = panel;
-      ldxs = w;
-    }
-    DwArgs d{};
-    d.x = xs;
-    d.ldx = ldxs;
-    d.z0 = scratch + L.za;  // zsplit = 0: never consumed, only staged
-    d.ldz0 = 4;
-    d.z1 = dz;
-    d.ldz1 = npad;
-    d.zsplit = 0;
-    d.zeros = zeros;
-    d.slab = scratch + L.dw_slab;
-    d.m = (int)m;
-    d.k_in = w;
-    d.n_out = out_features;
-    d.mode = gemm_bf16 == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;
-    if (int rc = launch_dw(d, s)) return rc;
-    if (int rc = launch_slab_reduce(scratch + L.dw_slab, dw_num_slabs(out_features), (size_t)w * out_features,
-                                    (size_t)w * out_features, grad_weight + (size_t)c0 * out_features, s))
-      return rc;
-    if (in_features <= 304) break;
-  }
+  // dW = X^T dZ
+  DwArgs d{};
+  d.z0 = scratch + L.za;  // zsplit = 0: never consumed, only staged
+  d.ldz0 = 4;
+  d.z1 = dz;
+  d.ldz1 = npad;
+  d.zsplit = 0;
+  d.zeros = zeros;
+  d.slab = scratch + L.dw_slab;
+  d.m = (int)m;
+  d.n_out = out_features;
+  d.mode = gemm_bf16 == GEMM_BF16_OPERANDS ? GEMM_BF16_OPERANDS : GEMM_FP32;
+  if (int rc = dw_panels(d, x, ld_x, in_features, scratch + L.panel, grad_weight, 0, false, s)) return rc;
   // dX = dZ W^T
   float *wp = scratch + L.wt;
   if (int rc = launch_copy_pad(weight, in_features, out_features, wp, rowgemm_bt_rows(ld_x), pad16(npad), s)) return rc;
@@ -1300,26 +1310,23 @@ int a3vt_ddqn_td_bwd(const float *diff, const float *actions, const float *grad_
 namespace {
 struct QnetLayout {
   size_t za, heavy, ga, dz, db_slab, slab, total;
+  int ldza;   // as LayerLayout's
 };
 QnetLayout qnet_layout(int batch, int n_vert, int hidden, int cut_len, int backward) {
   QnetLayout L{};
   const size_t m = (size_t)batch * n_vert;
-  const int cw = pad4(cut_len) > 4 ? pad4(cut_len) : 4, npad = pad4(hidden);
-  size_t off = 0;
-  auto take = [&](size_t nfloats) {
-    const size_t o = off;
-    off = align_up(off + nfloats, 64);
-    return o;
-  };
-  L.za = take(m * cw);
-  L.heavy = take(csr_heavy_scratch_ints(n_vert));
+  const int npad = pad4(hidden);
+  L.ldza = pad4(cut_len) > 4 ? pad4(cut_len) : 4;
+  Arena a;
+  L.za = a.take(m * L.ldza);
+  L.heavy = a.take(csr_heavy_scratch_ints(n_vert));
   if (backward) {
-    L.ga = take(m * cw);
-    L.dz = take(m * npad);
-    L.db_slab = take((size_t)csr_bwd_num_slabs(batch, n_vert) * cw);
-    L.slab = take((size_t)qnet_bwd_wgs(batch, n_vert) * qnet_slab_floats(hidden));
+    L.ga = a.take(m * L.ldza);
+    L.dz = a.take(m * npad);
+    L.db_slab = a.take((size_t)csr_bwd_num_slabs(batch, n_vert) * L.ldza);
+    L.slab = a.take((size_t)qnet_bwd_wgs(batch, n_vert) * qnet_slab_floats(hidden));
   }
-  L.total = off;
+  L.total = a.off;
   return L;
 }
 int check_qnet_dims(int hidden, int cut_len, int n_vert, int batch) {
@@ -1357,18 +1364,12 @@ int a3vt_qnet_input_fwd(const float *mesh, const float *w1, const float *b1, con
   a.comp_s = comp_s; a.comp_t = comp_t; a.comp_c = comp_c;
   a.batch = batch; a.n_vert = n_vert; a.hidden = hidden; a.cut_len = cut_len;
   a.za = scratch + L.za;
-  a.ldza = pad4(cut_len) > 4 ? pad4(cut_len) : 4;
+  a.ldza = L.ldza;
   a.y = y;
   a.ldy = ld_y;
   path_count(PATH_QNET_FWD);
   if (int rc = launch_qnet_fwd(a, s)) return rc;
-  if (cut_len > 0) {   // the rest of the layer, as a3vt_gcn_layer_fwd finishes one
-    int32_t *heavy;
-    if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
-    if (int rc = launch_csr_fwd(a.za, a.ldza, bias, cut_len, rowptr, col, val, heavy, n_vert, batch, y, ld_y, nullptr, 0, 1, s))
-      return rc;
-  }
-  return 0;
+  return layer_fwd_tail(a.za, a.ldza, bias, cut_len, 1, rowptr, col, val, max_degree, n_vert, batch, y, ld_y, scratch + L.heavy, s);
 }
 
 int a3vt_qnet_input_bwd(const float *mesh, const float *w1, const float *b1, const float *w2, const float *b2, const float *comp_c,
@@ -1382,20 +1383,11 @@ int a3vt_qnet_input_bwd(const float *mesh, const float *w1, const float *b1, con
   A3VT_CHECK_ARG(al16(mesh) && al16(comp_c) && al16(scratch));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const QnetLayout L = qnet_layout(batch, n_vert, hidden, cut_len, 1);
-  const size_t m = (size_t)batch * n_vert;
-  const int cpad = pad4(cut_len), npad = pad4(hidden);
-  float *ga = scratch + L.ga, *dz = scratch + L.dz;
+  float *dz = scratch + L.dz;
   path_count(PATH_QNET_BWD);
-  // the layer's own backward up to dZ, as a3vt_gcn_layer_bwd: activation mask, then A^T on the aggregated columns + bias gradient
-  if (int rc = launch_relu_split(grad_y, ld_gy, y, ld_y, 1, hidden, cpad, npad, (long long)m, ga, dz, s)) return rc;
-  if (int rc = launch_fill_zero(grad_bias, hidden, s)) return rc;
-  if (cut_len > 0) {
-    int32_t *heavyT;
-    if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
-    if (int rc = launch_csr_bwd(ga, cpad, cut_len, rowptrT, colT, valT, heavyT, n_vert, batch, dz, npad, scratch + L.db_slab, s))
-      return rc;
-    if (int rc = launch_slab_reduce(scratch + L.db_slab, csr_bwd_num_slabs(batch, n_vert), cpad, cut_len, grad_bias, s)) return rc;
-  }
+  if (int rc = layer_bwd_tail(grad_y, ld_gy, y, ld_y, 1, hidden, cut_len, rowptrT, colT, valT, max_degreeT, n_vert, batch,
+                              scratch + L.ga, dz, scratch + L.db_slab, scratch + L.heavy, grad_bias, s))
+    return rc;
   QnetArgs a{};
   a.mesh = mesh;
   a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;

@@ -33,7 +33,6 @@ constexpr int kQsPairs = 6;              // 12 edge slots per vertex
 constexpr int kQsWaves = kQsThreads / 64;
 
 int csrqs_max_degree() { return 2 * kQsPairs; }
-size_t csrqs_image_ints(int n_vert) { return (size_t)n_vert * (kQsPairs + 2) + 64; }
 bool csrqs_fits(int n_vert, int cut_len) {
   // two slices of one mesh in LDS, 16-bit byte offsets of the rows (the row of zeros included), <= 6 vertices per thread
   return cut_len > 0 && pad4(cut_len) <= 128 && n_vert <= 6 * kQsThreads && ((size_t)n_vert + 1) * 16 <= 65535 &&

@@ -616,18 +616,23 @@ static int launch_rowgemm_cols(const RowGemmArgs &a, hipStream_t s) {
 // tiles in pairs; M = 163,968 rows = 10,248 tiles would leave almost every SIMD idle while a few run a sixth
 // tile pair (+20 % time).  When such a small remainder exists, the tiles that fill whole rounds go to the main
 // launch and the leftover rows run in its tail (rowtile_unit): one 16 x 16 tile per wave, operands from registers.
+// rowgemm_main_rows: the rows of the main launch for m rows of nt column tiles (m itself: no tail).  launch_rowgemm_epi
+// splits by it, and rowgemm_quad_major_ok below judges the main launch it gives: the stack plan relies on one answer.
+static int rowgemm_main_rows(int m, int nt) {
+  const int tiles = cdiv(m, 16), full = tiles / 2048 * 2048, rem = tiles - full;
+  return full == 0 || rem == 0 || rem * nt > 1024 || nt < 2 ? m : full * 16;
+}
 template <int EPI>
 static int launch_rowgemm_epi(const RowGemmArgs &a0, hipStream_t s) {
   RowGemmArgs a = a0;
   a.bt_rows = rowgemm_bt_rows(a.n_store);
   a.col0 = 0;
-  const int tiles = cdiv(a.m, 16), nt = cdiv(a.n_store, 16);
-  const int full = tiles / 2048 * 2048, rem = tiles - full;
-  if (full == 0 || rem == 0 || rem * nt > 1024 || nt < 2) return launch_rowgemm_cols<EPI>(a, s);
+  const int main_m = rowgemm_main_rows(a.m, cdiv(a.n_store, 16));
+  if (main_m == a.m) return launch_rowgemm_cols<EPI>(a, s);
   RowGemmArgs m = a;
-  m.m = full * 16;
-  m.rem_row0 = full * 16;
-  m.rem_rows = a.m - full * 16;
+  m.m = main_m;
+  m.rem_row0 = main_m;
+  m.rem_rows = a.m - main_m;
   return launch_rowgemm_cols<EPI>(m, s);
 }
 
@@ -642,9 +647,7 @@ int rowgemm_bt_rows(int n_store) {
 bool rowgemm_quad_major_ok(int m, int n_store, int cpad) {
   const int nt = cdiv(n_store, 16);
   if (nt < 14 || nt > 19 || cpad <= 0 || cpad > 160 || cpad % 4 != 0) return false;   // NT = 19, first column group = 160 columns
-  const int tiles = cdiv(m, 16), full = tiles / 2048 * 2048, rem = tiles - full;     // as launch_rowgemm_epi
-  const int main_m = (full == 0 || rem == 0 || rem * nt > 1024) ? m : full * 16;
-  return cdiv(cdiv(main_m, 16), 8) >= 96;                                             // as launch_rowgemm_cols: no column blocks
+  return cdiv(cdiv(rowgemm_main_rows(m, nt), 16), 8) >= 96;                           // as launch_rowgemm_cols: no column blocks
 }
 
 int launch_rowgemm(const RowGemmArgs &a, int epi, hipStream_t s) {
@@ -1398,9 +1401,6 @@ int launch_slab_reduce_za(const float *slab, int nslab, size_t stride, size_t n,
                 accumulate);
   A3VT_CHECK_LAUNCH();
   return 0;
-}
-int launch_slab_reduce_z(const float *slab, int nslab, size_t stride, size_t n, size_t n_out, float *out, hipStream_t s) {
-  return launch_slab_reduce_za(slab, nslab, stride, n, n_out, out, 0, s);
 }
 int launch_slab_reduce(const float *slab, int nslab, size_t stride, size_t n, float *out, hipStream_t s) {
   return launch_slab_reduce_za(slab, nslab, stride, n, n, out, 0, s);

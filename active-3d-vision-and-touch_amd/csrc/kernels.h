@@ -148,9 +148,7 @@ int dww_images();   // slab images a dww launch writes (>= dw_num_slabs(300): si
 int launch_dww(const DwArgs &a, hipStream_t s);
 int launch_copy_cols(const float *src, int ld_src, int c0, int w, float *dst, long long m, hipStream_t s);
 int launch_slab_reduce(const float *slab, int nslab, size_t stride, size_t n, float *out, hipStream_t s);
-// same, and out[n .. n_out) = 0
-int launch_slab_reduce_z(const float *slab, int nslab, size_t stride, size_t n, size_t n_out, float *out, hipStream_t s);
-// same; accumulate != 0: out += the sum (the sum is formed first, in the same fixed order, then added once)
+// same, and out[n .. n_out) = 0; accumulate != 0: out += the sum (the sum is formed first, in the same fixed order, then added once)
 int launch_slab_reduce_za(const float *slab, int nslab, size_t stride, size_t n, size_t n_out, float *out, int accumulate,
                           hipStream_t s);
 
@@ -194,10 +192,9 @@ struct SplitRef {
   const uint8_t *cls;
 };
 // The same for structured adjacencies D^-1 (P + J), J = a complete bipartite block (gcn_csrqs.hip, a3vt_adj_split): `img` =
-// the index image launch_csrqs_image builds from the split (csrqs_image_ints(n_vert) ints); same layouts as csrq.
+// the index image launch_csrqs_image builds from the split (8 ints per vertex: it fits csrq_ell_ints(n_vert)); same layouts as csrq.
 bool csrqs_fits(int n_vert, int cut_len);
 int csrqs_max_degree();   // longest row of P the kernel takes
-size_t csrqs_image_ints(int n_vert);
 int launch_csrqs_image(const int32_t *rowptr, const int32_t *col, const float *scale, const uint8_t *cls, int n_vert,
                        int32_t *img, hipStream_t s);
 int launch_csrqs_fwd(const float *zq, const float *bias, int c, const int32_t *img, int n_vert, int batch, float *yq,

@@ -84,6 +84,38 @@ def test_size_queries_never_fail_on_odd_sizes(L):
     L.a3vt_chamfer_workspace_bytes(0, 0, 0, 0)
 
 
+def test_size_queries_agree_with_each_other(L):
+    """Relations between the size queries of the GCN entry points, over every 13th shape of the grid below (13 is coprime to
+    every axis length, so each value of each axis is visited; 222 shapes).  Nothing is allocated and no device is touched."""
+    import itertools
+    grid = itertools.product((1, 2, 13, 64), (162, 1824, 2562), (3, 50, 300, 448, 600), (16, 64, 300, 304), (1, 2, 3, 20), (0, 1, 2))
+    ab, mb = ctypes.c_size_t(), ctypes.c_size_t()
+    shapes = 0
+    for b, n, fin, h, nl, ci in itertools.islice(grid, 0, None, 13):
+        c = (0, round(0.33 * h), h)[ci]
+        shapes += 1
+        what = (b, n, fin, h, nl, c)
+        by_mode = [[L.a3vt_gcn_stack_scratch_bytes_mode(b, n, fin, h, nl, c, back, mode) for mode in range(4)] for back in (0, 1)]
+        for back in (0, 1):
+            modes = [m for m in range(4) if m != 2 or nl >= 2]          # the bf16 storage mode needs a hidden layer
+            assert L.a3vt_gcn_stack_scratch_bytes(b, n, fin, h, nl, c, back) == max(by_mode[back][m] for m in modes) > 0, what
+        assert all(by_mode[1][m] >= by_mode[0][m] for m in range(4)), what
+        assert L.a3vt_gcn_stack_scratch_bytes(b, n, fin, h, nl, c, 1) >= L.a3vt_gcn_stack_scratch_bytes(b, n, fin, h, nl, c, 0), what
+        for mode in range(4):
+            assert L.a3vt_gcn_stack_stash_bytes(b, n, h, nl, c, mode, ctypes.byref(ab), ctypes.byref(mb)) == 0, what
+            if nl == 1:
+                assert (ab.value, mb.value) == (0, 0), what
+            elif mode != 2:
+                assert mb.value == L.a3vt_gcn_stack_mask_bytes(b, n, h, nl, c), what
+                assert ab.value == (nl - 1) * b * n * h * 4, what
+        if nl == 1:
+            assert L.a3vt_gcn_stack_mask_bytes(b, n, h, nl, c) == 0, what
+        ld = (fin + 3) // 4 * 4
+        assert L.a3vt_gcn_layer_scratch_bytes(b, n, ld, h, c, 1) > L.a3vt_gcn_layer_scratch_bytes(b, n, ld, h, c, 0) > 0, what
+        assert L.a3vt_qnet_input_scratch_bytes(b, n, h, c, 1) > L.a3vt_qnet_input_scratch_bytes(b, n, h, c, 0) > 0, what
+    assert shapes == 222
+
+
 def test_entry_points_refuse_bad_arguments_before_touching_them(L):
     f32 = ctypes.c_float
     # BatchNorm + ReLU: fewer than two rows, misaligned maps, one running statistic without the other, short scratch

@@ -7,7 +7,7 @@ The checks are TEACHER-FORCED: every layer is recomputed from the activations th
 compound up a bf16 stack from the layers below.  Then the bounds can be tight enough to see one wrong row or column group:
 a dropped 8-row block of a 33 306-row dW reduction moves dW by ~1.5 %, far above them.
 
-Stash layout (csrc/capi.hip, stack_fwd16 / a3vt_gcn_stack_stash_bytes): mode 2 — hidden layer i as [M][pad8(hidden)] bf16
+Stash layout (csrc/capi.hip, StackStash / stack_stash; stated here independently): mode 2 — hidden layer i as [M][pad8(hidden)] bf16
 at element i * M * pad8(hidden), the stack's input converted to bf16 behind them as [M][pad8(in_features)]; mode 1 — hidden
 layer i as [M][hidden] fp32 at float i * M * hidden (never hybrid rows: the channel-sliced path is fp32-only).
 """
