@@ -1771,6 +1771,31 @@ int a3vt_conv5_weight_grad(const void *x, const void *grad_out, int batch, int h
   return launch_conv5_wrw(x, grad_out, batch, height, width, cin, cout, stride, grad_weight, scratch, static_cast<hipStream_t>(stream));
 }
 
+int a3vt_conv5f_supported(int cin, int cout, int stride) { return conv5f_shape_ok(cin, cout, stride) ? 1 : 0; }
+
+size_t a3vt_conv5f_image_bytes(int cin, int cout) { return conv5f_weight_image_bytes(cin, cout); }
+
+int a3vt_conv5f_weight_image(const float *weight, int cout, int cin, void *image, void *stream) {
+  A3VT_CHECK_ARG(weight && image);
+  A3VT_CHECK_ARG(conv5f_weight_image_bytes(cin, cout) != 0);
+  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(weight) & 3) == 0 && (reinterpret_cast<uintptr_t>(image) & 15) == 0);
+  return launch_conv5f_weight_image(weight, cout, cin, image, static_cast<hipStream_t>(stream));
+}
+
+int a3vt_conv5f_nhwc(const float *x, int batch, int height, int width, int cin, int cout, int stride, int pad, const void *image,
+                     const float *scale, const float *shift, int relu, float *y, void *stream) {
+  A3VT_CHECK_ARG(x && image && y);
+  A3VT_CHECK_ARG(conv5f_shape_ok(cin, cout, stride));
+  A3VT_CHECK_ARG(batch >= 1 && height >= 1 && width >= 1 && pad >= 0 && pad <= 4 && (relu == 0 || relu == 1));
+  A3VT_CHECK_ARG(height + 2 * pad >= 5 && width + 2 * pad >= 5);          // (an empty output otherwise)
+  A3VT_CHECK_ARG((long long)batch * height * width <= (1ll << 31) / 32);
+  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & (cin == 3 ? 3 : 15)) == 0);
+  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(image)) & 15) == 0);
+  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 3) == 0);
+  ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
+  return launch_conv5f(x, batch, height, width, cin, cout, stride, pad, image, scale, shift, relu, y, static_cast<hipStream_t>(stream));
+}
+
 int a3vt_adam_chunk_elems(void) { return adam_chunk_elems(); }
 
 int a3vt_adam_step(void *const *param, const void *const *grad, void *const *exp_avg, void *const *exp_avg_sq,

@@ -338,6 +338,14 @@ struct CastBatch {
 };
 int launch_cast_weights(const CastBatch &b, hipStream_t s);
 
+// conv5f.hip: fp32 5 x 5 convolutions of the touch predictor's stem on channels-last fp32 maps (scale / shift / ReLU epilogue),
+// (cin, cout, stride) in {(3,16,2), (16,16,1), (16,32,2), (32,32,1), (32,32,2)}; forward only
+bool conv5f_shape_ok(int cin, int cout, int stride);
+size_t conv5f_weight_image_bytes(int cin, int cout);
+int launch_conv5f_weight_image(const float *w, int cout, int cin, void *image, hipStream_t s);
+int launch_conv5f(const float *x, int batch, int h, int w, int cin, int cout, int stride, int pad, const void *image, const float *scale,
+                  const float *shift, int relu, float *y, hipStream_t s);
+
 // conv5.hip: 5 x 5 convolutions of the image pyramid on channels-last bf16 maps, (cin, cout, stride) in {(16,16,1), (32,32,1),
 // (16,32,2)}; with flip = 1 / pad = 3 (stride 1 only) the input gradient
 bool conv5_shape_ok(int cin, int cout, int stride);

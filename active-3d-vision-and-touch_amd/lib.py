@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT_LIB: another build of the library (tools/asan_host.sh)
-SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
+SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "conv5f.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
            "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip"]
 # Per-file extra flags (none at present; sample.hip / gcn_csr.hip rely on IEEE NaN semantics — the reference's NaN
 # scrubs, a3vt_check_finite — so fast-math style flags must never be applied globally).
@@ -78,6 +78,10 @@ SIGNATURES = {
     "a3vt_conv5_input_grad_3x16s2": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "a3vt_conv5_wrw_scratch_bytes": (_sz, [_i, _i]),
     "a3vt_conv5_weight_grad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "a3vt_conv5f_supported": (_i, [_i, _i, _i]),
+    "a3vt_conv5f_image_bytes": (_sz, [_i, _i]),
+    "a3vt_conv5f_weight_image": (_i, [_vp, _i, _i, _vp, _vp]),
+    "a3vt_conv5f_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "a3vt_adam_chunk_elems": (_i, []),
     "a3vt_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                        ctypes.c_longlong, _vp]),

@@ -584,6 +584,76 @@ def conv5_supported(weight, stride, padding):
     return bool(_lib.load().a3vt_conv5_supported(int(weight.shape[1]), int(weight.shape[0]), int(stride[0])))
 
 
+_CONV5F_FOLDS = {}   # id(conv.weight) -> (weakref, signature of every tensor read, optimizer epoch, image, scale, shift); as _BF16_COPIES
+
+
+def bn_fold(conv_bias, bn):
+    """Eval-mode ``BatchNorm2d`` after a convolution as the per-channel map ``y = scale * conv_without_bias(x) + shift``:
+    ``scale = gamma / sqrt(running_var + eps)``, ``shift = beta + scale * (conv_bias - running_mean)``.  Plain tensor
+    arithmetic in the dtype of the module's tensors (any device)."""
+    scale = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
+    mean = bn.running_mean if conv_bias is None else bn.running_mean - conv_bias.detach()
+    return scale, bn.bias.detach() - scale * mean
+
+
+def _conv5f_operands(conv, bn):
+    """(weight image, scale, shift) of ``a3vt_conv5f_nhwc`` for a convolution and the eval-mode BatchNorm that follows it
+    (``bn`` None: scale NULL, shift = the bias), cached until one of the tensors can have changed — the rules of
+    :func:`_bf16_copy`: ``_version`` and ``data_ptr`` of every tensor read, and the process-wide optimizer epoch."""
+    L = _lib.load()
+    on = _bf16_cache_on()
+    w = conv.weight
+    read = [w, conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+    sig = tuple((id(t), t._version, t.data_ptr()) for t in read if t is not None) + ((bn.eps,) if bn is not None else ())
+    key = id(w)
+    hit = _CONV5F_FOLDS.get(key) if on else None
+    if hit is not None and hit[0]() is w and hit[1] == sig and hit[2] == _OPT_EPOCH[0]:
+        return hit[3], hit[4], hit[5]
+    wd = _req(w.detach(), "conv weight")
+    cout, cin = int(wd.shape[0]), int(wd.shape[1])
+    img = torch.empty(L.a3vt_conv5f_image_bytes(cin, cout), dtype=torch.uint8, device=wd.device)
+    _lib.check(L.a3vt_conv5f_weight_image(_lib.ptr(wd), cout, cin, _lib.ptr(img), _stream()), "conv5f_weight_image")
+    if bn is not None:
+        scale, shift = bn_fold(conv.bias, bn)
+        scale, shift = _req(scale, "folded scale"), _req(shift, "folded shift")
+    else:
+        scale, shift = None, (None if conv.bias is None else _req(conv.bias.detach(), "conv bias"))
+    if on:
+        ref = weakref.ref(w, lambda r, key=key: _CONV5F_FOLDS.pop(key, None))
+        _CONV5F_FOLDS[key] = (ref, sig, _OPT_EPOCH[0], img, scale, shift)
+    return img, scale, shift
+
+
+def conv5f_supported(conv):
+    w = conv.weight
+    return (tuple(w.shape[2:]) == (5, 5) and conv.stride[0] == conv.stride[1] and conv.padding[0] == conv.padding[1]
+            and isinstance(conv.padding[0], int) and 0 <= conv.padding[0] <= 4 and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and bool(_lib.load().a3vt_conv5f_supported(int(w.shape[1]), int(w.shape[0]), int(conv.stride[0]))))
+
+
+def conv5f(x_nhwc, conv, bn=None, relu=False):
+    """``relu(bn(conv(x)))`` of an fp32 5 x 5 ``nn.Conv2d`` (+ an eval-mode ``nn.BatchNorm2d`` or None) on a channels-last
+    ``(B,H,W,cin)`` tensor -> ``(B,Ho,Wo,cout)``: ``a3vt_conv5f_nhwc`` (csrc/conv5f.hip), exact fp32 on the matrix pipe with the
+    BatchNorm folded into the epilogue.  Forward only: the result carries no autograd graph.  A shape the kernel does not take
+    is an error, not a detour."""
+    L = _lib.load()
+    if bn is not None and (bn.training or not bn.track_running_stats):
+        raise RuntimeError("a3vt: conv5f folds an eval-mode BatchNorm (running statistics); this one is in training mode")
+    if not conv5f_supported(conv):
+        raise RuntimeError(f"a3vt: conv5f does not take {conv}")
+    x = _req(x_nhwc.detach(), "x")
+    B, H, W, C = x.shape
+    cout, stride, pad = int(conv.weight.shape[0]), int(conv.stride[0]), int(conv.padding[0])
+    if C != conv.weight.shape[1]:
+        raise RuntimeError(f"a3vt: conv5f: the map has {C} channels, the convolution takes {conv.weight.shape[1]}")
+    img, scale, shift = _conv5f_operands(conv, bn)
+    y = torch.empty((B, (H + 2 * pad - 5) // stride + 1, (W + 2 * pad - 5) // stride + 1, cout), dtype=torch.float32, device=x.device)
+    _lib.check(L.a3vt_conv5f_nhwc(_lib.ptr(x), B, H, W, C, cout, stride, pad, _lib.ptr(img), _lib.ptr(scale), _lib.ptr(shift),
+                                  int(bool(relu)), _lib.ptr(y), _stream()), "conv5f_nhwc")
+    STATS["conv5f"] = STATS.get("conv5f", 0) + 1
+    return y
+
+
 LIBRARY_CONV5 = [True]   # layers 2-6 of the bf16 image branch on a3vt_conv5_nhwc (False: MIOpen, for A/B)
 LIBRARY_CONV5_WRW = [True]   # their weight gradients on a3vt_conv5_weight_grad (False: MIOpen's split-K kernel + fill + cast)
 _CONV5_WRW_SCRATCH = {}   # (device index, stream) -> scratch of a3vt_conv5_weight_grad (per-workgroup partial images)

@@ -22,6 +22,36 @@ def stack_charts(charts_list):
     return {key: torch.cat([c[key] for c in charts_list], dim=0) for key in charts_list[0]}
 
 
+def touch_slots(encoder, touch, ref_frame, status, template):
+    """The touch charts and masks of a batch of sensor readings — what ``ActiveTouch.get_inputs`` (``policies/environment.py:
+    294-353``) does with the touch model's predictions, for any leading shape at once (environments x fingers, or candidates x
+    environments x fingers: one ``Encoder`` forward for all of them).
+
+    encoder    : ``reconstruction.touch.model.Encoder`` (run under ``no_grad``)
+    touch      : (..., 3, 121, 121) tactile images in [0, 1]
+    ref_frame  : {"rot": (..., 3, 3), "pos": (..., 3)} finger frames
+    status     : nested lists / array of strings with the leading shape: "touch", "no_touch" or anything else (no contact made)
+    template   : (25, 3) chart template
+    returns    : charts (..., 25, 3), masks (..., 25, 1): "touch" -> the predicted chart, mask 2; "no_touch" -> the chart collapsed
+                 to the finger's position, mask 1; otherwise zeros, mask 0 — the ``touch_charts`` / ``touch_masks`` slots of
+                 ``prepare_mesh`` / ``score_actions``' chart dicts."""
+    import numpy as np
+    lead = tuple(touch.shape[:-3])
+    dev = touch.device
+    status = np.asarray(status, dtype=object).reshape(lead)
+    code = torch.from_numpy(np.where(status == "touch", 2, np.where(status == "no_touch", 1, 0)).astype(np.float32)).to(dev)
+    n = int(code.numel())
+    pos = ref_frame["pos"].to(dev).reshape(n, 3)
+    ref = {"rot": ref_frame["rot"].to(dev).reshape(n, 3, 3), "pos": pos}
+    verts = template.to(dev).view(1, -1, 3).repeat(n, 1, 1)
+    with torch.no_grad():
+        pred = encoder(touch.reshape(n, *touch.shape[-3:]), ref, verts)
+    code = code.view(n, 1, 1)
+    charts = torch.where(code == 2, pred, torch.where(code == 1, pos.view(n, 1, 3).expand_as(pred), torch.zeros_like(pred)))
+    masks = code.expand(n, verts.shape[1], 1)
+    return charts.reshape(*lead, verts.shape[1], 3).contiguous(), masks.reshape(*lead, verts.shape[1], 1).contiguous()
+
+
 def score_actions(deform, img, charts_list, gt_points, faces, number_points, loss_coeff, repeat=3, samples=None):
     """Scores of K candidate touch configurations for E environment elements.
 

@@ -1,4 +1,4 @@
-"""``pterotactyl.utility.data_loaders`` — the vision-trainer dataset and its wire formats.
+"""``pterotactyl.utility.data_loaders`` — the trainers' datasets and their wire formats.
 
 ``mesh_loader_vision`` (reference ``utility/data_loaders.py:132-258``) reads the on-disk layout the reference's
 ``download_data.sh`` / ``data_making`` scripts produce and yields the batch dict the trainer and ``prepare_mesh`` consume:
@@ -13,6 +13,7 @@
 
 The data root is a directory argument (``args.data_root``, or the ``PTEROTACTYL_DATA`` environment variable) instead of
 the reference's package-relative constants (:18-29) — the dataset is a download, not part of either tree.
+``mesh_loader_touch`` (reference :47-127) is the touch trainer's dataset: see the class.
 ``DevicePrefetcher`` is the host->HBM leg: pinned staging buffers and a copy stream one batch ahead of the compute
 stream, so a 65 ms GPU step is not stalled by the 7.7 MB (no image) / 58 MB (image) batch upload.
 """
@@ -115,6 +116,74 @@ class mesh_loader_vision(object):
         for key in ("gt_points", "img", "touch_charts"):
             out[key] = torch.stack([item[key] for item in batch])
         return out
+
+
+class mesh_loader_touch(object):
+    """The touch-trainer dataset (reference ``utility/data_loaders.py:47-127``): one item per successful touch,
+
+        <root>/grasp_info/<id>/<grasp>/<finger>_touch.npy       (121, 121, 3) uint8-valued tactile image
+        <root>/grasp_info/<id>/<grasp>/<finger>_points.npy      (n, 3) points of the surface the sensor saw
+        <root>/grasp_info/<id>/<grasp>/<finger>_ref_frame.npy   pickled dict: rot (3, 3), pos (3,) of the finger
+
+    for the objects of the split's ``set_type`` that also have an image and a point cloud.
+
+        batch = {"names": [(id, grasp, finger)], "samples": (B,num_samples,3) f32, "sim_touch": (B,3,121,121) f32 in [0,1],
+                 "ref": {"rot": (B,3,3), "pos": (B,3)}}"""
+
+    def __init__(self, args, set_type="train"):
+        self.args = args
+        self.set_type = set_type
+        root = data_root(args)
+        self.grasp_dir = os.path.join(root, "grasp_info")
+        point_dir, image_dir = os.path.join(root, "point_cloud_info"), os.path.join(root, "images_colourful")
+        names = [os.path.splitext(os.path.basename(f))[0] for f in glob(os.path.join(image_dir, "*.npy"))]
+        limit = getattr(args, "limit_data", False)
+        if limit:
+            random.shuffle(names)
+            names = names[:3000]
+        wanted = set(load_split(args)[set_type])
+        self.object_names = []
+        for n in names:
+            if n in wanted and os.path.exists(os.path.join(point_dir, n + ".npy")) and os.path.exists(os.path.join(self.grasp_dir, n)):
+                touches = glob(os.path.join(self.grasp_dir, n, "*", "*_touch.npy"))
+                if limit:
+                    random.shuffle(touches)
+                    touches = touches[:7]
+                for touch in touches:
+                    grasp = os.path.basename(os.path.dirname(touch))
+                    finger = os.path.basename(touch).split("_")[0]
+                    self.object_names.append([n, grasp, finger])
+        print(f"The number of {set_type} set objects found : {len(self.object_names)}")
+
+    def __len__(self):
+        return len(self.object_names)
+
+    def standerdize_point_size(self, points):
+        """``num_samples`` of the points in random order; a shorter file is repeated four-fold until it is long enough."""
+        np.random.shuffle(points)
+        points = torch.FloatTensor(points)
+        while points.shape[0] < self.args.num_samples:
+            points = torch.cat((points, points, points, points))
+        return points[torch.randperm(points.shape[0])[: self.args.num_samples]]
+
+    def get_finger_transforms(self, obj, grasp, finger):
+        frame = np.load(os.path.join(self.grasp_dir, obj, str(grasp), f"{finger}_ref_frame.npy"), allow_pickle=True).item()
+        return torch.FloatTensor(frame["rot"]), torch.FloatTensor(frame["pos"])
+
+    def __getitem__(self, index):
+        obj, grasp, finger = self.object_names[index]
+        rot, pos = self.get_finger_transforms(obj, grasp, finger)
+        touch = np.load(os.path.join(self.grasp_dir, obj, grasp, f"{finger}_touch.npy"))
+        points = np.load(os.path.join(self.grasp_dir, obj, grasp, f"{finger}_points.npy"))
+        return {"names": (obj, grasp, finger), "rot": rot, "pos": pos,
+                "sim_touch": torch.FloatTensor(touch).permute(2, 0, 1).contiguous().view(3, 121, 121) / 255.0,
+                "samples": self.standerdize_point_size(points)}
+
+    def collate(self, batch):
+        return {"names": [item["names"] for item in batch],
+                "samples": torch.stack([item["samples"] for item in batch]),
+                "sim_touch": torch.stack([item["sim_touch"] for item in batch]),
+                "ref": {"rot": torch.stack([item["rot"] for item in batch]), "pos": torch.stack([item["pos"] for item in batch])}}
 
 
 class DevicePrefetcher:

@@ -44,6 +44,25 @@ def touch_charts(batch, args, seed=0):
     return torch.from_numpy(t)
 
 
+def touch_batch(batch, num_samples, seed=0):
+    """A batch in the wire format of ``mesh_loader_touch.collate`` without a dataset: seeded random tactile images in
+    [0, 1] (multiples of 1/255, as the loader produces), orthonormal ``rot`` (proper rotations), ``pos`` in the objects'
+    0.3 cube, and ``samples`` scattered (sigma 2 mm) around points of the chart template moved into each finger's frame."""
+    from . import mesh as amesh
+    g = torch.Generator().manual_seed(seed)
+    img = torch.randint(0, 256, (batch, 3, 121, 121), generator=g).float() / 255.0
+    q, r = torch.linalg.qr(torch.randn(batch, 3, 3, generator=g))
+    q = q * torch.sign(torch.diagonal(r, dim1=1, dim2=2)).unsqueeze(1)
+    q[:, :, 0] *= torch.linalg.det(q).unsqueeze(-1)
+    pos = (torch.rand(batch, 3, generator=g) - 0.5) * 0.3
+    tv = torch.from_numpy(amesh.load_asset("touch_chart")[0]).float()
+    pick = torch.randint(0, tv.shape[0], (batch, num_samples), generator=g)
+    local = tv[pick] + 0.002 * torch.randn(batch, num_samples, 3, generator=g)
+    samples = torch.bmm(q, local.permute(0, 2, 1)).permute(0, 2, 1) + pos.view(batch, 1, 3)
+    return {"names": [(f"synthetic_{seed}_{i}", "0", "0") for i in range(batch)], "samples": samples.contiguous(),
+            "sim_touch": img, "ref": {"rot": q.contiguous(), "pos": pos}}
+
+
 class SyntheticLoader:
     """Iterable of `steps` identical-shape batches (fresh clouds per step, deterministic in `seed`)."""
 

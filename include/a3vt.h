@@ -339,6 +339,24 @@ size_t a3vt_conv5_wrw_scratch_bytes(int cin, int cout);
 int a3vt_conv5_weight_grad(const void *x, const void *grad_out, int batch, int height, int width, int cin, int cout, int stride,
                            float *grad_weight, void *scratch, size_t scratch_bytes, void *stream);
 
+/* The fp32 5 x 5 convolutions of the touch chart predictor's stem (`DoubleConv` blocks 1-3 of `Encoder`, reconstruction/touch/
+ * model.py:10-47) on channels-last fp32 maps, with the per-channel affine map of an eval-mode BatchNorm and the ReLU in the epilogue:
+ *   y[b][oy][ox][co] = act(scale[co] * (sum over (ky, kx, ci) of x[b][oy stride + ky - pad][ox stride + kx - pad][ci] * W[co][ci][ky][kx]) + shift[co])
+ * (pixels outside the map are zeros; act = max(., 0) with relu = 1, the identity with relu = 0; scale / shift: fp32 [cout], NULL = 1 / 0).
+ * x: [batch][height][width][cin] fp32, y: [batch][Ho][Wo][cout] fp32, Ho = (height + 2 pad - 5) / stride + 1, pad in 0 .. 4.
+ * Shapes taken (a3vt_conv5f_supported): (cin, cout, stride) = (3, 16, 2), (16, 16, 1), (16, 32, 2), (32, 32, 1), (32, 32, 2).
+ * Exact fp32 on the matrix pipe (v_mfma_f32_16x16x4_f32: a chain of fused multiply-adds); every output element is ONE chain over
+ * (tap, channel) in a fixed order, so a result depends neither on the batch around it nor on the launch: repeatable bit for bit.
+ * `image` (a3vt_conv5f_image_bytes(cin, cout) bytes; 0 for channel counts not taken) is written by a3vt_conv5f_weight_image from the
+ * fp32 weight [cout][cin][5][5] (OIHW).  image and y 16-byte aligned; x 16-byte aligned for 16 / 32 channels, 4-byte for 3.  No
+ * allocation, no host synchronisation; invalid arguments (NULL pointers, a shape not taken, batch < 1, pad outside 0 .. 4, an empty
+ * output) return < 0 before anything is launched.  Forward only. */
+int a3vt_conv5f_supported(int cin, int cout, int stride);
+size_t a3vt_conv5f_image_bytes(int cin, int cout);
+int a3vt_conv5f_weight_image(const float *weight, int cout, int cin, void *image, void *stream);
+int a3vt_conv5f_nhwc(const float *x, int batch, int height, int width, int cin, int cout, int stride, int pad, const void *image,
+                     const float *scale, const float *shift, int relu, float *y, void *stream);
+
 /* The optimizer step of the trainer, `optim.Adam(params, lr, weight_decay=0)` + `optimizer.step()` (vision/train.py:64,148), over ALL
  * parameter tensors in one launch — torch's Adam (amsgrad off, maximize off) in its own order of operations per element:
  *   g' = g + weight_decay p;  m += (g' - m)(1 - beta1);  v = v beta2 + ((1 - beta2) g') g';
