@@ -12,14 +12,13 @@
 // HBM-bound: 16 bytes read and 12 written per parameter.  torch's fused multi-tensor kernel takes 7 launches of 104 us for the 47 M
 // parameters of the image model (1.8 TB/s); here the tensors are cut into chunks of 4096 elements once, when the optimizer is
 // built (a table of {tensor, offset} in device memory), and one grid of workgroups walks the chunk list with 16-byte accesses.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int kAdamChunk = 4096;      // elements per chunk: 256 threads x 4 pieces of 16 bytes
 constexpr int kAdamMaxWgs = 2048;
 

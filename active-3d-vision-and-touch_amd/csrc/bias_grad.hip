@@ -10,8 +10,8 @@
 // stride S (in elements, 8*S) is a multiple of C, so each of its eight accumulators stays on ONE channel for the
 // whole walk; the workgroup folds its 2048 accumulators into C partial sums in a fixed order (no atomics: the
 // result does not depend on scheduling), and the per-workgroup rows are summed by slab_reduce.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
@@ -20,8 +20,6 @@ namespace {
 constexpr int kBgThreads = 256;
 constexpr int kBgMaxWgs = 1024;
 
-__device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 template <bool BF16>
 __device__ __forceinline__ void load_piece(const void *g, long long piece, long long n_elem, float v[8]) {
@@ -41,7 +39,7 @@ __device__ __forceinline__ void load_piece(const void *g, long long piece, long 
     for (int j = 0; j < 8; ++j) {
       float x = 0.f;
       if (e0 + j < n_elem)
-        x = BF16 ? bf16_lo(static_cast<const uint16_t *>(g)[e0 + j]) : static_cast<const float *>(g)[e0 + j];
+        x = BF16 ? bf16_to_f32(static_cast<const uint16_t *>(g)[e0 + j]) : static_cast<const float *>(g)[e0 + j];
       v[j] = x;
     }
   }

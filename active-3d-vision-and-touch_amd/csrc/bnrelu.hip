@@ -15,8 +15,8 @@
 // two launches each way: the device-scope fences that needs — an L2 write-back per workgroup on this multi-die part — cost
 // 30 us per launch on the 32 MB maps, against 5 us for the extra launch.)
 // The ReLU mask of the backward pass is recomputed from x with the forward's own fma and coefficients (bit-identical to y > 0).
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
@@ -24,14 +24,6 @@ namespace {
 
 constexpr int kBnThreads = 256;
 constexpr int kBnMaxWgs = 1024;
-
-__device__ __forceinline__ float bn_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bn_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ uint32_t bn_pack(float a, float b) {   // two floats -> two bf16, round to nearest even
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){a, b}, b2));
-}
 
 __device__ __forceinline__ float bn_relu(float r) { return (r > 0.f || r != r) ? r : 0.f; }   // NaN stays NaN (torch.relu)
 
@@ -43,21 +35,21 @@ __device__ __forceinline__ void bn_load(const uint16_t *g, long long p, long lon
     for (int j = 0; j < 8; ++j) v[j] = 0.f;
   } else if (e0 + 8 <= n_elem) {
     const uint4 u = *reinterpret_cast<const uint4 *>(g + e0);
-    v[0] = bn_lo(u.x); v[1] = bn_hi(u.x); v[2] = bn_lo(u.y); v[3] = bn_hi(u.y);
-    v[4] = bn_lo(u.z); v[5] = bn_hi(u.z); v[6] = bn_lo(u.w); v[7] = bn_hi(u.w);
+    v[0] = bf16_lo(u.x); v[1] = bf16_hi(u.x); v[2] = bf16_lo(u.y); v[3] = bf16_hi(u.y);
+    v[4] = bf16_lo(u.z); v[5] = bf16_hi(u.z); v[6] = bf16_lo(u.w); v[7] = bf16_hi(u.w);
   } else {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = e0 + j < n_elem ? bn_lo(g[e0 + j]) : 0.f;
+    for (int j = 0; j < 8; ++j) v[j] = e0 + j < n_elem ? bf16_to_f32(g[e0 + j]) : 0.f;
   }
 }
 __device__ __forceinline__ void bn_store(uint16_t *g, long long p, long long n_elem, const float v[8]) {
   const long long e0 = p * 8;
   if (e0 + 8 <= n_elem) {
-    *reinterpret_cast<uint4 *>(g + e0) = make_uint4(bn_pack(v[0], v[1]), bn_pack(v[2], v[3]), bn_pack(v[4], v[5]), bn_pack(v[6], v[7]));
+    *reinterpret_cast<uint4 *>(g + e0) = make_uint4(bf16_pack2(v[0], v[1]), bf16_pack2(v[2], v[3]), bf16_pack2(v[4], v[5]), bf16_pack2(v[6], v[7]));
   } else {
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      if (e0 + j < n_elem) g[e0 + j] = (uint16_t)(bn_pack(v[j], 0.f) & 0xffffu);   // (nothing for pieces past the end)
+      if (e0 + j < n_elem) g[e0 + j] = bf16_round(v[j]);   // (nothing for pieces past the end)
   }
 }
 
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(kBnThreads) void bnrelu_stats_kernel(BnFwd p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       acc[0][j] = acc[1][j] = 0.f;
-      pv[j] = bn_lo(p.x[ch]);
+      pv[j] = bf16_to_f32(p.x[ch]);
       ch = ch + 1 == p.c ? 0 : ch + 1;
     }
   }
@@ -245,7 +237,7 @@ __global__ __launch_bounds__(kBnThreads) void bnrelu_stats_final_kernel(BnFwd p,
       }
       const double m = (double)p.rows;
       const double md = s / m;                                              // mean of x - pivot (row 0's value)
-      const double mean = (double)bn_lo(p.x[c0 + ch]) + md;
+      const double mean = (double)bf16_to_f32(p.x[c0 + ch]) + md;
       double var = ss / m - md * md;
       var = var > 0.0 ? var : 0.0;
       const float meanf = (float)mean, varf = (float)var;
@@ -423,7 +415,7 @@ __global__ __launch_bounds__(kBnThreads) void bnrelu_bwd_dx_kernel(BnBwd p) {
         const long long e0 = (q + u * stride) * 8;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          if (e0 + j < p.n_elem) acc[0][j] += bn_lo(bn_pack(v[u][j], 0.f));   // the value as stored
+          if (e0 + j < p.n_elem) acc[0][j] += bf16_lo(bf16_pack2(v[u][j], 0.f));   // the value as stored
       }
     }
   }
@@ -478,7 +470,7 @@ __global__ __launch_bounds__(256) void cast_weights_kernel(CastBatch b) {
   const int rem = (int)(r - o * inner * hw);
   const int p = rem / inner, i = rem - p * inner;          // destination order: [o][p][i]
   const float v = b.src[lo][(o * inner + i) * hw + p];
-  b.dst[lo][r] = (uint16_t)(bn_pack(v, 0.f) & 0xffffu);
+  b.dst[lo][r] = bf16_round(v);
 }
 
 }  // namespace

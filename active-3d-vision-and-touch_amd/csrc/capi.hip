@@ -10,8 +10,8 @@
 #include <mutex>
 #include <unordered_map>
 
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
@@ -350,7 +350,6 @@ static int check_stack_dims(int ld_feats, int in_features, int num_layers, int h
 
 
 // ---- bf16 STORAGE mode (GEMM_BF16_STORAGE): scratch layout and the stack loops on the bf16 kernels (gcn_bf16s.hip) ----------
-static inline int pad8(int n) { return (n + 7) & ~7; }
 // ReLU-sign bytes per row in this mode: the aggregated-channel bytes cover pad8(cut_len) columns, and the row length is
 // even so that the 2-byte groups of an 8-column epilogue store never straddle rows
 static inline int mask_ld16(int hidden, int cut_len) { return (pad8(cut_len) / 4 + (hidden + 3) / 4 + 1) & ~1; }
@@ -459,7 +458,6 @@ static int stack_fwd16(const float *feats, int ld_feats, int in_features, const 
   const Stack16Layout L = stack16_layout(batch, n_vert, in_features, hidden, num_layers, cut_len, 0);
   const StackStash S = stack_stash(batch, n_vert, hidden, num_layers, cut_len, GEMM_BF16_STORAGE);
   const size_t m = (size_t)batch * n_vert;
-  using u16 = unsigned short;
   int32_t *heavy;
   if (int rc = hub_rows(rowptr, n_vert, max_degree, scratch + L.heavy, &heavy, s)) return rc;
   if (int rc = launch_stack_images(GEMM_BF16_STORAGE, 1, weights, 0, num_layers - 1, in_features, hidden, L.ld0, L.ldh,
@@ -534,7 +532,6 @@ static int stack_bwd16(const float *feats, int ld_feats, int in_features, const 
   const StackStash S = stack_stash(batch, n_vert, hidden, num_layers, cut_len, GEMM_BF16_STORAGE);
   const size_t m = (size_t)batch * n_vert;
   const int last = num_layers - 1;
-  using u16 = unsigned short;
   const u16 *acts16 = static_cast<const u16 *>(acts);
   int32_t *heavyT;
   if (int rc = hub_rows(rowptrT, n_vert, max_degreeT, scratch + L.heavy, &heavyT, s)) return rc;
@@ -1340,7 +1337,6 @@ int check_qnet_dims(int hidden, int cut_len, int n_vert, int batch) {
   }
   return 0;
 }
-bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }  // namespace
 
 size_t a3vt_qnet_input_scratch_bytes(int batch, int n_vert, int hidden, int cut_len, int backward) {
@@ -1355,7 +1351,7 @@ int a3vt_qnet_input_fwd(const float *mesh, const float *w1, const float *b1, con
   if (int rc = check_qnet_dims(hidden, cut_len, n_vert, batch)) return rc;
   A3VT_CHECK_ARG(mesh && w1 && b1 && w2 && b2 && comp_s && comp_t && comp_c && bias && rowptr && col && val && y && scratch);
   A3VT_CHECK_ARG(ld_y % 4 == 0 && ld_y >= hidden);
-  A3VT_CHECK_ARG(al16(mesh) && al16(comp_s) && al16(comp_t) && al16(comp_c) && al16(scratch));
+  A3VT_CHECK_ARG(aligned_to(mesh, 16) && aligned_to(comp_s, 16) && aligned_to(comp_t, 16) && aligned_to(comp_c, 16) && aligned_to(scratch, 16));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const QnetLayout L = qnet_layout(batch, n_vert, hidden, cut_len, 0);
   QnetArgs a{};
@@ -1380,7 +1376,7 @@ int a3vt_qnet_input_bwd(const float *mesh, const float *w1, const float *b1, con
   A3VT_CHECK_ARG(mesh && w1 && b1 && w2 && b2 && comp_c && rowptrT && colT && valT && y && grad_y && scratch);
   A3VT_CHECK_ARG(d_s && d_t && d_c && dw1 && db1 && dw2 && db2 && grad_bias);
   A3VT_CHECK_ARG(ld_y >= hidden && ld_gy >= hidden);
-  A3VT_CHECK_ARG(al16(mesh) && al16(comp_c) && al16(scratch));
+  A3VT_CHECK_ARG(aligned_to(mesh, 16) && aligned_to(comp_c, 16) && aligned_to(scratch, 16));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const QnetLayout L = qnet_layout(batch, n_vert, hidden, cut_len, 1);
   float *dz = scratch + L.dz;
@@ -1399,9 +1395,6 @@ int a3vt_qnet_input_bwd(const float *mesh, const float *w1, const float *b1, con
 }
 
 // ---- FoldingNet fold (fold.hip) ----------------------------------------------------------------------------------------------
-static bool fold_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool fold_al4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 size_t a3vt_fold_workspace_bytes(int batch, int points, int backward) { return fold_workspace_bytes(batch, points, backward); }
 
 int a3vt_fold_fwd(const float *bias_s, const float *g, int k, const float *w1g, const float *w2, const float *b2, const float *w3,
@@ -1410,8 +1403,8 @@ int a3vt_fold_fwd(const float *bias_s, const float *g, int k, const float *w1g, 
   A3VT_CHECK_ARG(k == 2 || k == 3);
   A3VT_CHECK_ARG(batch > 0 && points > 0 && (long long)batch * points <= 16000000);
   A3VT_CHECK_ARG(bias_s && g && w1g && w2 && b2 && w3 && b3 && y && workspace);
-  A3VT_CHECK_ARG(fold_al16(bias_s) && fold_al16(w2) && fold_al16(b2) && fold_al16(w3) && fold_al16(workspace));
-  A3VT_CHECK_ARG(fold_al4(g) && fold_al4(w1g) && fold_al4(b3) && fold_al4(y));
+  A3VT_CHECK_ARG(aligned_to(bias_s, 16) && aligned_to(w2, 16) && aligned_to(b2, 16) && aligned_to(w3, 16) && aligned_to(workspace, 16));
+  A3VT_CHECK_ARG(aligned_to(g, 4) && aligned_to(w1g, 4) && aligned_to(b3, 4) && aligned_to(y, 4));
   A3VT_CHECK_ARG(workspace_bytes >= fold_workspace_bytes(batch, points, 0));
   return launch_fold_fwd(bias_s, g, k, w1g, w2, b2, w3, b3, batch, points, y, static_cast<float *>(workspace),
                          static_cast<hipStream_t>(stream));
@@ -1426,9 +1419,10 @@ int a3vt_fold_bwd(const float *bias_s, const float *g, int k, const float *w1g, 
   A3VT_CHECK_ARG(bias_s && g && w1g && w2 && b2 && w3 && dy && workspace);
   A3VT_CHECK_ARG(d_bias_s && dw1g && dw2 && db2 && dw3 && db3);
   A3VT_CHECK_ARG(dg == nullptr || k == 3);   // the lattice of fold 1 has no gradient
-  A3VT_CHECK_ARG(fold_al16(bias_s) && fold_al16(w2) && fold_al16(b2) && fold_al16(w3) && fold_al16(workspace) && fold_al16(dw2));
-  A3VT_CHECK_ARG(fold_al4(g) && fold_al4(w1g) && fold_al4(dy) && fold_al4(d_bias_s) && fold_al4(dg) && fold_al4(dw1g) && fold_al4(db2) &&
-                 fold_al4(dw3) && fold_al4(db3));
+  A3VT_CHECK_ARG(aligned_to(bias_s, 16) && aligned_to(w2, 16) && aligned_to(b2, 16) && aligned_to(w3, 16) && aligned_to(workspace, 16) &&
+                 aligned_to(dw2, 16));
+  A3VT_CHECK_ARG(aligned_to(g, 4) && aligned_to(w1g, 4) && aligned_to(dy, 4) && aligned_to(d_bias_s, 4) && aligned_to(dg, 4) &&
+                 aligned_to(dw1g, 4) && aligned_to(db2, 4) && aligned_to(dw3, 4) && aligned_to(db3, 4));
   A3VT_CHECK_ARG(workspace_bytes >= fold_workspace_bytes(batch, points, 1));
   return launch_fold_bwd(bias_s, g, k, w1g, w2, b2, w3, dy, batch, points, d_bias_s, dg, dw1g, dw2, db2, dw3, db3,
                          static_cast<float *>(workspace), static_cast<hipStream_t>(stream));
@@ -1661,7 +1655,7 @@ int a3vt_bias_grad_nhwc(const void *grad, int bf16, long long rows, int channels
                         size_t scratch_bytes, void *stream) {
   A3VT_CHECK_ARG(grad && out && scratch);
   A3VT_CHECK_ARG(rows > 0 && channels > 0 && (bf16 == 0 || bf16 == 1));
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(grad) & 15) == 0);
+  A3VT_CHECK_ARG(aligned_to(grad, 16));
   const size_t need = a3vt_bias_grad_scratch_bytes(rows, channels);
   A3VT_CHECK_ARG(need > 0 && scratch_bytes >= need);
   return launch_bias_grad(grad, bf16, rows, channels, out, static_cast<float *>(scratch), static_cast<hipStream_t>(stream));
@@ -1676,7 +1670,7 @@ int a3vt_bnrelu_fwd(const void *x, long long rows, int channels, const float *ga
   A3VT_CHECK_ARG(rows >= 2 && channels > 0 && rows <= (1ll << 40) / channels);
   A3VT_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
   A3VT_CHECK_ARG(eps >= 0.f && momentum >= 0.f && momentum <= 1.f);
-  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(scratch)) & 15) == 0);
+  A3VT_CHECK_ARG(aligned_to(x, 16) && aligned_to(y, 16) && aligned_to(scratch, 16));
   A3VT_CHECK_ARG(bnrelu_wgs(rows * channels, channels, 4, 1024) > 0 && scratch_bytes >= bnrelu_scratch_bytes(channels));
   ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
   return launch_bnrelu_fwd(x, rows, channels, gamma, beta, pre_bias, eps, momentum, running_mean, running_var, num_batches_tracked, y,
@@ -1687,8 +1681,7 @@ int a3vt_bnrelu_bwd(const void *dy, const void *x, long long rows, int channels,
                     float *dbeta, float *dx_colsum, void *scratch, size_t scratch_bytes, void *stream) {
   A3VT_CHECK_ARG(dy && x && save && dx && dgamma && dbeta && scratch);
   A3VT_CHECK_ARG(rows >= 2 && channels > 0 && rows <= (1ll << 40) / channels);
-  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) |
-                   reinterpret_cast<uintptr_t>(scratch)) & 15) == 0);
+  A3VT_CHECK_ARG(aligned_to(x, 16) && aligned_to(dy, 16) && aligned_to(dx, 16) && aligned_to(scratch, 16));
   A3VT_CHECK_ARG(bnrelu_wgs(rows * channels, channels, 4, 1024) > 0 && scratch_bytes >= bnrelu_scratch_bytes(channels));
   ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
   return launch_bnrelu_bwd(dy, x, rows, channels, save, dx, dgamma, dbeta, dx_colsum, scratch, static_cast<hipStream_t>(stream));
@@ -1727,7 +1720,7 @@ int a3vt_conv5_weight_image(const float *weight, int cout, int cin, int flip, vo
   A3VT_CHECK_ARG(weight && image && (flip == 0 || flip == 1));
   A3VT_CHECK_ARG(((cin == 16 || cin == 32) && (cout == 16 || cout == 32)) || (cin == 3 && flip == 0 && (cout == 3 || cout == 16)) ||
                  (cin == 3 && flip == 1 && cout == 16));
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(image) & 15) == 0);
+  A3VT_CHECK_ARG(aligned_to(image, 16));
   return launch_conv5_weight_image(weight, flip, cout, cin, image, static_cast<hipStream_t>(stream));
 }
 
@@ -1738,9 +1731,9 @@ int a3vt_conv5_nhwc(const void *x, int batch, int height, int width, int cin, in
   A3VT_CHECK_ARG(batch > 0 && height > 0 && width > 0 && pad >= 0 && pad <= 4);
   A3VT_CHECK_ARG(height + 2 * pad >= 5 && width + 2 * pad >= 5);
   A3VT_CHECK_ARG((long long)batch * height * width <= (1ll << 31) / 32);
-  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & (cin == 3 ? 1 : 15)) == 0);
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(image) & 15) == 0 && (cout == 3 || (reinterpret_cast<uintptr_t>(y) & 15) == 0));
-  A3VT_CHECK_ARG(bias == nullptr || (reinterpret_cast<uintptr_t>(bias) & (cout == 3 ? 3 : 15)) == 0);
+  A3VT_CHECK_ARG(aligned_to(x, cin == 3 ? 2 : 16) && aligned_to(y, cin == 3 ? 2 : 16));
+  A3VT_CHECK_ARG(aligned_to(image, 16) && (cout == 3 || aligned_to(y, 16)));
+  A3VT_CHECK_ARG(aligned_to(bias, cout == 3 ? 4 : 16));
   ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
   return launch_conv5(x, batch, height, width, cin, cout, stride, pad, image, bias, y, static_cast<hipStream_t>(stream));
 }
@@ -1749,8 +1742,8 @@ int a3vt_conv5_input_grad_3x16s2(const void *grad_out, int batch, int out_height
                                  void *stream) {
   A3VT_CHECK_ARG(grad_out && image && grad_in && batch > 0 && out_height > 0 && out_width > 0);
   A3VT_CHECK_ARG((long long)batch * (2 * out_height + 2) * (2 * out_width + 2) <= (1ll << 31) / 16);
-  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(image)) & 15) == 0);
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(grad_in) & 1) == 0);
+  A3VT_CHECK_ARG(aligned_to(grad_out, 16) && aligned_to(image, 16));
+  A3VT_CHECK_ARG(aligned_to(grad_in, 2));
   ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
   return launch_conv5_up3(grad_out, batch, out_height, out_width, image, grad_in, static_cast<hipStream_t>(stream));
 }
@@ -1764,8 +1757,8 @@ int a3vt_conv5_weight_grad(const void *x, const void *grad_out, int batch, int h
   A3VT_CHECK_ARG(x && grad_out && grad_weight && scratch);
   A3VT_CHECK_ARG(conv5_shape_ok(cin, cout, stride));
   A3VT_CHECK_ARG(batch > 0 && height >= 3 && width >= 3 && (long long)batch * height * width <= (1ll << 31) / 32);
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 15) == 0);
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & (cin == 3 ? 1 : 15)) == 0 && (reinterpret_cast<uintptr_t>(grad_out) & (cout == 3 ? 1 : 15)) == 0);
+  A3VT_CHECK_ARG(aligned_to(scratch, 16));
+  A3VT_CHECK_ARG(aligned_to(x, cin == 3 ? 2 : 16) && aligned_to(grad_out, cout == 3 ? 2 : 16));
   A3VT_CHECK_ARG(scratch_bytes >= conv5_wrw_scratch_bytes(cin, cout));
   ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
   return launch_conv5_wrw(x, grad_out, batch, height, width, cin, cout, stride, grad_weight, scratch, static_cast<hipStream_t>(stream));
@@ -1778,7 +1771,7 @@ size_t a3vt_conv5f_image_bytes(int cin, int cout) { return conv5f_weight_image_b
 int a3vt_conv5f_weight_image(const float *weight, int cout, int cin, void *image, void *stream) {
   A3VT_CHECK_ARG(weight && image);
   A3VT_CHECK_ARG(conv5f_weight_image_bytes(cin, cout) != 0);
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(weight) & 3) == 0 && (reinterpret_cast<uintptr_t>(image) & 15) == 0);
+  A3VT_CHECK_ARG(aligned_to(weight, 4) && aligned_to(image, 16));
   return launch_conv5f_weight_image(weight, cout, cin, image, static_cast<hipStream_t>(stream));
 }
 
@@ -1789,9 +1782,9 @@ int a3vt_conv5f_nhwc(const float *x, int batch, int height, int width, int cin, 
   A3VT_CHECK_ARG(batch >= 1 && height >= 1 && width >= 1 && pad >= 0 && pad <= 4 && (relu == 0 || relu == 1));
   A3VT_CHECK_ARG(height + 2 * pad >= 5 && width + 2 * pad >= 5);          // (an empty output otherwise)
   A3VT_CHECK_ARG((long long)batch * height * width <= (1ll << 31) / 32);
-  A3VT_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & (cin == 3 ? 3 : 15)) == 0);
-  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(image)) & 15) == 0);
-  A3VT_CHECK_ARG(((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 3) == 0);
+  A3VT_CHECK_ARG(aligned_to(x, cin == 3 ? 4 : 16));
+  A3VT_CHECK_ARG(aligned_to(y, 16) && aligned_to(image, 16));
+  A3VT_CHECK_ARG(aligned_to(scale, 4) && aligned_to(shift, 4));
   ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
   return launch_conv5f(x, batch, height, width, cin, cout, stride, pad, image, scale, shift, relu, y, static_cast<hipStream_t>(stream));
 }

@@ -11,16 +11,14 @@
 // best distance per 64-candidate chunk and remembers the winning chunk; that chunk is rescanned once
 // at the end.  Inputs are tiny (120 KB per cloud): the kernel is VALU-bound, not HBM-bound.
 
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 constexpr int kNNTile = 2048;  // candidates staged in LDS per pass (SoA, 24 KiB)
 constexpr int kNNChunk = 64;   // arg-min granularity of the hot loop
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr float kFar = 1.0e18f;
 
 __device__ __forceinline__ f32x2 sqdist2(float qx, float qy, float qz, f32x2 cx, f32x2 cy, f32x2 cz) {

@@ -1,4 +1,4 @@
-// common.h — shared helpers for the gfx950 kernels (internal; not part of the C ABI).
+// common.h — shared helpers for the gfx950 kernels (internal; not part of the C ABI).  The device primitives are in prims.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -77,25 +77,14 @@ enum PathCount {
 };
 void path_count(int which);
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-static inline int pad4(int n) { return (n + 3) & ~3; }
-static inline int pad16(int n) { return (n + 15) & ~15; }
+__host__ __device__ static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+__host__ __device__ static inline int pad4(int n) { return (n + 3) & ~3; }
+__host__ __device__ static inline int pad8(int n) { return (n + 7) & ~7; }
+__host__ __device__ static inline int pad16(int n) { return (n + 15) & ~15; }
+// p is a multiple of `bytes` (a power of two); true for a null pointer
+static inline bool aligned_to(const void *p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 constexpr int kWave = 64;  // gfx950 wavefront
-
-// 64-lane butterfly sum; every lane gets the total.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// 64-lane butterfly max; every lane gets the result.
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // ---- order-independent float accumulation (deterministic scatter-adds) ---------------------------------------------
 // A float atomicAdd makes a sum depend on the order in which the threads arrive.  The backward scatters of this library

@@ -15,18 +15,12 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u16 = unsigned short;
 
 constexpr int kTaps = 25;
 constexpr int kTile = 16;                         // output tile edge (pixels)
@@ -45,15 +39,6 @@ struct C5 {
 
 __device__ __attribute__((aligned(16))) unsigned g_conv5_zero[4];   // 16 bytes of zeros: the source of out-of-map patch pieces
 
-__device__ __forceinline__ void c5_glds16(const void *gsrc, void *lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                   (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ unsigned c5_pack(float a, float b) {   // two floats -> two bf16, round to nearest even
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, b2));
-}
 
 struct Conv5Args {
   const u16 *x;       // [B][H][W][CIN] bf16
@@ -80,7 +65,7 @@ __global__ void conv5_weight_image_kernel(const float *__restrict__ w, int flip,
     // forward: rows = cout, inner = cin, w[m][c]; flipped: rows = cin, inner = cout, w[co = c][ci = m]
     v = flip ? w[((c * real_rows + m) * 5 + (4 - ky)) * 5 + (4 - kx)] : w[((m * inner + c) * 5 + ky) * 5 + kx];
   }
-  out[i] = (u16)(c5_pack(v, 0.f) & 0xffffu);
+  out[i] = bf16_round(v);
 }
 
 // UP3 (the input gradient of layer 1, 3 <- 16 at stride 2, as a stride-1 convolution): the input is read as if upsampled by two with
@@ -110,7 +95,7 @@ __global__ __launch_bounds__(256) void conv5_kernel(Conv5Args a) {
         const int sy = UP3 ? iy >> 1 : iy, sx = UP3 ? ix >> 1 : ix;
         const void *src = in ? static_cast<const void *>(xb + ((size_t)sy * mw + sx) * CIN + part * 8)
                              : static_cast<const void *>(g_conv5_zero);
-        c5_glds16(src, lds + i0 * 16);
+        glds16(src, lds + i0 * 16);
       }
     }
   }
@@ -155,7 +140,7 @@ __global__ __launch_bounds__(256) void conv5_kernel(Conv5Args a) {
       if (UP3) {
         if (q == 0) {
           u16 *o = a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * 3;
-          const unsigned lo = c5_pack(acc[0][0], acc[0][1]), hi = c5_pack(acc[0][2], 0.f);
+          const unsigned lo = bf16_pack2(acc[0][0], acc[0][1]), hi = bf16_pack2(acc[0][2], 0.f);
           o[0] = (u16)(lo & 0xffffu);
           o[1] = (u16)(lo >> 16);
           o[2] = (u16)(hi & 0xffffu);
@@ -164,7 +149,7 @@ __global__ __launch_bounds__(256) void conv5_kernel(Conv5Args a) {
 #pragma unroll
         for (int mb = 0; mb < S::kMB; ++mb) {
           const f32x4 v = acc[mb] + bs[mb];
-          const u32x2 o = {c5_pack(v[0], v[1]), c5_pack(v[2], v[3])};
+          const u32x2 o = {bf16_pack2(v[0], v[1]), bf16_pack2(v[2], v[3])};
           *reinterpret_cast<u32x2 *>(a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * COUT + mb * 16 + 4 * q) = o;
         }
       }
@@ -231,11 +216,11 @@ __global__ __launch_bounds__(256) void conv5c3_kernel(Conv5Args a) {
     if (oy < a.Ho && ox < a.Wo) {
       const f32x4 v = acc + bs;
       if (COUT == 16) {
-        const u32x2 o = {c5_pack(v[0], v[1]), c5_pack(v[2], v[3])};
+        const u32x2 o = {bf16_pack2(v[0], v[1]), bf16_pack2(v[2], v[3])};
         *reinterpret_cast<u32x2 *>(a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * 16 + 4 * q) = o;
       } else if (q == 0) {
         u16 *o = a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * 3;
-        const unsigned lo = c5_pack(v[0], v[1]), hi = c5_pack(v[2], 0.f);
+        const unsigned lo = bf16_pack2(v[0], v[1]), hi = bf16_pack2(v[2], 0.f);
         o[0] = (u16)(lo & 0xffffu);
         o[1] = (u16)(lo >> 16);
         o[2] = (u16)(hi & 0xffffu);
@@ -254,7 +239,7 @@ __global__ void conv5c3_weight_image_kernel(const float *__restrict__ w, int cou
   const int tap = 8 * s + 2 * q + (e >> 2), c = e & 3;
   float v = 0.f;
   if (tap < kTaps && c < 3 && m < cout) v = w[((m * 3 + c) * 5 + tap / 5) * 5 + tap % 5];
-  out[i] = (u16)(c5_pack(v, 0.f) & 0xffffu);
+  out[i] = bf16_round(v);
 }
 
 template <int COUT, int STRIDE>
@@ -300,7 +285,6 @@ struct Conv5WrwArgs {
 // Transposed LDS reads as written instructions: with an LDS-DMA in flight the compiler puts s_waitcnt vmcnt(0) in front of every
 // LDS read it issues itself (csr16t_kernel, gcn_bf16s.hip) — here that is the NEXT tile's prefetch.  The waits are written too and
 // tied to the registers they release.
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 template <int OFF>
 __device__ __forceinline__ u32x2 c5_tr64(unsigned addr) {
   u32x2 r;
@@ -361,7 +345,7 @@ __global__ __launch_bounds__(320) void conv5_wrw_kernel(Conv5WrwArgs a) {
           const int oy = oy0 + r, ox = ox0 + c;
           const void *src = (oy < a.Ho && ox < a.Wo) ? static_cast<const void *>(gb + ((size_t)oy * a.Wo + ox) * COUT + part * 8)
                                                       : static_cast<const void *>(g_conv5_zero);
-          c5_glds16(src, st + i0 * 16);
+          glds16(src, st + i0 * 16);
         }
       }
     }
@@ -376,7 +360,7 @@ __global__ __launch_bounds__(320) void conv5_wrw_kernel(Conv5WrwArgs a) {
           const int iy = oy0 * STRIDE + py - 1, ix = ox0 * STRIDE + px - 1;
           const void *src = (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) ? static_cast<const void *>(xb + ((size_t)iy * a.W + ix) * CIN + part * 8)
                                                                          : static_cast<const void *>(g_conv5_zero);
-          c5_glds16(src, st + kGyBytes + i0 * 16);
+          glds16(src, st + kGyBytes + i0 * 16);
         }
       }
     }
@@ -472,14 +456,6 @@ __global__ __launch_bounds__(16 * kRedSlices) void conv5_wrw_reduce_kernel(const
 constexpr int kC3Blocks = 7, kC3Image = kC3Blocks * 64 * 4;      // floats per partial image
 constexpr int kC3Wgs = 1024;
 
-__device__ __forceinline__ bf16x8 c5_tr_pair(const char *p, int block2_bytes) {
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(p + block2_bytes));
-  return __builtin_bit_cast(bf16x8, (s16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
-}
-
 // a [rows][cols] window of 6-byte pixels of a map -> 8-byte pixels in LDS (zero outside the map)
 __device__ __forceinline__ void c5_stage_px3(const u16 *map, int H, int W, int y0, int x0, int rows, int cols, char *dst) {
   for (int p = threadIdx.x; p < rows * cols; p += 256) {
@@ -539,7 +515,7 @@ __global__ __launch_bounds__(256) void conv5c3_wrw_kernel(Conv5WrwArgs a) {
         const int oy = oy0 + p / kWC, ox = ox0 + p % kWC;
         const void *src = (oy < a.Ho && ox < a.Wo) ? static_cast<const void *>(gb + ((size_t)oy * a.Wo + ox) * 16 + part * 8)
                                                     : static_cast<const void *>(g_conv5_zero);
-        c5_glds16(src, gy_l + i0 * 16);
+        glds16(src, gy_l + i0 * 16);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
@@ -549,11 +525,11 @@ __global__ __launch_bounds__(256) void conv5c3_wrw_kernel(Conv5WrwArgs a) {
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
       const int r = wave * 2 + rr;
-      const bf16x8 af = c5_tr_pair(a_ptr + r * a_row, COUT == 16 ? 16 * 32 : 16 * 8);
+      const bf16x8 af = tr_operand(reinterpret_cast<const u16 *>(a_ptr + r * a_row), COUT == 16 ? 16 : 4);
       const char *xr = x_l + r * STRIDE * kPW * 8;
 #pragma unroll
       for (int nb = 0; nb < kC3Blocks; ++nb) {
-        const bf16x8 bf = c5_tr_pair(xr + boff[nb], 16 * STRIDE * 8);
+        const bf16x8 bf = tr_operand(reinterpret_cast<const u16 *>(xr + boff[nb]), STRIDE * 4);
         acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[nb], 0, 0, 0);
       }
     }

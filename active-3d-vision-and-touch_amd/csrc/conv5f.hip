@@ -27,14 +27,13 @@
 //  * Epilogue in registers: D[m = channel][n = pixel] leaves a lane with channels 4 q .. 4 q + 3 of its pixel: scale, shift, ReLU, one
 //    16-byte store per row; a wave instruction writes 16 pixels x 64 bytes.
 // The K loop is MFMAs and LDS reads only (fp32 MFMA and the vector ALU share a pipe: profiles/r06_fp32_pipe_ubench.txt).
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kTaps = 25;
 constexpr int kTileW = 16;

@@ -10,8 +10,8 @@
 // The reference walks the batch in a Python loop (one device sync per sample) around a dozen small launches.  Here one workgroup
 // does the batch: a wave per sample (lanes over the actions), then the mean as a fixed-order tree over the squares kept in LDS —
 // no atomics, the same bits on every call.  B <= 4096, A <= 304.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 

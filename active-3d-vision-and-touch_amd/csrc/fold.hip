@@ -34,7 +34,6 @@
 
 namespace a3vt {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kFW = 512;           // the compiled width
 constexpr int kFLd = 516;          // floats per row of an LDS tile read as MFMA fragments (ds_read_b128, 4-bank row skew)

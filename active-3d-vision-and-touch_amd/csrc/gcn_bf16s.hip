@@ -12,25 +12,11 @@
 //                                     16-byte lane access, 16-lane groups per vertex)
 #include <stdlib.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using s16x4 = __attribute__((ext_vector_type(4))) short;
-using s16x8 = __attribute__((ext_vector_type(8))) short;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u16 = unsigned short;
-
-__device__ __forceinline__ unsigned pack2_bf16(float a, float b) {  // RNE, a in the low half
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2));
-}
-__device__ __forceinline__ u16 bf16_of(float v) { return (u16)(pack2_bf16(v, 0.f) & 0xffffu); }
-__device__ __forceinline__ float f32_of(u16 h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
 // 8 bf16 (one 16-byte access) <-> 8 floats
 struct F8 {
   f32x4 lo, hi;
@@ -39,27 +25,19 @@ __device__ __forceinline__ F8 unpack8(u32x4 r) {
   F8 o;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    o.lo[2 * t] = __builtin_bit_cast(float, r[t] << 16);
-    o.lo[2 * t + 1] = __builtin_bit_cast(float, r[t] & 0xffff0000u);
-    o.hi[2 * t] = __builtin_bit_cast(float, r[2 + t] << 16);
-    o.hi[2 * t + 1] = __builtin_bit_cast(float, r[2 + t] & 0xffff0000u);
+    o.lo[2 * t] = bf16_lo(r[t]);
+    o.lo[2 * t + 1] = bf16_hi(r[t]);
+    o.hi[2 * t] = bf16_lo(r[2 + t]);
+    o.hi[2 * t + 1] = bf16_hi(r[2 + t]);
   }
   return o;
 }
 __device__ __forceinline__ u32x4 pack8(const F8 &v) {
-  return u32x4{pack2_bf16(v.lo[0], v.lo[1]), pack2_bf16(v.lo[2], v.lo[3]), pack2_bf16(v.hi[0], v.hi[1]),
-               pack2_bf16(v.hi[2], v.hi[3])};
+  return u32x4{bf16_pack2(v.lo[0], v.lo[1]), bf16_pack2(v.lo[2], v.lo[3]), bf16_pack2(v.hi[0], v.hi[1]),
+               bf16_pack2(v.hi[2], v.hi[3])};
 }
 __device__ __forceinline__ float f8_get(const F8 &v, int t) { return t < 4 ? v.lo[t] : v.hi[t - 4]; }
 
-__device__ __forceinline__ void glds16b(const void *gsrc, void *lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                   (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // ------------------------------------------------------------------------------------------------
 // fp32 rows -> bf16 rows, zero padded to ld_out (stack input features; ld_out % 8 == 0)
@@ -105,7 +83,7 @@ __global__ void weight_images16_kernel(WeightImages w) {
     } else {
       if (r < k && c < n) v = src[(size_t)r * n + c];
     }
-    dst[idx] = bf16_of(v);
+    dst[idx] = bf16_round(v);
   }
 }
 int launch_weight_images16(const WeightImages &w, int max_rows, int max_ld, hipStream_t s) {
@@ -127,14 +105,6 @@ int launch_weight_images16(const WeightImages &w, int max_rows, int max_ld, hipS
 // 4-row blocks — with 608-byte rows (24 banks mod 64) rows r and r + 8 would land on the same banks, rows r and r + 4 do not.
 // ------------------------------------------------------------------------------------------------
 constexpr int DW16_MAXI = 5, DW16_MAXO = 3;
-
-__device__ __forceinline__ bf16x8 tr_operand(const u16 *lds_row0_col, int row_stride_elems) {
-  // address of (the lane's row of its first block, the lane's 4-column quad); the second block sits 16 rows further
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(lds_row0_col));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(lds_row0_col + 16 * row_stride_elems));
-  return __builtin_bit_cast(bf16x8, (s16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
-}
 
 __global__ __launch_bounds__(1024, 1) void dw16_kernel(Dw16Args p) {
   extern __shared__ __attribute__((aligned(16))) u16 lds16[];
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(1024, 1) void dw16_kernel(Dw16Args p) {
     const int rows_left = p.m - unit * 32;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      glds16b(srow[j] < rows_left || rows_left >= 32 ? (const void *)sp[j] : (const void *)p.zeros, base + sdst[j]);
+      glds16(srow[j] < rows_left || rows_left >= 32 ? (const void *)sp[j] : (const void *)p.zeros, base + sdst[j]);
       sp[j] += sstep[j];
     }
   };
@@ -232,10 +202,10 @@ __global__ __launch_bounds__(1024, 1) void dw16_kernel(Dw16Args p) {
   int buf = 0;
   for (int t = 0; t < nu; ++t) {
     const int younger = min(nu - 1 - t, nst - 2);
-    if (younger >= 3) wait_vm<6>();
-    else if (younger == 2) wait_vm<4>();
-    else if (younger == 1) wait_vm<2>();
-    else wait_vm<0>();
+    if (younger >= 3) wait_vmcnt<6>();
+    else if (younger == 2) wait_vmcnt<4>();
+    else if (younger == 1) wait_vmcnt<2>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (t + nst - 1 < nu) issue(u0 + t + nst - 1, buf >= 1 ? buf - 1 : nst - 1);
     const u16 *sb = lds16 + buf * stage;
@@ -423,7 +393,7 @@ __device__ __forceinline__ void csr16_fwd_store(const F8 &acc, int ch, int c, co
   } else {
 #pragma unroll
     for (int t = 0; t < 8; ++t)
-      if (ch + t < c) yo[t] = bf16_of(f8_get(o, t));
+      if (ch + t < c) yo[t] = bf16_round(f8_get(o, t));
   }
   // two sign bytes (4 channels each) in one 2-byte store: ch is a multiple of 8 and the mask rows have even length
   if (mrow) *reinterpret_cast<u16 *>(mrow + (ch >> 2)) = (u16)((bits & 15u) | ((bits >> 4) << 8));
@@ -805,10 +775,10 @@ __device__ __forceinline__ void t16_stage_tile(const T16Args &a, char *buf, long
   for (int i0 = wave * 64; i0 < kTilePieces; i0 += 256) {
     const int i = i0 + lane;
     const int r = (i * 5042) >> 16, p = i - r * kT16Pieces;       // i / 13 (exact below 2^12)
-    glds16b(sb + (long long)(t0 + (r < rows_here ? r : 0)) * a.ld_src + p * 8, buf + i0 * 16);
+    glds16(sb + (long long)(t0 + (r < rows_here ? r : 0)) * a.ld_src + p * 8, buf + i0 * 16);
   }
-  if (t < rows_here) glds16b(a.plan.slot + (size_t)(t0 + t) * kT16Slots, buf + kT16LdsRows + wave * 64 * 16);
-  if (t < rows_here * 2) glds16b(a.plan.wgt + (size_t)t0 * kT16Slots + t * 4, buf + kT16LdsRows + kT16LdsSlots + wave * 64 * 16);
+  if (t < rows_here) glds16(a.plan.slot + (size_t)(t0 + t) * kT16Slots, buf + kT16LdsRows + wave * 64 * 16);
+  if (t < rows_here * 2) glds16(a.plan.wgt + (size_t)t0 * kT16Slots + t * 4, buf + kT16LdsRows + kT16LdsSlots + wave * 64 * 16);
   if (t < kT16Pieces) *reinterpret_cast<u32x4 *>(buf + (kT16Zero * kT16Pieces + t) * 16) = u32x4{0u, 0u, 0u, 0u};
 }
 // The halo rows, from the unit's header in LDS (list = LDS byte address of its first entry).
@@ -821,7 +791,7 @@ __device__ __forceinline__ void t16_stage_halo(const T16Args &a, char *buf, long
     if (i < total) {
       const int r = (i * 5042) >> 16, p = i - r * kT16Pieces;
       const int v = t16_lds32(list + r * 4);       // (a written read: see t16_lds128)
-      glds16b(sb + (long long)v * a.ld_src + p * 8, buf + (kT16Tile * kT16Pieces + i0) * 16);
+      glds16(sb + (long long)v * a.ld_src + p * 8, buf + (kT16Tile * kT16Pieces + i0) * 16);
     }
   }
 }
@@ -1025,7 +995,7 @@ __global__ __launch_bounds__(256) void csr16t_kernel(T16Args a) {
     }
   }
   if (BWD) {
-    wait_vm<0>();
+    wait_vmcnt<0>();
     __syncthreads();          // (no DMA in flight, nobody reads a buffer any more)
     float(*red)[128] = reinterpret_cast<float(*)[128]>(lds);
 #pragma unroll

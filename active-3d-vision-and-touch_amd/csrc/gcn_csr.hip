@@ -5,12 +5,11 @@
 // row-normalised CSR adjacency (nnz 17,922 on the 2562-vertex icosphere vs 6.6 M dense entries), fused
 // with the partial bias add and ReLU of model.py:357-358,361,363.  All of these are HBM/L2-bound
 // gathers of 400-byte rows; the neighbour rows of one mesh (<= 1 MB) live in the XCD's L2.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // XCD-aware work mapping.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 names the XCD group,
 // MI355X_MICROARCH.md "Workgroup dispatch"), each XCD has a private 4 MiB L2, and a neighbour gather only

@@ -6,12 +6,11 @@
 // Compiled with -fno-slp-vectorize (lib.py): the sums below are written per component on purpose — as <4 x float> the
 // compiler forms v_pk_fma_f32 and keeps every edge weight as a (w, w) register pair, which doubles the registers of the
 // index entries a thread holds and spills them; packed fp32 has no throughput advantage on gfx950.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // ------------------------------------------------------------------------------------------------
 // Channel-sliced aggregation with the whole mesh resident in LDS (round 3; the stack's default when it fits).
@@ -44,11 +43,8 @@ constexpr int kEllW = 8;      // edge slots per vertex in the slot-major index i
 // are read at a 28-byte lane stride, i.e. every 128-byte line of col / val is touched once per edge slot (8.6 line
 // accesses per line); here consecutive lanes read consecutive 8-byte entries.  Built once per stack call
 // (n_vert x 17 words); edges beyond kEllW stay in CSR.
-using i32x2 = __attribute__((ext_vector_type(2))) int;
 // by-value helpers: __builtin_bit_cast applied DIRECTLY to an element of an ext_vector reads element 0 with this hipcc
 // ("a compiler trap worth recording") — the first version of this kernel multiplied by the column index
-__device__ __forceinline__ float bits_to_f32(int x) { return __builtin_bit_cast(float, x); }
-__device__ __forceinline__ int f32_to_bits(float x) { return __builtin_bit_cast(int, x); }
 __global__ void csr_ell_build_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
                                      const float *__restrict__ val, int n_vert, i32x2 *__restrict__ ell,
                                      int32_t *__restrict__ degs) {
@@ -58,7 +54,7 @@ __global__ void csr_ell_build_kernel(const int32_t *__restrict__ rowptr, const i
   degs[v] = n;
 #pragma unroll
   for (int j = 0; j < kEllW; ++j)
-    ell[(size_t)j * n_vert + v] = j < n ? i32x2{colidx[e0 + j], f32_to_bits(val[e0 + j])} : i32x2{n_vert, 0};
+    ell[(size_t)j * n_vert + v] = j < n ? i32x2{colidx[e0 + j], (int)f32_bits(val[e0 + j])} : i32x2{n_vert, 0};
 }
 size_t csrq_ell_ints(int n_vert) { return (size_t)n_vert * (2 * kEllW + 1) + 64; }
 int launch_csrq_ell(const int32_t *rowptr, const int32_t *col, const float *val, int n_vert, int32_t *ell, hipStream_t s) {
@@ -115,7 +111,7 @@ __global__ __launch_bounds__(kCsrqThreads) void csrq_kernel(const float *__restr
       const i32x2 e = ell[(size_t)j * n_vert + vv[k]];
       const int e0 = e[0], e1 = e[1];
       cj[k][j] = e0;
-      wj[k][j] = bits_to_f32(e1);
+      wj[k][j] = bits_f32((unsigned)e1);
     }
   }
 

@@ -21,12 +21,10 @@
 //     32 row sums per class in LDS, and — behind the barrier the slice needs anyway — one lane-parallel read and a DPP tree per
 //     wave.  Fixed order everywhere: outputs are bit-repeatable and do not depend on the batch size or on `parts`.
 // Not bit-identical to the row walk over the full CSR (other association of the same sum): gated by the fp64 oracle.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kQsThreads = 512;
 constexpr int kQsPairs = 6;              // 12 edge slots per vertex
@@ -90,11 +88,6 @@ __device__ __forceinline__ float qs_sum32(float x) {
   const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 16));
   return a + b;
 }
-__device__ __forceinline__ int qs_wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // MODE 0: Y = relu(scale * (P Z + bipartite) + bias) on the aggregated channels (model.py:356-358,363), sign bytes out.
 // MODE 1: dZa = P (G .* sign / d) + bipartite, bias-gradient partial per (mesh, quad) (autograd of the same lines).
@@ -134,7 +127,7 @@ __global__ __launch_bounds__(kQsThreads) void csrqs_kernel(const float *__restri
     fs[k] = cl == 1 ? 1.f : 0.f;
     fc[k] = cl == 2 ? 1.f : 0.f;
     wv[k] = __builtin_bit_cast(float, img[(size_t)(kQsPairs + 1) * n_vert + vv[k]]);
-    npairs[k] = __builtin_amdgcn_readfirstlane(qs_wave_max((int)((info & 255u) + 1) >> 1));
+    npairs[k] = __builtin_amdgcn_readfirstlane(wave_max((int)((info & 255u) + 1) >> 1));
 #pragma unroll
     for (int jp = 0; jp < kQsPairs; ++jp) pk[k][jp] = img[(size_t)jp * n_vert + vv[k]];
   }

@@ -223,17 +223,17 @@ __global__ __launch_bounds__(64 * WAVES, 2) void rowgemm_kernel(RowGemmArgs p) {
         for (int jp = 0; jp < NP; ++jp) {
           f32x4 bn0 = bc0, bn1 = bc1;
           if (ST16) {
-            acc[0][2 * jp] = mfma_bf16s(af[0], bc0, acc[0][2 * jp]);
+            acc[0][2 * jp] = mfma_bf16x32(af[0], bc0, acc[0][2 * jp]);
             __builtin_amdgcn_sched_barrier(0);
             if (jp + 1 < NP) {
               bn0 = *reinterpret_cast<const f32x4 *>(sBl + (2 * jp + 2) * 256);
               if (2 * jp + 3 < NT) bn1 = *reinterpret_cast<const f32x4 *>(sBl + (2 * jp + 3) * 256);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (2 * jp + 1 < NT) acc[0][2 * jp + 1] = mfma_bf16s(af[0], bc1, acc[0][2 * jp + 1]);
+            if (2 * jp + 1 < NT) acc[0][2 * jp + 1] = mfma_bf16x32(af[0], bc1, acc[0][2 * jp + 1]);
             if (nm > 1) {
-              acc[1][2 * jp] = mfma_bf16s(af[1], bc0, acc[1][2 * jp]);
-              if (2 * jp + 1 < NT) acc[1][2 * jp + 1] = mfma_bf16s(af[1], bc1, acc[1][2 * jp + 1]);
+              acc[1][2 * jp] = mfma_bf16x32(af[1], bc0, acc[1][2 * jp]);
+              if (2 * jp + 1 < NT) acc[1][2 * jp + 1] = mfma_bf16x32(af[1], bc1, acc[1][2 * jp + 1]);
             }
           } else if (BF16) {
             const s16x4 b0 = cvt_bf16x4(bc0), b1 = cvt_bf16x4(bc1);

@@ -18,20 +18,12 @@
 // active lanes write one 608-byte row per instruction, straight-line code).  The DMA waves' counted vmcnt waits step over
 // their own stores of the previous block (a fixed number per block; loads, LDS-DMA and stores retire in issue order on the
 // one counter).  Two workgroup barriers per block.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u16 = unsigned short;
 
 constexpr int kRows = 48;                  // rows per block (3 tiles of 16)
 constexpr int kRT = kRows / 16;
@@ -44,24 +36,6 @@ constexpr int kMaskSlot = 1280;            // floats (5120 B) per sign-byte slot
 constexpr int kLdsFloats = kStages * kStage + kEp + 2 * kMaskSlot;   // 161,536 B
 constexpr int kAInstr = kRT * kKS;         // LDS-DMA wave-instructions per block of A
 
-__device__ __forceinline__ void glds16(const float *gsrc, float *lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                   (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma(f32x4 a, f32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 pack8(f32x4 lo, f32x4 hi) {   // 8 floats -> 8 bf16 (RNE, v_cvt_pk_bf16_f32)
-  const bf16x2 a = __builtin_convertvector((f32x2){lo[0], lo[1]}, bf16x2), b = __builtin_convertvector((f32x2){lo[2], lo[3]}, bf16x2);
-  const bf16x2 c = __builtin_convertvector((f32x2){hi[0], hi[1]}, bf16x2), d = __builtin_convertvector((f32x2){hi[2], hi[3]}, bf16x2);
-  return __builtin_bit_cast(f32x4, (u32x4){__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                           __builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d)});
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // all but the n youngest vector-memory operations of this wave are done (n <= 26: the A pieces of one block + one block's stores)
 __device__ __forceinline__ void wait_younger(int n) {
   switch (n) {
@@ -194,12 +168,12 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int rt = 0; rt < kRT; ++rt) {
-        acc[rt][0] = mfma(a[rt], bfrag[0][s], acc[rt][0]);
-        acc[rt][1] = mfma(a[rt], bfrag[1][s], acc[rt][1]);
+        acc[rt][0] = mfma_bf16x32(a[rt], bfrag[0][s], acc[rt][0]);
+        acc[rt][1] = mfma_bf16x32(a[rt], bfrag[1][s], acc[rt][1]);
       }
       if (third) {
 #pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) acc[rt][2] = mfma(a[rt], bfrag[2][s], acc[rt][2]);
+        for (int rt = 0; rt < kRT; ++rt) acc[rt][2] = mfma_bf16x32(a[rt], bfrag[2][s], acc[rt][2]);
       }
       if (s < 8) {
         __builtin_amdgcn_sched_barrier(0);
@@ -241,7 +215,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
           const int row = row_first + i;
           const bool rok = row < p.m;
           f32x4 v[2] = {*reinterpret_cast<const f32x4 *>(e + i * kEpLd), *reinterpret_cast<const f32x4 *>(e + i * kEpLd + 4)};
-          const f32x4 raw = pack8(v[0], v[1]);
+          const f32x4 raw = pack_bf16x8(v[0], v[1]);
           unsigned bits = 0;
 #pragma unroll
           for (int h = 0; h < 2; ++h)
@@ -254,7 +228,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
           if (has_z) {
             if (rok && to_z) *reinterpret_cast<f32x4 *>(z16 + (size_t)row * p.ldc2 + col) = raw;
           }
-          if (rok && to_y) *reinterpret_cast<f32x4 *>(c16 + (size_t)row * p.ldc + col) = pack8(v[0], v[1]);
+          if (rok && to_y) *reinterpret_cast<f32x4 *>(c16 + (size_t)row * p.ldc + col) = pack_bf16x8(v[0], v[1]);
           if (p.maskb) {   // two sign bytes (4 columns each); bytes of groups left of the cut are never read
             if (rok && on)
               *reinterpret_cast<u16 *>(p.maskb + (size_t)row * p.mld + p.moff + 2 * c8) = (u16)((bits & 15u) | ((bits >> 4) << 8));
@@ -277,7 +251,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm16_kernel(RowGemmArgs p) {
           for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int t = 0; t < 4; ++t) v[h][t] = ((keep >> (4 * h + t)) & 1u) ? v[h][t] : 0.f;
-          if (row < p.m && on) *reinterpret_cast<f32x4 *>(c16 + (size_t)row * p.ldc + col) = pack8(v[0], v[1]);
+          if (row < p.m && on) *reinterpret_cast<f32x4 *>(c16 + (size_t)row * p.ldc + col) = pack_bf16x8(v[0], v[1]);
         }
       }
       wait_lgkm0();   // this wave's reads of the output tile and the sign slot are done before it reaches the next barrier

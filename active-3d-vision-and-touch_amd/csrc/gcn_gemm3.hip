@@ -27,18 +27,12 @@
 // sign bytes, row-major or the quad-major hybrid layout; backward: ReLU-sign multiply from the bytes DMA'd into LDS).
 #include <type_traits>
 
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 constexpr int kNT = 19;                 // column tiles of 16
 constexpr int kWaves = 8;
@@ -53,34 +47,18 @@ constexpr int kBPer = (kPieces + kDmaWaves - 1) / kDmaWaves;   // Bt pieces per 
 constexpr size_t kLdsBytes = (size_t)(kStages * kStage + kWaves * kMSlot) * sizeof(float);   // 149,504 B
 static_assert(kLdsBytes <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ void glds16(const float *gsrc, float *lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                   (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma(f32x4 a, f32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ unsigned fbits(float v) { return __builtin_bit_cast(unsigned, v); }
-__device__ __forceinline__ float bfloat(unsigned v) { return __builtin_bit_cast(float, v); }
-__device__ __forceinline__ unsigned cvt_pk(float a, float b) {   // v_cvt_pk_bf16_f32: round to nearest even, a in the low half
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2));
-}
-
 // The exact three-way split of two floats (a -> low halves, b -> high halves of the packed words):
 //   hi  = the upper 16 bits of x (truncation: never overflows, x - hi is exact and has the sign of x),
 //   mid = RNE_bf16(x - hi), lo = (x - hi) - mid  — exact again, and lo has at most 8 significant bits, so it IS a bf16.
 // hi + mid + lo == x for every finite x whose lowest set bit is >= 2^-133 (the bf16 subnormal grid; all normal floats
 // down to 2^-110 qualify); below that the difference is < 2^-133.  11 VALU instructions per pair.
 __device__ __forceinline__ void split3_pair(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-  const unsigned ua = fbits(a), ub = fbits(b);
+  const unsigned ua = f32_bits(a), ub = f32_bits(b);
   h = __builtin_amdgcn_perm(ub, ua, 0x07060302u);            // (ua >> 16) | (ub & 0xffff0000)
-  const float ra = a - bfloat(ua & 0xffff0000u), rb = b - bfloat(ub & 0xffff0000u);
-  m = cvt_pk(ra, rb);
-  const float sa = ra - bfloat(m << 16), sb = rb - bfloat(m & 0xffff0000u);
-  l = cvt_pk(sa, sb);
+  const float ra = a - bits_f32(ua & 0xffff0000u), rb = b - bits_f32(ub & 0xffff0000u);
+  m = bf16_pack2(ra, rb);
+  const float sa = ra - bits_f32(m << 16), sb = rb - bits_f32(m & 0xffff0000u);
+  l = bf16_pack2(sa, sb);
 }
 struct Pieces {
   f32x4 h, m, l;   // 8 bf16 each, element j = k-offset j of the lane's 8 operand elements
@@ -133,12 +111,12 @@ __device__ __forceinline__ void rowtile3_unit(const RowGemmArgs &p, int row_base
     for (int c = 0; c < KB; ++c) {
       if (c0 + c >= nch) break;
       const Pieces ap = split3_x8(ra[c][0], ra[c][1]);
-      acc = mfma(ap.h, rb[c][2], acc);
-      acc = mfma(ap.m, rb[c][1], acc);
-      acc = mfma(ap.h, rb[c][1], acc);
-      acc = mfma(ap.l, rb[c][0], acc);
-      acc = mfma(ap.m, rb[c][0], acc);
-      acc = mfma(ap.h, rb[c][0], acc);
+      acc = mfma_bf16x32(ap.h, rb[c][2], acc);
+      acc = mfma_bf16x32(ap.m, rb[c][1], acc);
+      acc = mfma_bf16x32(ap.h, rb[c][1], acc);
+      acc = mfma_bf16x32(ap.l, rb[c][0], acc);
+      acc = mfma_bf16x32(ap.m, rb[c][0], acc);
+      acc = mfma_bf16x32(ap.h, rb[c][0], acc);
     }
   }
   // C/D layout: this lane holds column n0 + l16 of rows 4 q .. 4 q + 3 of the tile
@@ -307,23 +285,23 @@ __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p)
 #pragma unroll
       for (int j = 0; j < kNT; ++j) {
 #pragma unroll
-        for (int i = 0; i < NM; ++i) acc[i][j] = mfma(ap[i].h, bl, acc[i][j]);
+        for (int i = 0; i < NM; ++i) acc[i][j] = mfma_bf16x32(ap[i].h, bl, acc[i][j]);
         __builtin_amdgcn_sched_barrier(0);
         if (j + 1 < kNT) bl = *reinterpret_cast<const f32x4 *>(sB + (2 * kNT + j + 1) * 256);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < NM; ++i) {
-          acc[i][j] = mfma(ap[i].m, bm, acc[i][j]);
-          acc[i][j] = mfma(ap[i].h, bm, acc[i][j]);
+          acc[i][j] = mfma_bf16x32(ap[i].m, bm, acc[i][j]);
+          acc[i][j] = mfma_bf16x32(ap[i].h, bm, acc[i][j]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (j + 1 < kNT) bm = *reinterpret_cast<const f32x4 *>(sB + (kNT + j + 1) * 256);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < NM; ++i) {
-          acc[i][j] = mfma(ap[i].l, bh, acc[i][j]);
-          acc[i][j] = mfma(ap[i].m, bh, acc[i][j]);
-          acc[i][j] = mfma(ap[i].h, bh, acc[i][j]);
+          acc[i][j] = mfma_bf16x32(ap[i].l, bh, acc[i][j]);
+          acc[i][j] = mfma_bf16x32(ap[i].m, bh, acc[i][j]);
+          acc[i][j] = mfma_bf16x32(ap[i].h, bh, acc[i][j]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (j + 1 < kNT) bh = *reinterpret_cast<const f32x4 *>(sB + (j + 1) * 256);
@@ -336,19 +314,19 @@ __global__ __launch_bounds__(64 * kWaves, 2) void rowgemm3_kernel(RowGemmArgs p)
     // (one loop per tile count: with both bodies inside one loop the register allocator spills the accumulators)
     if (nm == 2) {
       for (int t = 0; t < nchunks; ++t) {
-        wait_vm0();                       // chunk t (this wave's share) has landed
+        wait_vmcnt<0>();                  // chunk t (this wave's share) has landed
         __builtin_amdgcn_s_barrier();     // ... everyone's has; everyone is done with chunk t - 1's stage
         chunk_step(std::integral_constant<int, 2>{}, t);
       }
     } else if (nm == 1) {
       for (int t = 0; t < nchunks; ++t) {
-        wait_vm0();
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         chunk_step(std::integral_constant<int, 1>{}, t);
       }
     } else {                              // idle wave of a partial round: it still carries its share of the Bt staging
       for (int t = 0; t < nchunks; ++t) {
-        wait_vm0();
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if (t + 1 < nchunks) {
 #pragma unroll
@@ -553,10 +531,6 @@ __global__ void split3_kernel(const float *__restrict__ x, size_t n, unsigned sh
 // Two barriers per stage.  The raw slots are wave-private (a wave splits the quads it requested), so the next stage's DMA is
 // issued as soon as a wave holds its quads in registers and stays in flight through the split, the barriers and the MFMA phase.
 // ------------------------------------------------------------------------------------------------
-using s16x4 = __attribute__((ext_vector_type(4))) short;
-using s16x8 = __attribute__((ext_vector_type(8))) short;
-using u16 = unsigned short;
-
 constexpr int kDwThreads = 512;
 constexpr int kDwXq = 76, kDwZq = 40;                    // fp32 quads per stage row: X (304 columns), dZ window (160)
 constexpr int kDwUnits = 32 * (kDwXq + kDwZq);           // 3712 quads per stage
@@ -566,13 +540,6 @@ constexpr int kDwXimg = 32 * kDwXld, kDwZimg = 32 * kDwZld;
 constexpr int kDwPieceElems = 3 * (kDwXimg + kDwZimg);   // 46,080 bf16 = 92,160 B
 constexpr int kDwRawFloats = kDwPer * kDwThreads * 4;    // 16,384 floats = 65,536 B
 constexpr size_t kDwLdsBytes = (size_t)kDwPieceElems * 2 + (size_t)kDwRawFloats * 4 + 1024;   // + tail slack for clamped tiles
-
-__device__ __forceinline__ f32x4 tr_operand(const u16 *lds_row0_col, int row_stride_elems) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(lds_row0_col));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(lds_row0_col + 16 * row_stride_elems));
-  return __builtin_bit_cast(f32x4, (s16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
-}
 
 __global__ __launch_bounds__(kDwThreads, 2) void dw3_kernel(DwArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -717,7 +684,7 @@ __global__ __launch_bounds__(kDwThreads, 2) void dw3_kernel(DwArgs p) {
   // and the whole MFMA phase to land.
   if (nu > 0) issue(u0);
   for (int t = 0; t < nu; ++t) {
-    wait_vm0();                     // this wave's quads of stage t have landed
+    wait_vmcnt<0>();                // this wave's quads of stage t have landed
     f32x4 rv[kDwPer];
 #pragma unroll
     for (int j = 0; j < kDwPer; ++j) rv[j] = *reinterpret_cast<const f32x4 *>(raw + (j * kDwThreads + tid) * 4);
@@ -737,7 +704,6 @@ __global__ __launch_bounds__(kDwThreads, 2) void dw3_kernel(DwArgs p) {
         const bool isx = pdst[j] < 3 * kDwXimg;
         u16 *d = pieces + pdst[j];
         const int img = isx ? kDwXimg : kDwZimg;
-        using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
         *reinterpret_cast<u32x2 *>(d) = u32x2{hh[j][0], hh[j][1]};
         *reinterpret_cast<u32x2 *>(d + img) = u32x2{mm[j][0], mm[j][1]};
         *reinterpret_cast<u32x2 *>(d + 2 * img) = u32x2{ll[j][0], ll[j][1]};
@@ -752,17 +718,17 @@ __global__ __launch_bounds__(kDwThreads, 2) void dw3_kernel(DwArgs p) {
     f32x4 fa[5], fb[5], fc[5];
     auto load_a = [&](f32x4 (&dst)[5], int piece) {
 #pragma unroll
-      for (int i = 0; i < 5; ++i) dst[i] = tr_operand(xp + piece * kDwXimg + xoff[i], kDwXld);
+      for (int i = 0; i < 5; ++i) dst[i] = __builtin_bit_cast(f32x4, tr_operand(xp + piece * kDwXimg + xoff[i], kDwXld));
     };
     auto load_b = [&](f32x4 (&dst)[5], int piece) {
 #pragma unroll
-      for (int j = 0; j < 5; ++j) dst[j] = tr_operand(zp + piece * kDwZimg + zoff[j], kDwZld);
+      for (int j = 0; j < 5; ++j) dst[j] = __builtin_bit_cast(f32x4, tr_operand(zp + piece * kDwZimg + zoff[j], kDwZld));
     };
     auto pass = [&](const f32x4 (&av)[5], const f32x4 (&bv)[5]) {
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 #pragma unroll
-        for (int j = 0; j < 5; ++j) acc[i][j] = mfma(av[i], bv[j], acc[i][j]);
+        for (int j = 0; j < 5; ++j) acc[i][j] = mfma_bf16x32(av[i], bv[j], acc[i][j]);
     };
     load_a(fa, 0);                  // a_h
     load_b(fb, 2);                  // b_l

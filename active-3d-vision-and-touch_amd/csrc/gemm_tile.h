@@ -1,61 +1,19 @@
-// gemm_tile.h — helpers shared by the fp32 / bf16 product kernels (gcn_gemm.hip, gcn_gemmw.hip): LDS-DMA, bf16 packing, counted
-// waits, and rowtile_unit — one 16 x 16 output tile with its operands pulled straight from global memory (the leftover rows
-// of a load-balanced split).  Internal; moved here unchanged from gcn_gemm.hip in round 6.
+// gemm_tile.h — helpers shared by the fp32 / bf16 product kernels (gcn_gemm.hip, gcn_gemmw.hip, gcn_dww.hip) on top of prims.h:
+// rowtile_unit — one 16 x 16 output tile with its operands pulled straight from global memory (the leftover rows of a
+// load-balanced split) — and w_at.  Internal.
+//
+// Operand modes of the products.  bf16 operand mode (MODE 1, "bf16 + MFMA feature MLP", BASELINE configs[3]/[4]): the fp32 values
+// staged in LDS are rounded to bf16 (cvt_bf16x4) as they are read into fragments and multiplied with v_mfma_f32_16x16x16_bf16
+// into the same fp32 accumulators — ONE bf16 MFMA replaces the four fp32 16x16x4 steps (1/8 of the matrix-pipe time).
+// bf16 STORAGE mode (MODE 2, "bf16s"): activations, gradients and the weight images are stored as bf16; a staged 64-byte chunk
+// row then holds 32 k values instead of 16 and a lane's ds_read_b128 IS the operand of v_mfma_f32_16x16x32_bf16 (mfma_bf16x32) —
+// no conversion, half the chunks.  All pointers / strides of RowGemmArgs stay in 4-byte units on the operand side (a row of
+// 304 bf16 = 152 "floats"); the outputs of the hidden-layer epilogues are bf16 with their leading dimension in elements.
 #pragma once
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-// 16-byte LDS-DMA: each active lane copies 16 B from its own global address to lds_base + lane*16.
-__device__ __forceinline__ void glds16(const float *gsrc, float *lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                   (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
-// bf16 operand mode ("bf16 + MFMA feature MLP", BASELINE configs[3]/[4]): the fp32 values staged in LDS are rounded to
-// bf16 (RNE, v_cvt_pk_bf16_f32) as they are read into fragments and multiplied with v_mfma_f32_16x16x16_bf16 into the
-// same fp32 accumulators.  A lane's ds_read_b128 already holds k = 4q..4q+3 of its row — exactly the operand layout of
-// the 16x16x16 instruction — so ONE bf16 MFMA replaces the four fp32 16x16x4 steps (1/8 of the matrix-pipe time).
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using s16x4 = __attribute__((ext_vector_type(4))) short;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-__device__ __forceinline__ s16x4 cvt_bf16x4(f32x4 v) {
-  const bf16x2 lo = __builtin_convertvector((f32x2){v[0], v[1]}, bf16x2);
-  const bf16x2 hi = __builtin_convertvector((f32x2){v[2], v[3]}, bf16x2);
-  const u32x2 r = {__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
-  return __builtin_bit_cast(s16x4, r);
-}
-
-// bf16 STORAGE mode (gemm mode 2, "bf16s"): activations, gradients and the weight images are stored as bf16; a staged
-// 64-byte chunk row then holds 32 k values instead of 16 and a lane's ds_read_b128 (8 consecutive bf16 of its row) IS
-// the A / B operand of v_mfma_f32_16x16x32_bf16 — no conversion, one MFMA per (m-tile, n-tile) and chunk, half the chunks.
-// All pointers / strides of RowGemmArgs stay in 4-byte units on the operand side (a row of 304 bf16 = 152 "floats"); the
-// outputs of the hidden-layer epilogues are bf16 with their leading dimension in elements.  fp32 accumulation throughout.
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u16 = unsigned short;
-__device__ __forceinline__ f32x4 mfma_bf16s(f32x4 a, f32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ u16 to_bf16(float v) {  // round to nearest even (v_cvt_pk_bf16_f32)
-  const bf16x2 r = __builtin_convertvector((f32x2){v, 0.f}, bf16x2);
-  return (u16)(__builtin_bit_cast(unsigned, r) & 0xffffu);
-}
-__device__ __forceinline__ f32x4 pack_bf16x8(f32x4 lo, f32x4 hi) {  // 8 floats -> 8 bf16 in one 16-byte register group
-  const s16x4 a = cvt_bf16x4(lo), b = cvt_bf16x4(hi);
-  const u32x2 ua = __builtin_bit_cast(u32x2, a), ub = __builtin_bit_cast(u32x2, b);
-  using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-  return __builtin_bit_cast(f32x4, (u32x4){ua[0], ua[1], ub[0], ub[1]});
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // One 16 x 16 output tile — rows row_base + 16 mt .., columns n0 .. — with its operands pulled straight from global
 // memory into registers: all loads of up to 19 K-chunks in flight at once, no LDS, no barrier, then the MFMA chain (one
@@ -92,7 +50,7 @@ __device__ __forceinline__ void rowtile_unit(const RowGemmArgs &p, int row_base,
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
       if (MODE == 2) {
-        acc = mfma_bf16s(af[c], bf[c], acc);
+        acc = mfma_bf16x32(af[c], bf[c], acc);
       } else if (MODE == 1) {
         acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(cvt_bf16x4(af[c]), cvt_bf16x4(bf[c]), acc, 0, 0, 0);
       } else {
@@ -122,8 +80,8 @@ __device__ __forceinline__ void rowtile_unit(const RowGemmArgs &p, int row_base,
         p.maskb[(size_t)row * p.mld + p.moff + (col >> 2)] = (uint8_t)bits;
       if (MODE == 2) {  // bf16 rows; the pad columns [n_store, ldc) are written too (exact zeros: Bt rows there are zero)
         if (row_ok && col < p.ldc) {
-          if (col < p.csplit) reinterpret_cast<u16 *>(p.c2)[(size_t)row * p.ldc2 + col] = to_bf16(v);
-          else reinterpret_cast<u16 *>(p.c)[(size_t)row * p.ldc + col] = to_bf16((v > 0.f || p.no_relu) ? v : 0.f);
+          if (col < p.csplit) reinterpret_cast<u16 *>(p.c2)[(size_t)row * p.ldc2 + col] = bf16_round(v);
+          else reinterpret_cast<u16 *>(p.c)[(size_t)row * p.ldc + col] = bf16_round((v > 0.f || p.no_relu) ? v : 0.f);
         }
       } else if (row_ok && col_ok) {
         if (p.zq_nvert > 0 && col < p.zq_quads * 4) {   // quad-major raw columns (RowGemmArgs::zq_nvert)
@@ -143,7 +101,7 @@ __device__ __forceinline__ void rowtile_unit(const RowGemmArgs &p, int row_base,
       if (MODE == 2) {
         if (row_ok && col < p.ldc) {
           const unsigned byte = col_ok ? p.maskb[(size_t)row * p.mld + (col < p.csplit ? 0 : p.moff) + (col >> 2)] : 0u;
-          reinterpret_cast<u16 *>(p.c)[(size_t)row * p.ldc + col] = to_bf16(((byte >> (col & 3)) & 1u) ? v : 0.f);
+          reinterpret_cast<u16 *>(p.c)[(size_t)row * p.ldc + col] = bf16_round(((byte >> (col & 3)) & 1u) ? v : 0.f);
         }
       } else if (row_ok && col_ok) {
         if (p.zq_nvert > 0 && col < p.zq_quads * 4) {   // quad-major gradient columns: unmasked (RowGemmArgs::zq_nvert)

@@ -37,25 +37,15 @@
 // §4, §8.  All kernels are deterministic in their outputs (the order of points inside a grid cell depends on LDS atomics, the
 // minima do not).
 
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kPB = 64;                 // points per block = lanes per wave
 constexpr float kPadCoord = 1.0e18f;    // coordinates of the pad entries of a cloud's last block (never a minimum)
 constexpr int kSortThreads = 1024;
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-// (__builtin_bit_cast applied directly to an element of an ext_vector reads element 0 with this compiler: go through
-// a by-value argument)
-__device__ __forceinline__ int as_int(float v) { return __builtin_bit_cast(int, v); }
 __device__ __forceinline__ float sq3(float dx, float dy, float dz) {
   return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));   // the distance arithmetic of chamfer.hip
 }
@@ -488,7 +478,7 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
   int32_t *oi = fwd ? a.ixy + (size_t)z * a.p : a.iyx + (size_t)z * a.q;
 
   const f32x4 me = qpts[(size_t)qblk * kPB + lane];
-  const int qidx = as_int(me[3]);
+  const int qidx = (int)f32_bits(me[3]);
   // Pad lanes (last block of the cloud) ask for lane 0's point and write nothing.  Lane 0's coordinates are read with
   // v_readlane BEFORE the select: as `qidx < 0 ? __shfl(me[0], 0, 64) : me[0]` the shuffle ran in the branch of the pad lanes
   // only, where lane 0 is inactive — a bpermute from an inactive lane returns 0, so the pad lanes asked about the ORIGIN.
@@ -496,9 +486,9 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
   // (the untrained network's sphere): everything is then equidistant, nothing can be pruned, and the last query block of
   // every cloud evaluated 440-590 of the 625 groups — 192 waves of 2.2 ms each at the tail of a 1.5 ms launch
   // (profiles/r05_nn_wave_timeline.txt).
-  const float q0x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(as_int(me[0]), 0));
-  const float q0y = __builtin_bit_cast(float, __builtin_amdgcn_readlane(as_int(me[1]), 0));
-  const float q0z = __builtin_bit_cast(float, __builtin_amdgcn_readlane(as_int(me[2]), 0));
+  const float q0x = __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)f32_bits(me[0]), 0));
+  const float q0y = __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)f32_bits(me[1]), 0));
+  const float q0z = __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)f32_bits(me[2]), 0));
   const float qx = qidx < 0 ? q0x : me[0];
   const float qy = qidx < 0 ? q0y : me[1];
   const float qz = qidx < 0 ? q0z : me[2];
@@ -620,7 +610,7 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
 #pragma unroll 4
     for (int j = 0; j < 16; ++j) {
       const f32x4 cnd = rp[j];
-      const int ci = as_int(cnd[3]);
+      const int ci = (int)f32_bits(cnd[3]);
       if (sq3(qx - cnd[0], qy - cnd[1], qz - cnd[2]) == best && ci >= 0) bidx = min(bidx, ci);
     }
   }
@@ -638,7 +628,7 @@ __device__ __forceinline__ void nn_query_wave(const NNQuery &a, int y, int qblk,
       const f32x4 *__restrict__ tp = tpts + (size_t)blk * kPB;
       for (int j = 0; j < kPB; ++j) {
         const f32x4 cnd = tp[j];
-        const int ci = as_int(cnd[3]);
+        const int ci = (int)f32_bits(cnd[3]);
         if (tie && ci >= 0 && sq3(qx - cnd[0], qy - cnd[1], qz - cnd[2]) == best) bidx = min(bidx, ci);
       }
     }
@@ -699,7 +689,7 @@ size_t nn_pruned_workspace_bytes(int draws, int batch, int p, int q) {
 int launch_nn_pruned(const float *x, const float *y, int draws, int batch, int p, int q, float *dxy, int32_t *ixy,
                      float *dyx, int32_t *iyx, void *ws, hipStream_t s, int y_batch) {
   if (y_batch <= 0) y_batch = batch;   // clouds in y: pair (draw, mesh b) asks y[b % y_batch]
-  if (reinterpret_cast<uintptr_t>(ws) & 15) {
+  if (!aligned_to(ws, 16)) {
     set_error("chamfer_fwd: the workspace of the pruned search must be 16-byte aligned");
     return -1;
   }

@@ -15,12 +15,11 @@
 // (one atomic per pixel-channel per workgroup); the position gradient is a wave reduction per vertex.
 #include <float.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 struct Bilinear {
   int x0, y0;             // north-west corner

@@ -9,12 +9,11 @@
 // contiguous row).  Backward recomputes the activations, back-propagates to the vertex position
 // (the path that links refinement stage s+1 to stage s) and reduces the parameter gradients per
 // workgroup through LDS into slabs that slab_reduce sums in a fixed order.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 template <int I>
 struct PE {

@@ -17,12 +17,11 @@
 // its bias row IS the bias gradient, its four one-hot rows ARE the embedding gradient — and dX' = dZ B'^T on rowgemm,
 // the ReLU masks from the saved activations, the sin / cos chain rule for the vertex positions at the end.
 // Every sum runs in a fixed order (slab reduces): bit-reproducible.
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 namespace {
 

@@ -17,14 +17,13 @@
 // dh2 = dZ C^T, walks back through L2 and L1, and keeps dC, the per-token column sums of dZ (dT; dS is their sum over tokens per
 // sample), dW2, db2, dW1, db1 in registers over ALL its tiles; one partial image per workgroup, summed by one launch in a fixed
 // order.  No atomics: two calls give the same bits.  No position gradient (observations need none).
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kRows = 64;                  // vertex rows per tile
 constexpr int kE = 63, kH1 = 25, kH2 = 50; // widths of the encoder's input and two hidden activations
@@ -115,7 +114,6 @@ __device__ __forceinline__ void enc_tile(const EncLds &L, const float *__restric
   __syncthreads();
 }
 
-__device__ __forceinline__ int dpad4(int n) { return (n + 3) & ~3; }
 __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 __device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(256) void qnet_fwd_kernel(QnetArgs a, int tiles_per
   const EncLds L = enc_carve(lds);
   const int b = blockIdx.x / tiles_per, v0 = (blockIdx.x - b * tiles_per) * kRows;
   const int nrows = a.n_vert - v0 < kRows ? a.n_vert - v0 : kRows;
-  const int npad = dpad4(a.hidden), nq = npad / 4, cpad = dpad4(a.cut_len);
+  const int npad = pad4(a.hidden), nq = npad / 4, cpad = pad4(a.cut_len);
   enc_load_weights(L, a);
   enc_tile(L, a.mesh + (size_t)b * a.n_vert * 4, v0, nrows);
 
@@ -202,7 +200,7 @@ __global__ __launch_bounds__(256) void qnet_bwd_kernel(QnetArgs a, int tiles_per
   float *dp2 = dyn + kEncFloats;               // [64][52] gradient before the second ReLU
   float *dp1 = dp2 + kRows * kLdH2;            // [64][28] gradient before the first ReLU
   float *Cl = dp1 + kRows * kLdH1;             // [50][ldcl] the composite C
-  const int npad = dpad4(a.hidden), nq = npad / 4, ldcl = c_lds_ld(npad);
+  const int npad = pad4(a.hidden), nq = npad / 4, ldcl = c_lds_ld(npad);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / wgs_per, g0 = blockIdx.x - b * wgs_per;

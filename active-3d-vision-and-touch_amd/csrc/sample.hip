@@ -8,8 +8,8 @@
 // mode draws them from Philox4x32-10 through an inverse-CDF search (same distribution, tested
 // statistically).  Backward = scatter-add of w_k * grad into the three corner vertices (autograd of
 // the gather at :175,182-184).
-#include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace a3vt {
 

@@ -130,7 +130,7 @@ def build(force=False, verbose=False):
 
 def _build(force, verbose, lib_path, objdir):
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "gemm_tile.h")] + \
+    deps = srcs + [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "prims.h", "gemm_tile.h")] + \
         [os.path.join(_HERE, "..", "include", "a3vt.h")]
     force = force or os.environ.get("A3VT_FORCE_BUILD", "0") not in ("", "0")   # prove on any box that it compiles
     if not force and os.path.exists(lib_path) and all(
