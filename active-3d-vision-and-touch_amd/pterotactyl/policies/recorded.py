@@ -1,0 +1,91 @@
+"""``RecordedSampler``: the sampler interface of ``ActiveTouch`` (``policies/environment.py``) answered from recorded signals.
+
+The reference's environment drives its simulator through two calls, ``sampler.load_objects(names, from_dataset=True)`` and
+``sampler.sample(actions, touch_point_cloud=True)`` (``simulator/scene/sampler.py:62-175``).  The simulator needs pybullet and
+pyrender; this class replays what it recorded instead, with the same signatures and the same result dict (the reference's key
+spellings included):
+
+    touch_status             E x 4 strings: "touch", "no_touch" or "no_intersection"
+    touch_signal             (E, 4, 121, 121, 3) float32, values 0..255
+    finger_transfrom_pos     (E, 4, 3) float32
+    finger_transform_rot_M   (E, 4, 3, 3) float32
+
+Sources:
+* a mapping ``{(object_id, action): record}``; a record holds ``touch`` (4, 121, 121, 3), ``pos`` (4, 3), ``rot`` (4, 3, 3) and
+  ``status`` (4 strings);
+* a dataset root laid out as ``mesh_loader_touch`` reads it: ``grasp_info/<id>/<action>/<finger>_touch.npy`` and
+  ``<finger>_ref_frame.npy`` (pickled ``{"rot", "pos"}``).
+
+Conventions of THIS package (the reference never replays, so none of this restates it): in a dataset tree a finger with a touch
+image is "touch", a finger with only a frame file is "no_touch", a finger with neither is "no_intersection" and all zeros; the
+object id is the basename of the ``names`` entry given to ``load_objects``; an unknown ``(id, action)`` is "no_intersection" for
+all four fingers, like a grasp that failed (``sampler.py:115-121``)."""
+import os
+from collections.abc import Mapping
+
+import numpy as np
+import torch
+
+FINGERS = 4
+NO_CONTACT = "no_intersection"
+
+
+def _tree_record(root, obj, action):
+    d = os.path.join(root, "grasp_info", obj, str(action))
+    if not os.path.isdir(d):
+        return None
+    rec = {"touch": np.zeros((FINGERS, 121, 121, 3), np.float32), "pos": np.zeros((FINGERS, 3), np.float32),
+           "rot": np.zeros((FINGERS, 3, 3), np.float32), "status": [NO_CONTACT] * FINGERS}
+    for f in range(FINGERS):
+        frame = os.path.join(d, f"{f}_ref_frame.npy")
+        if not os.path.exists(frame):
+            continue
+        ref = np.load(frame, allow_pickle=True).item()
+        rec["pos"][f], rec["rot"][f] = np.asarray(ref["pos"]).reshape(3), np.asarray(ref["rot"]).reshape(3, 3)
+        touch = os.path.join(d, f"{f}_touch.npy")
+        if os.path.exists(touch):
+            rec["touch"][f] = np.load(touch)
+            rec["status"][f] = "touch"
+        else:
+            rec["status"][f] = "no_touch"
+    return rec
+
+
+class RecordedSampler:
+    def __init__(self, source, bs=None, vision=False):
+        """``source``: the mapping or the dataset root described above; ``bs`` and ``vision`` are accepted for the reference's
+        constructor shape (``Sampler(grasp, bs=, vision=)``) and not needed: the batch is whatever ``load_objects`` was given."""
+        if not isinstance(source, Mapping) and not os.path.isdir(os.path.join(str(source), "grasp_info")):
+            raise ValueError(f"RecordedSampler: {source!r} is neither a mapping of records nor a directory holding grasp_info/")
+        self.source = source
+        self.bs = bs
+        self.ids = []
+
+    def load_objects(self, batch, from_dataset=True, scale=3.1):
+        self.ids = [os.path.basename(os.path.normpath(str(name))) for name in batch]
+
+    def record(self, obj, action):
+        if isinstance(self.source, Mapping):
+            return self.source.get((obj, int(action)))
+        return _tree_record(str(self.source), obj, int(action))
+
+    def sample(self, actions, touch_point_cloud=False, **unused):
+        if len(actions) != len(self.ids):
+            raise ValueError(f"RecordedSampler: {len(actions)} actions for {len(self.ids)} loaded objects")
+        E = len(self.ids)
+        status = [[NO_CONTACT] * FINGERS for _ in range(E)]
+        touch = torch.zeros((E, FINGERS, 121, 121, 3))
+        pos = torch.zeros((E, FINGERS, 3))
+        rot = torch.zeros((E, FINGERS, 3, 3))
+        for e, (obj, action) in enumerate(zip(self.ids, actions)):
+            rec = self.record(obj, action)
+            if rec is None:
+                continue
+            status[e] = [str(s) for s in rec["status"]]
+            touch[e] = torch.as_tensor(np.asarray(rec["touch"]), dtype=torch.float32)
+            pos[e] = torch.as_tensor(np.asarray(rec["pos"]), dtype=torch.float32)
+            rot[e] = torch.as_tensor(np.asarray(rec["rot"]), dtype=torch.float32)
+        return {"touch_status": status, "touch_signal": touch, "finger_transfrom_pos": pos, "finger_transform_rot_M": rot}
+
+    def disconnect(self):
+        pass

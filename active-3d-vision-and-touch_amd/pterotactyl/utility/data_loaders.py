@@ -13,7 +13,8 @@
 
 The data root is a directory argument (``args.data_root``, or the ``PTEROTACTYL_DATA`` environment variable) instead of
 the reference's package-relative constants (:18-29) — the dataset is a download, not part of either tree.
-``mesh_loader_touch`` (reference :47-127) is the touch trainer's dataset: see the class.
+``mesh_loader_touch`` (reference :47-127) is the touch trainer's dataset, ``mesh_loader_active`` (:263-336) the policy
+environment's: see the classes.
 ``DevicePrefetcher`` is the host->HBM leg: pinned staging buffers and a copy stream one batch ahead of the compute
 stream, so a 65 ms GPU step is not stalled by the 7.7 MB (no image) / 58 MB (image) batch upload.
 """
@@ -184,6 +185,60 @@ class mesh_loader_touch(object):
                 "samples": torch.stack([item["samples"] for item in batch]),
                 "sim_touch": torch.stack([item["sim_touch"] for item in batch]),
                 "ref": {"rot": torch.stack([item["rot"] for item in batch]), "pos": torch.stack([item["pos"] for item in batch])}}
+
+
+class mesh_loader_active(object):
+    """The environment's dataset (reference ``utility/data_loaders.py:263-336``): the objects of the split's ``set_type`` that
+    have an image file and a point cloud; ``limit_data`` keeps 400 of the image files (``random.Random(0)`` shuffle) before the
+    filter; the length is rounded down to a multiple of ``env_batch_size``.
+
+        batch = {"names": ["<root>/object_info/<id>"], "gt_points": (B,number_points,3) f32,
+                 "img": (B,3,256,256) f32 in [0,1] | (B,1) dummy}"""
+
+    def __init__(self, args, set_type="RL_train"):
+        self.args = args
+        self.set_type = set_type
+        root = data_root(args)
+        self.point_dir = os.path.join(root, "point_cloud_info")
+        self.image_dir = os.path.join(root, "images_colourful")
+        self.obj_dir = os.path.join(root, "object_info")
+        names = [os.path.splitext(os.path.basename(f))[0] for f in glob(os.path.join(self.image_dir, "*.npy"))]
+        if getattr(args, "limit_data", False):
+            random.Random(0).shuffle(names)
+            names = names[:400]
+        wanted = set(load_split(args)[set_type])
+        self.object_names = [n for n in names if os.path.exists(os.path.join(self.point_dir, n + ".npy")) and n in wanted]
+        print(f"The number of {set_type} set objects found : {len(self.object_names)}")
+
+    def __len__(self):
+        return (len(self.object_names) // self.args.env_batch_size) * self.args.env_batch_size
+
+    def get_instance(self, index):
+        obj = self.object_names[index]
+        count = random.choice(range(0, self.args.num_grasps + 1))
+        order = list(range(50))
+        random.shuffle(order)
+        return obj, order[:count]
+
+    def get_points(self, obj):
+        samples = np.load(os.path.join(self.point_dir, obj + ".npy"))
+        np.random.shuffle(samples)
+        return torch.FloatTensor(samples[: self.args.number_points])
+
+    def get_image(self, obj):
+        if not self.args.use_img:
+            return torch.empty((1))
+        img = np.load(os.path.join(self.image_dir, obj + ".npy"))
+        return torch.FloatTensor(img).permute(2, 0, 1) / 255.0
+
+    def __getitem__(self, index):
+        obj = self.object_names[index]
+        return {"names": os.path.join(self.obj_dir, obj), "gt_points": self.get_points(obj), "img": self.get_image(obj)}
+
+    def collate(self, batch):
+        return {"names": [item["names"] for item in batch],
+                "gt_points": torch.cat([item["gt_points"].unsqueeze(0) for item in batch]),
+                "img": torch.cat([item["img"].unsqueeze(0) for item in batch])}
 
 
 class DevicePrefetcher:

@@ -1,0 +1,159 @@
+#!/usr/bin/env python
+"""One greedy step of the ActiveTouch environment (``policies/environment.py::best_step``), batched against the reference's
+candidate loop, at the reference's defaults: E = 3 elements, K = 50 candidate actions, 30 000 surface points and 30 000-point
+clouds, 20 GCN layers x 300, for both chart topologies (``finger``: atlas + 5 charts, N = 1949; four fingers: atlas + 20 charts,
+N = 2324).  The sampler is a ``RecordedSampler`` over synthetic records, so no simulator time is in the figures; the models carry
+seeded weights with damped output layers (centimetre deformations, as trained models make: the search's pruning sees realistic
+geometry); the surface draws are fixed (``score_samples``), so both paths score the same points and ``same_actions`` /
+``score_rel_diff`` compare their decisions.
+
+Protocol: the two paths alternate in one process on the same environment (``args.batched_greedy`` switched per call); every call
+is ``reset`` (not timed) then ``best_step`` (timed: device events around the call, which ends in the step's device-to-host
+copies, and the host clock around the same window); ``--warmup`` calls of each path first, then ``--calls`` each.  Reported per
+path: median, p10, p90 of the device-event times, the host-clock median, and the allocator's peak during a step.  The verdict
+line applies the project's rule for a knob's default: on only if the batched p90 lies below the loop's p10 at both topologies.
+
+    python tools/env_bench.py > profiles/env_greedy_step_ab.txt"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def write_checkpoint(directory, config, net):
+    os.makedirs(directory)
+    with open(os.path.join(directory, "config.json"), "w") as f:
+        json.dump(dict(config, check_point=directory), f)
+    torch.save({k: v.detach().cpu() for k, v in net.state_dict().items()}, os.path.join(directory, "model"))
+    return directory + "/"
+
+
+def synthetic_records(objects, actions, seed):
+    """{(object, action): record}: random tactile images, frames on a 12 cm sphere, two fingers in three touching."""
+    g = torch.Generator().manual_seed(seed)
+    status = ("touch", "touch", "no_touch", "no_intersection")
+    out = {}
+    for o in objects:
+        for a in range(actions):
+            q, _ = torch.linalg.qr(torch.randn(4, 3, 3, generator=g))
+            d = torch.randn(4, 3, generator=g)
+            out[(o, a)] = {"touch": torch.randint(0, 256, (4, 121, 121, 3), generator=g).float(), "rot": q.contiguous(),
+                           "pos": 0.12 * d / d.norm(dim=-1, keepdim=True),
+                           "status": [status[int(i)] for i in torch.randint(0, 4, (4,), generator=g)]}
+    return out
+
+
+def percentiles(ms):
+    return {"median": float(np.percentile(ms, 50)), "p10": float(np.percentile(ms, 10)), "p90": float(np.percentile(ms, 90))}
+
+
+def measure(finger, a, root):
+    from a3vt_amd.pterotactyl.policies import environment, recorded
+    from a3vt_amd.pterotactyl.reconstruction.touch import model as touch_model
+    from a3vt_amd.pterotactyl.reconstruction.vision import model as vision_model
+    from a3vt_amd.pterotactyl.utility import utils
+    from a3vt_amd.synthetic import gt_cloud
+    tag = "finger" if finger else "four_fingers"
+    config = dict(use_img=False, use_touch=True, finger=finger, num_grasps=5, num_GCN_layers=a.layers, hidden_GCN_size=300, cut=0.33)
+    info, verts = utils.load_mesh_vision(SimpleNamespace(**config), "vision_charts")
+    torch.manual_seed(0)
+    deform = vision_model.Deformation(info, verts, SimpleNamespace(**config))
+    with torch.no_grad():
+        for gcn in (deform.mesh_deform_1, deform.mesh_deform_2):
+            gcn.layers[-1].weight.mul_(0.02)
+            gcn.layers[-1].bias.mul_(0.02)
+    torch.manual_seed(0)
+    locations = {"vision_location": write_checkpoint(os.path.join(root, tag, "vision"), config, deform),
+                 "touch_location": write_checkpoint(os.path.join(root, tag, "touch"), {}, touch_model.Encoder())}
+    args = SimpleNamespace(seed=0, eval=True, pretrained_recon=False, use_img=False, use_touch=True, finger=finger, num_grasps=5,
+                           use_latent=False, num_actions=a.candidates, budget=5, env_batch_size=a.env, number_points=a.points,
+                           loss_coeff=9000.0, batched_greedy=True, candidate_chunk=a.chunk, **locations)
+    objects = [f"object{e}" for e in range(a.env)]
+    class Environment(environment.ActiveTouch):
+        def get_loaders(self):                                       # no dataset: the batch below is synthetic
+            pass
+
+    env = Environment(args, sampler=recorded.RecordedSampler(synthetic_records(objects, a.candidates, 1)))
+    # the same surface draws for every call: the two paths score the same points, so their choices can be compared
+    g = torch.Generator().manual_seed(2)
+    env.score_samples = (torch.randint(0, info["faces"].shape[0], (3, a.env, a.points), generator=g).to(torch.int32),
+                         torch.rand(3, a.env, a.points, generator=g), torch.rand(3, a.env, a.points, generator=g))
+    batch = {"names": ["/data/object_info/" + o for o in objects], "gt_points": gt_cloud(a.env, a.points, 3), "img": torch.zeros(a.env, 1)}
+
+    def call(batched):
+        args.batched_greedy = batched
+        env.reset(batch)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        actions, obs, _, _ = env.best_step()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), 1e3 * (time.perf_counter() - t0), torch.cuda.max_memory_allocated(), actions, obs
+
+    for _ in range(a.warmup):
+        for batched in (True, False):
+            call(batched)
+    dev = {True: [], False: []}
+    host = {True: [], False: []}
+    peak = {True: 0, False: 0}
+    chosen = {}
+    for _ in range(a.calls):
+        for batched in (True, False):
+            d, h, p, actions, obs = call(batched)
+            dev[batched].append(d)
+            host[batched].append(h)
+            peak[batched] = max(peak[batched], p)
+            chosen[batched] = (actions, obs["score"])
+    rec = {"topology": tag, "n_vert": 1824 + 125 * (1 if finger else 4),
+           "env": a.env, "candidates": a.candidates, "points": a.points, "layers": a.layers, "candidate_chunk": a.chunk,
+           "calls": a.calls, "warmup": a.warmup,
+           "same_actions": bool(np.array_equal(chosen[True][0], chosen[False][0])),
+           "score_rel_diff": float(((chosen[True][1] - chosen[False][1]).abs() / chosen[False][1].abs()).max())}
+    for batched, name in ((True, "batched"), (False, "loop")):
+        rec[name] = dict(percentiles(dev[batched]), host_median=float(np.percentile(host[batched], 50)),
+                         peak_allocated_MiB=peak[batched] / 2 ** 20)
+    rec["speedup_median"] = rec["loop"]["median"] / rec["batched"]["median"]
+    rec["batched_p90_below_loop_p10"] = rec["batched"]["p90"] < rec["loop"]["p10"]
+    return rec
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--env", type=int, default=3)
+    p.add_argument("--candidates", type=int, default=50)
+    p.add_argument("--points", type=int, default=30000)
+    p.add_argument("--layers", type=int, default=20)
+    p.add_argument("--calls", type=int, default=30)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--chunk", type=int, default=None, help="args.candidate_chunk of the batched path")
+    a = p.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("env_bench: no GPU visible; nothing is measured without one")
+    print(f"# one ActiveTouch.best_step, batched vs the candidate loop; device-event ms per call; {torch.cuda.get_device_name(0)}")
+    verdict = True
+    with tempfile.TemporaryDirectory() as root:
+        for finger in (True, False):
+            rec = measure(finger, a, root)
+            verdict = verdict and rec["batched_p90_below_loop_p10"]
+            for name in ("batched", "loop"):
+                r = rec[name]
+                print(f"# {rec['topology']:>12} {name:>7}: median {r['median']:8.2f}  p10 {r['p10']:8.2f}  p90 {r['p90']:8.2f}  "
+                      f"host median {r['host_median']:8.2f}  allocator peak {r['peak_allocated_MiB']:8.0f} MiB")
+            print(json.dumps(rec))
+    print(f"# batched p90 below loop p10 at both topologies: {verdict} -> BATCHED_GREEDY_DEFAULT = {verdict}")
+
+
+if __name__ == "__main__":
+    main()
