@@ -44,8 +44,10 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
 }
 
 // CLAMP: the reference's `param.grad.data.clamp_(-1, 1)` before the step (policies/DDQN/ddqn.py:120-122) inside the same launch: the
-// clamped gradient is what the step uses and what is left in the gradient tensor (4 more bytes written per parameter).
-__device__ __forceinline__ float clamp_grad(float g, float c) { return fminf(fmaxf(g, -c), c); }
+// clamped gradient is what the step uses and what is left in the gradient tensor (4 more bytes written per parameter).  As
+// torch.clamp, and as optim.py clamps the parameters this kernel does not take: +-Inf become +-c and a NaN stays a NaN (fmaxf alone
+// returns its other operand, -c, and a diverged loss would go on training).
+__device__ __forceinline__ float clamp_grad(float g, float c) { return g != g ? g : fminf(fmaxf(g, -c), c); }
 
 template <bool CLAMP>
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {

@@ -25,7 +25,7 @@ class Adam(torch.optim.Adam):
         # new (no torch counterpart): every gradient element is clamped to +-grad_clamp, in place, before the step — the reference
         # learner's `param.grad.data.clamp_(-1, 1)` loop (policies/DDQN/ddqn.py:120-122) inside the a3vt_adam_step_clamp launch
         self.grad_clamp = None if grad_clamp is None else float(grad_clamp)
-        self._tables = {}        # group index -> (key, device tables)
+        self._tables = {}        # (group index, position of the step-count partition) -> (key, device tables)
         self.library_steps = 0   # steps taken by a3vt_adam_step (tests, bench)
 
     # -- the tensors of one group, state created as torch's _init_group does ------------------------------------------------------
@@ -56,9 +56,9 @@ class Adam(torch.optim.Adam):
             steps.append(st["step"])
         return ps, gs, ms, vs, steps
 
-    def _table(self, gi, ps, gs, ms, vs):
+    def _table(self, slot, ps, gs, ms, vs):
         key = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, g, m, v in zip(ps, gs, ms, vs))
-        hit = self._tables.get(gi)
+        hit = self._tables.get(slot)
         if hit is not None and hit[0] == key:
             return hit[1]
         L = _lib.load()
@@ -72,7 +72,7 @@ class Adam(torch.optim.Adam):
                 ct.append(t)
                 co.append(off)
         tabs = (ptrs.to(dev), numel.to(dev), torch.tensor(ct, dtype=torch.int32).to(dev), torch.tensor(co, dtype=torch.int64).to(dev), len(ct))
-        self._tables[gi] = (key, tabs)
+        self._tables[slot] = (key, tabs)
         return tabs
 
     @torch.no_grad()
@@ -113,12 +113,15 @@ class Adam(torch.optim.Adam):
                 for i, s in enumerate(steps):
                     by.setdefault(int(s.item()), []).append(i)
                 parts = [(c, [[x[i] for i in idx] for x in (ps, gs, ms, vs)]) for c, idx in sorted(by.items())]
-                self._tables.pop(gi, None)
             else:
                 parts = [(counts.pop(), [ps, gs, ms, vs])]
+            # a partition's tables are kept under its position, not its count (which rises every step): the next step finds them
+            # again, and a set that no longer matches is replaced where it lies
+            for slot in [k for k in self._tables if k[0] == gi and k[1] >= len(parts)]:
+                del self._tables[slot]
             beta1, beta2 = group["betas"]
-            for count, (p_, g_, m_, v_) in parts:
-                ptrs, numel, ct, co, n_chunks = self._table(gi if len(parts) == 1 else (gi, count), p_, g_, m_, v_)
+            for k, (count, (p_, g_, m_, v_)) in enumerate(parts):
+                ptrs, numel, ct, co, n_chunks = self._table((gi, k), p_, g_, m_, v_)
                 with torch.cuda.device(p_[0].device):
                     if self.grad_clamp is not None:
                         _lib.check(L.a3vt_adam_step_clamp(_lib.ptr(ptrs[0]), _lib.ptr(ptrs[1]), _lib.ptr(ptrs[2]), _lib.ptr(ptrs[3]),

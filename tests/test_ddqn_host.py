@@ -333,3 +333,22 @@ def test_adam_grad_clamp_on_parameters_the_kernel_does_not_take():
     assert torch.equal(p.grad, q.grad) and p.grad.abs().max() == 1.0 and torch.equal(p.data, q.data)
     with pytest.raises(ValueError):
         Adam([p], grad_clamp=0.0)
+
+
+def test_adam_grad_clamp_host_fallback_keeps_a_nan_gradient():
+    """The kernel's clamp and this one are pinned to the same rule (``torch.clamp``, test_gpu_adam.py::test_non_finite_gradients):
+    +-Inf become +-c, a NaN gradient stays NaN and makes that element of the parameter and of both moments NaN."""
+    from a3vt_amd.optim import Adam
+    torch.manual_seed(1)
+    p = torch.nn.Parameter(torch.randn(9))
+    before = p.detach().clone()
+    p.grad = torch.tensor([float("nan"), float("inf"), float("-inf"), 3.0, -3.0, 0.25, float("nan"), -0.5, 0.0])
+    opt = Adam([p], lr=1e-2, grad_clamp=1.0)
+    opt.step()
+    nan = torch.tensor([True, False, False, False, False, False, True, False, False])
+    assert torch.equal(torch.isnan(p.grad), nan)
+    assert p.grad[~nan].tolist() == [1.0, -1.0, 1.0, -1.0, 0.25, -0.5, 0.0]
+    for t in (p.detach(), opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"]):
+        assert torch.equal(torch.isnan(t), nan) and bool(torch.isfinite(t[~nan]).all())
+    # the first step from zero state moves a finite element by lr against its gradient's sign: +-Inf stepped as +-1
+    assert torch.allclose((before - p.detach())[1:5], 1e-2 * torch.tensor([1.0, -1.0, 1.0, -1.0]), rtol=1e-5, atol=0)
