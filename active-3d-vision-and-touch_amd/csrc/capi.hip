@@ -1304,6 +1304,40 @@ int a3vt_ddqn_td_bwd(const float *diff, const float *actions, const float *grad_
   return launch_ddqn_td_bwd(diff, actions, grad_loss, batch, num_actions, dq_cur, static_cast<hipStream_t>(stream));
 }
 
+// ---- the nearest-neighbour policy's bank lookup (latent_nn.hip) -----------------------------------------------------------------
+namespace {
+bool latent_dims_ok(int n_queries, int bank_rows, int k) {
+  return n_queries >= 1 && n_queries <= kLatentMaxQueries && bank_rows >= 1 && bank_rows <= kLatentMaxRows && k >= 1 && k <= kLatentMaxK;
+}
+}  // namespace
+
+size_t a3vt_latent_nearest_scratch_bytes(int n_queries, int bank_rows, int k) {
+  if (!latent_dims_ok(n_queries, bank_rows, k)) return 0;
+  return (size_t)n_queries * bank_rows * sizeof(float);
+}
+
+int a3vt_latent_nn_tile(void) { return kLatentTile; }
+int a3vt_latent_nn_query_floats(void) { return kLatentQueryFloats; }
+int a3vt_latent_nn_cached_rows(void) { return kLatentCachedRows; }
+
+int a3vt_latent_nearest(const float *bank, const int32_t *bank_actions, int bank_rows, int dim, const float *queries, const float *taken,
+                        int n_queries, int num_actions, int k, int32_t *idx, float *dist, int32_t *action, int32_t *rank, void *scratch,
+                        void *stream) {
+  if (!latent_dims_ok(n_queries, bank_rows, k) || dim < 1 || dim > kLatentMaxDim || num_actions < 1 || num_actions > kTdMaxActions) {
+    set_error("latent_nearest: bank_rows=%d (1..%d) dim=%d (1..%d) n_queries=%d (1..%d) num_actions=%d (1..%d) k=%d (1..%d) unsupported",
+              bank_rows, kLatentMaxRows, dim, kLatentMaxDim, n_queries, kLatentMaxQueries, num_actions, kTdMaxActions, k, kLatentMaxK);
+    return -1;
+  }
+  A3VT_CHECK_ARG(bank && queries && idx && dist && scratch);
+  A3VT_CHECK_ARG((bank_actions && action && rank) || (!bank_actions && !action && !rank));
+  const unsigned row_align = dim % 4 == 0 ? 16 : 4;   // (16-byte loads along dim when every row starts on one)
+  A3VT_CHECK_ARG(aligned_to(bank, row_align) && aligned_to(queries, row_align));
+  A3VT_CHECK_ARG(aligned_to(bank_actions, 4) && aligned_to(taken, 4) && aligned_to(idx, 4) && aligned_to(dist, 4) && aligned_to(action, 4) &&
+                 aligned_to(rank, 4) && aligned_to(scratch, 4));
+  return launch_latent_nearest(bank, bank_actions, bank_rows, dim, queries, taken, n_queries, num_actions, k, idx, dist, action, rank,
+                               scratch, static_cast<hipStream_t>(stream));
+}
+
 namespace {
 struct QnetLayout {
   size_t za, heavy, ga, dz, db_slab, slab, total;

@@ -373,6 +373,15 @@ int launch_ddqn_td(const float *q_cur, const float *q_next_online, const float *
 int launch_ddqn_td_bwd(const float *diff, const float *actions, const float *grad_loss, int batch, int num_actions, float *dq_cur,
                        hipStream_t s);
 
+// latent_nn.hip: the nearest-neighbour policy's bank lookup (policies/NearestNeighbor/train.py:114-137)
+constexpr int kLatentTile = 32;             // bank rows per workgroup of the distance kernel
+constexpr int kLatentQueryFloats = 8192;    // floats of queries a workgroup keeps in LDS at a time
+constexpr int kLatentCachedRows = 16384;    // largest bank the selection kernel holds in registers
+constexpr int kLatentMaxDim = 4096, kLatentMaxQueries = 1024, kLatentMaxK = 64, kLatentMaxRows = 1 << 24;
+int launch_latent_nearest(const float *bank, const int32_t *bank_actions, int bank_rows, int dim, const float *queries,
+                          const float *taken, int n_queries, int num_actions, int k, int32_t *idx, float *dist, int32_t *action,
+                          int32_t *rank, void *scratch, hipStream_t s);
+
 // qnet_input.hip: features + product of the DDQN graph model's layer 0 without the (B N) x 300 feature rows
 struct QnetArgs {
   const float *mesh;                  // [B][N][4]: x, y, z, mask token (0..3 as a float)

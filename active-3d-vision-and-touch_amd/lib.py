@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT_LIB: another build of the library (tools/asan_host.sh)
 SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "conv5f.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
-           "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip"]
+           "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip", "latent_nn.hip"]
 # Per-file extra flags (none at present; sample.hip / gcn_csr.hip rely on IEEE NaN semantics — the reference's NaN
 # scrubs, a3vt_check_finite — so fast-math style flags must never be applied globally).
 # chamfer.hip: keep the nearest-neighbour loop on scalar fp32 ops (the SLP vectoriser would re-pack it into v_pk_*_f32,
@@ -106,6 +106,11 @@ SIGNATURES = {
     "a3vt_fold_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "a3vt_ddqn_td": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
     "a3vt_ddqn_td_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "a3vt_latent_nearest_scratch_bytes": (_sz, [_i, _i, _i]),
+    "a3vt_latent_nearest": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "a3vt_latent_nn_tile": (_i, []),
+    "a3vt_latent_nn_query_floats": (_i, []),
+    "a3vt_latent_nn_cached_rows": (_i, []),
     "a3vt_qnet_input_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "a3vt_qnet_input_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "a3vt_qnet_input_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i,

@@ -1088,6 +1088,93 @@ def ddqn_td(q_cur, q_next_online, q_next_target, mask, actions, rewards, denom, 
     return DDQNTDFn.apply(q_cur, q_next_online.detach(), q_next_target.detach(), mask, actions, rewards, denom, budget, gamma)
 
 
+# csrc/kernels.h's kLatentTile / kLatentQueryFloats / kLatentCachedRows (a3vt_latent_nn_tile() and its neighbours return the
+# library's own; the tests choose their shapes around them): bank rows per workgroup of the distance kernel, floats of queries
+# kept in LDS at a time, the largest bank the selection holds in registers.
+LATENT_NN_TILE = 32
+LATENT_NN_QUERY_FLOATS = 8192
+LATENT_NN_CACHED_ROWS = 16384
+LATENT_NN_MAX = dict(dim=4096, n_queries=1024, k=64, bank_rows=1 << 24, num_actions=304)
+
+
+def _latent_nearest_check(bank, bank_actions, queries, taken, k):
+    """Shapes, dtypes and limits of ``latent_nearest`` (both forms) -> (M, D, E, A)."""
+    for t, name, dtype in ((bank, "bank", torch.float32), (queries, "queries", torch.float32), (taken, "taken", torch.float32),
+                           (bank_actions, "bank_actions", torch.int32)):
+        if t is None and name in ("taken", "bank_actions"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise RuntimeError(f"a3vt: latent_nearest `{name}` must be a {dtype} tensor")
+        if t.device != bank.device:
+            raise RuntimeError(f"a3vt: latent_nearest `{name}` is on {t.device}, the bank on {bank.device}")
+    if bank.dim() != 2 or queries.dim() != 2 or queries.shape[1] != bank.shape[1]:
+        raise RuntimeError(f"a3vt: latent_nearest wants bank (M, D) and queries (E, D), got {tuple(bank.shape)} and {tuple(queries.shape)}")
+    (M, D), E = bank.shape, queries.shape[0]
+    if bank_actions is not None and bank_actions.shape != (M,):
+        raise RuntimeError(f"a3vt: latent_nearest bank_actions must be ({M},), got {tuple(bank_actions.shape)}")
+    if taken is not None and (taken.dim() != 2 or taken.shape[0] != E):
+        raise RuntimeError(f"a3vt: latent_nearest taken must be ({E}, num_actions), got {tuple(taken.shape)}")
+    if taken is not None and bank_actions is None:
+        raise RuntimeError("a3vt: latent_nearest taken without bank_actions")
+    A = taken.shape[1] if taken is not None else LATENT_NN_MAX["num_actions"]     # (no mask: every action of the range qualifies)
+    lim = LATENT_NN_MAX
+    if not (1 <= D <= lim["dim"] and 1 <= E <= lim["n_queries"] and 1 <= int(k) <= lim["k"] and 1 <= M <= lim["bank_rows"]
+            and 1 <= A <= lim["num_actions"]):
+        raise RuntimeError(f"a3vt: latent_nearest bank_rows={M} dim={D} n_queries={E} num_actions={A} k={k} outside {lim}")
+    return M, D, E, A
+
+
+def _latent_nearest_torch(bank, bank_actions, queries, taken, k):
+    """The contract of ``a3vt_latent_nearest`` on torch ops (CPU tensors: the host tests, the policy without a GPU): a stable
+    sort by distance, so a tie goes to the lower row and NaN distances come last."""
+    M, D, E, A = _latent_nearest_check(bank, bank_actions, queries, taken, k)
+    k, k_eff = int(k), min(int(k), M)
+    d = ((bank.unsqueeze(0) - queries.unsqueeze(1)) ** 2).mean(dim=2)                     # (E, M)
+    sd, order = torch.sort(d, dim=1, stable=True)
+    idx = torch.full((E, k), -1, dtype=torch.int32, device=bank.device)
+    dist = torch.full((E, k), float("inf"), dtype=torch.float32, device=bank.device)
+    idx[:, :k_eff], dist[:, :k_eff] = order[:, :k_eff].to(torch.int32), sd[:, :k_eff]
+    if bank_actions is None:
+        return idx, dist, None, None
+    acts = bank_actions.long()[order[:, :k_eff]]                                          # (E, k_eff)
+    ok = (acts >= 0) & (acts < A)
+    if taken is not None:
+        ok &= taken.gather(1, acts.clamp(0, A - 1)) == 0
+    first = ok.int().argmax(dim=1)
+    found = ok.any(dim=1)
+    minus = torch.full((E,), -1, dtype=torch.int32, device=bank.device)
+    action = torch.where(found, acts.gather(1, first.unsqueeze(1)).squeeze(1).to(torch.int32), minus)
+    return idx, dist, action, torch.where(found, first.to(torch.int32), minus)
+
+
+def latent_nearest(bank, bank_actions, queries, taken, k):
+    """The nearest-neighbour policy's bank lookup (reference ``policies/NearestNeighbor/train.py:114-137``) ->
+    ``(idx (E, k) int32, dist (E, k), action (E,) int32, rank (E,) int32)``: per query the ``min(k, M)`` nearest rows of ``bank``
+    (M, D) by mean squared difference, nearest first, ties to the lower row, NaN last, padded with -1 / +inf; ``action`` is
+    ``bank_actions`` (M,) int32 of the first listed row whose action is inside ``taken``'s (E, A) columns and not taken
+    (``taken[e, a] == 0``), ``rank`` its position, both -1 when none qualifies.  ``taken`` None excludes nothing;
+    ``bank_actions`` None gives a pure k-nearest query (``action`` and ``rank`` are None).  GPU tensors run
+    ``a3vt_latent_nearest`` (csrc/latent_nn.hip: two launches, no host sync); CPU tensors take the same contract on torch ops."""
+    if not bank.is_cuda:
+        return _latent_nearest_torch(bank, bank_actions, queries, taken, k)
+    M, D, E, A = _latent_nearest_check(bank, bank_actions, queries, taken, k)
+    L = _lib.load()
+    bank, queries = bank.contiguous(), queries.contiguous()
+    bank_actions = None if bank_actions is None else bank_actions.contiguous()
+    taken = None if taken is None else taken.contiguous()
+    k, dev = int(k), bank.device
+    idx = torch.empty((E, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((E, k), dtype=torch.float32, device=dev)
+    action = rank = None
+    if bank_actions is not None:
+        action, rank = torch.empty(E, dtype=torch.int32, device=dev), torch.empty(E, dtype=torch.int32, device=dev)
+    scratch = workspace("latent_nn", L.a3vt_latent_nearest_scratch_bytes(E, M, k), dev)
+    _lib.check(L.a3vt_latent_nearest(_lib.ptr(bank), _lib.ptr(bank_actions), M, D, _lib.ptr(queries), _lib.ptr(taken), E, A, k,
+                                     _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(action), _lib.ptr(rank), _lib.ptr(scratch), _stream()),
+               "latent_nearest")
+    return idx, dist, action, rank
+
+
 class QnetInputFn(torch.autograd.Function):
     """Features + layer 0 of the DDQN graph model on ``a3vt_qnet_input_fwd/bwd`` (csrc/qnet_input.hip).  ``mesh`` (B, N, 4);
     the composites ``comp_s`` (B, npad), ``comp_t`` (4, npad), ``comp_c`` (50, npad) come padded to npad = pad4(h) columns."""

@@ -515,6 +515,36 @@ int a3vt_ddqn_td(const float *q_cur, const float *q_next_online, const float *q_
 int a3vt_ddqn_td_bwd(const float *diff, const float *actions, const float *grad_loss, int batch, int num_actions, float *dq_cur,
                      void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The nearest-neighbour latent policy's bank lookup (policies/NearestNeighbor/train.py:114-137).
+ *
+ * a3vt_latent_nearest: for each of n_queries latents the k nearest rows of a bank, and the action of the first of them that has not
+ * been taken.  bank [bank_rows][dim] fp32, contiguous; queries [n_queries][dim]; taken [n_queries][num_actions] fp32, non-zero = the
+ * action was already performed (the environment's obs["mask"] as it is), NULL excludes nothing; bank_actions [bank_rows] int32, NULL
+ * only together with action and rank (a pure k-nearest query).
+ * Distance: d(e, j) = (1 / dim) * sum_c (bank[j][c] - queries[e][c])^2 in fp32.  The order of operations of one (query, row) pair is
+ * fixed and depends neither on the row's position, bank_rows, n_queries nor the query's position: bit-identical rows have
+ * bit-identical distances, and a query's results do not change bit-wise when other queries or farther rows are added.
+ * Outputs: idx, dist [n_queries][k] hold the k_eff = min(k, bank_rows) nearest rows, nearest first; a tie goes to the LOWER row
+ * index; a NaN distance ranks after every number, +inf included (as torch.topk(largest=False) ranks it); entries from k_eff on are
+ * -1 and +inf.  action[e] = bank_actions of the first listed row whose action a lies in [0, num_actions) and has taken[e][a] == 0,
+ * rank[e] its position in the list; both -1 when no listed row qualifies.  A bank action outside the range never qualifies and
+ * never indexes taken.
+ * Limits: 1 <= dim <= 4096, 1 <= n_queries <= 1024, 1 <= k <= 64, 1 <= bank_rows <= 2^24, 1 <= num_actions <= 304.  Anything else,
+ * a null required pointer, a null scratch (a3vt_latent_nearest_scratch_bytes bytes; 0 for unsupported sizes) or a misaligned pointer
+ * (bank and queries: 16 bytes when dim % 4 == 0; everything else 4) returns non-zero with a message in a3vt_last_error and launches
+ * nothing.  Two kernel launches on `stream`; no host synchronisation, no allocation, no float atomics: the same bits on every call.
+ * A bank of more than a3vt_latent_nn_cached_rows() rows is selected from the scratch rather than from registers: a thread whose key
+ * was taken reads its share of the query's distances again.  a3vt_latent_nn_tile(): bank rows per workgroup; a3vt_latent_nn_query_floats(): floats of queries held in
+ * LDS at a time (queries are processed in chunks of that / dim). */
+size_t a3vt_latent_nearest_scratch_bytes(int n_queries, int bank_rows, int k);
+int a3vt_latent_nearest(const float *bank, const int32_t *bank_actions, int bank_rows, int dim, const float *queries, const float *taken,
+                        int n_queries, int num_actions, int k, int32_t *idx, float *dist, int32_t *action, int32_t *rank, void *scratch,
+                        void *stream);
+int a3vt_latent_nn_tile(void);
+int a3vt_latent_nn_query_floats(void);
+int a3vt_latent_nn_cached_rows(void);
+
 /* Graph_Model's features and layer 0 (policies/DDQN/model.py:100-118) without the (batch * n_vert) x 300 feature rows:
  *   y = relu(layer0([a_b | PE(p) | E[token]])) = relu(agg(S[b] + T[token] + relu(L2(relu(L1(nerf(p) ++ p)))) C))
  * with the composites S = a Wa + b3 Wp [batch][npad], T = E Wm [4][npad], C = W3^T Wp [50][npad] formed by the caller
