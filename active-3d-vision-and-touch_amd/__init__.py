@@ -40,10 +40,12 @@ def install_as_pterotactyl():
         "pterotactyl.policies.baselines.baselines": ".pterotactyl.policies.baselines.baselines",
         "pterotactyl.policies.replay": ".pterotactyl.policies.replay",
         "pterotactyl.policies.DDQN.ddqn": ".pterotactyl.policies.DDQN.ddqn",
+        "pterotactyl.policies.supervised.model": ".pterotactyl.policies.supervised.model",
+        "pterotactyl.policies.supervised.train": ".pterotactyl.policies.supervised.train",
     }
     for parent in ("pterotactyl", "pterotactyl.reconstruction", "pterotactyl.reconstruction.vision",
                    "pterotactyl.reconstruction.autoencoder", "pterotactyl.policies", "pterotactyl.policies.DDQN",
-                   "pterotactyl.policies.baselines",
+                   "pterotactyl.policies.baselines", "pterotactyl.policies.supervised",
                    "pterotactyl.utility"):
         if parent not in sys.modules:
             try:

@@ -1338,6 +1338,122 @@ int a3vt_latent_nearest(const float *bank, const int32_t *bank_actions, int bank
                                scratch, static_cast<hipStream_t>(stream));
 }
 
+// ---- the supervised latent policy's value network (latent_policy.hip) ------------------------------------------------------------
+namespace {
+static_assert(sizeof(a3vt_mlp) == sizeof(PolicyNet) && sizeof(a3vt_mlp_layer) == sizeof(PolicyLayer) &&
+                  sizeof(a3vt_mlp_grads) == sizeof(PolicyGrads) && offsetof(a3vt_mlp, n_layers) == offsetof(PolicyNet, n_layers) &&
+                  offsetof(a3vt_mlp, scale) == offsetof(PolicyNet, scale) && offsetof(a3vt_mlp_layer, in) == offsetof(PolicyLayer, in),
+              "a3vt_mlp is PolicyNet field for field");
+std::atomic<long long> g_policy_launches[3];
+
+// The table's own rules -> floats of a stash row (the sum of the layers' out), or -1 with the message set.
+int policy_net_check(const char *who, const a3vt_mlp *net) {
+  if (!net) {
+    set_error("%s: net is null", who);
+    return -1;
+  }
+  if (net->n_layers < 2 || net->n_layers > kPolicyMaxLayers || net->concat_at < 1 || net->concat_at >= net->n_layers ||
+      net->latent_size < 1 || 3 * (long long)net->latent_size > kPolicyMaxWidth || (net->transform != 0 && net->transform != 1)) {
+    set_error("%s: n_layers=%d (2..%d) concat_at=%d (1..n_layers-1) latent_size=%d (3*latent_size <= %d) transform=%d (0, 1) unsupported",
+              who, net->n_layers, kPolicyMaxLayers, net->concat_at, net->latent_size, kPolicyMaxWidth, net->transform);
+    return -1;
+  }
+  int total = 0;
+  for (int l = 0; l < net->n_layers; ++l) {
+    const a3vt_mlp_layer &L = net->layer[l];
+    if (L.in < 1 || L.in > kPolicyMaxWidth || L.out < 1 || L.out > kPolicyMaxWidth) {
+      set_error("%s: layer %d in=%d out=%d outside 1..%d", who, l, L.in, L.out, kPolicyMaxWidth);
+      return -1;
+    }
+    const int want = l == 0 ? L.in : net->layer[l - 1].out + (l == net->concat_at ? 2 * net->latent_size : 0);
+    if (L.in != want) {
+      set_error("%s: layer %d in=%d does not chain (the rows before it give %d)", who, l, L.in, want);
+      return -1;
+    }
+    if (!L.weight || !L.bias || !aligned_to(L.weight, L.in % 4 == 0 ? 16 : 4) || !aligned_to(L.bias, 4)) {
+      set_error("%s: layer %d weight / bias null or misaligned (weight: %d bytes)", who, l, L.in % 4 == 0 ? 16 : 4);
+      return -1;
+    }
+    total += L.out;
+  }
+  return total;
+}
+bool policy_rows_ok(const char *who, const char *name, int v) {
+  if (v >= 1 && v <= kPolicyMaxRows) return true;
+  set_error("%s: %s=%d (1..%d) unsupported", who, name, v, kPolicyMaxRows);
+  return false;
+}
+PolicyNet policy_net_of(const a3vt_mlp *net) {
+  PolicyNet n;
+  memcpy(&n, net, sizeof(n));
+  return n;
+}
+}  // namespace
+
+int a3vt_latent_policy_limit(int which) {
+  return which == 0 ? kPolicyMaxRows : which == 1 ? kPolicyMaxWidth : which == 2 ? kPolicyMaxLayers : 0;
+}
+
+int a3vt_latent_policy_stash_floats(const a3vt_mlp *net) {
+  const int total = policy_net_check("latent_policy_stash_floats", net);
+  return total < 0 ? 0 : total;
+}
+
+int a3vt_latent_policy_fwd(const a3vt_mlp *net, const float *mask, const float *latent, const float *first_latent, const float *taken,
+                           int rows, float *values, int32_t *action, float *stash, void *stream) {
+  const int ld = policy_net_check("latent_policy_fwd", net);
+  if (ld < 0 || !policy_rows_ok("latent_policy_fwd", "rows", rows)) return -1;
+  A3VT_CHECK_ARG(mask && latent && first_latent && values);
+  A3VT_CHECK_ARG((taken && action) || (!taken && !action));
+  A3VT_CHECK_ARG(aligned_to(mask, 4) && aligned_to(latent, 4) && aligned_to(first_latent, 4) && aligned_to(taken, 4) &&
+                 aligned_to(values, 4) && aligned_to(action, 4) && aligned_to(stash, 4));
+  g_policy_launches[0].fetch_add(1, std::memory_order_relaxed);
+  return launch_policy_fwd(policy_net_of(net), mask, latent, first_latent, taken, rows, values, action, stash, ld,
+                           static_cast<hipStream_t>(stream));
+}
+
+int a3vt_action_value_loss(const float *values, const int32_t *actions, const float *targets, int steps, int rows, int num_actions,
+                           float *loss, float *dvalues, void *stream) {
+  if (!policy_rows_ok("action_value_loss", "steps", steps) || !policy_rows_ok("action_value_loss", "rows", rows)) return -1;
+  if (num_actions < 1 || num_actions > kPolicyMaxWidth) {
+    set_error("action_value_loss: num_actions=%d (1..%d) unsupported", num_actions, kPolicyMaxWidth);
+    return -1;
+  }
+  A3VT_CHECK_ARG(values && actions && targets && loss && dvalues);
+  A3VT_CHECK_ARG(aligned_to(values, 4) && aligned_to(actions, 4) && aligned_to(targets, 4) && aligned_to(loss, 4) && aligned_to(dvalues, 4));
+  g_policy_launches[1].fetch_add(1, std::memory_order_relaxed);
+  return launch_action_value_loss(values, actions, targets, steps, rows, num_actions, loss, dvalues, static_cast<hipStream_t>(stream));
+}
+
+int a3vt_latent_policy_bwd(const a3vt_mlp *net, const a3vt_mlp_grads *grads, const float *mask, const float *latent,
+                           const float *first_latent, const float *dvalues, const float *stash, float *delta, int rows, int accumulate,
+                           void *stream) {
+  const int ld = policy_net_check("latent_policy_bwd", net);
+  if (ld < 0 || !policy_rows_ok("latent_policy_bwd", "rows", rows)) return -1;
+  A3VT_CHECK_ARG(grads && mask && latent && first_latent && dvalues && stash && delta);
+  A3VT_CHECK_ARG(aligned_to(mask, 4) && aligned_to(latent, 4) && aligned_to(first_latent, 4) && aligned_to(dvalues, 4) &&
+                 aligned_to(stash, 4) && aligned_to(delta, 4));
+  PolicyGrads g;
+  memcpy(&g, grads, sizeof(g));
+  for (int l = 0; l < net->n_layers; ++l) {
+    if (!g.dw[l] || !g.db[l] || !aligned_to(g.dw[l], 4) || !aligned_to(g.db[l], 4)) {
+      set_error("latent_policy_bwd: layer %d dweight / dbias null or misaligned", l);
+      return -1;
+    }
+  }
+  g_policy_launches[2].fetch_add(2, std::memory_order_relaxed);
+  return launch_policy_bwd(policy_net_of(net), g, mask, latent, first_latent, dvalues, stash, delta, rows, ld, accumulate ? 1 : 0,
+                           static_cast<hipStream_t>(stream));
+}
+
+int a3vt_latent_policy_launches(long long *counts, int reset) {
+  for (int i = 0; i < 3; ++i) {
+    if (counts) counts[i] = g_policy_launches[i].load(std::memory_order_relaxed);
+    if (reset) g_policy_launches[i].store(0, std::memory_order_relaxed);
+  }
+  return 3;
+}
+
 namespace {
 struct QnetLayout {
   size_t za, heavy, ga, dz, db_slab, slab, total;

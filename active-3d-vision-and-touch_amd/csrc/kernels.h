@@ -382,6 +382,31 @@ int launch_latent_nearest(const float *bank, const int32_t *bank_actions, int ba
                           const float *taken, int n_queries, int num_actions, int k, int32_t *idx, float *dist, int32_t *action,
                           int32_t *rank, void *scratch, hipStream_t s);
 
+// latent_policy.hip: the supervised policy's value network (policies/supervised/model.py), its loss and its backward.  The layer
+// table travels by value in the kernel arguments (a3vt_mlp of include/a3vt.h, field for field).
+constexpr int kPolicyMaxLayers = 16;     // layers of a table
+constexpr int kPolicyMaxWidth = 1024;    // every layer's in and out (so 2 * latent_size + the action embedding too): one LDS row
+constexpr int kPolicyMaxRows = 4096;     // E, and T of the loss
+constexpr int kPolicySlab = 8;           // output rows of a layer per workgroup of the gradient kernel
+struct PolicyLayer {
+  const float *w, *b;   // [out][in] (torch's layout), [out]
+  int32_t in, out, relu, reserved;
+};
+struct PolicyNet {
+  PolicyLayer layer[kPolicyMaxLayers];
+  int32_t n_layers, concat_at, latent_size, transform;   // transform: 0 none, 1 sigmoid(z) * scale - offset
+  float scale, offset;
+};
+struct PolicyGrads {
+  float *dw[kPolicyMaxLayers], *db[kPolicyMaxLayers];
+};
+int launch_policy_fwd(const PolicyNet &net, const float *mask, const float *latent, const float *first_latent, const float *taken,
+                      int rows, float *values, int32_t *action, float *stash, int ld, hipStream_t s);
+int launch_action_value_loss(const float *values, const int32_t *actions, const float *targets, int steps, int rows, int num_actions,
+                             float *loss, float *dvalues, hipStream_t s);
+int launch_policy_bwd(const PolicyNet &net, const PolicyGrads &grads, const float *mask, const float *latent, const float *first_latent,
+                      const float *dvalues, const float *stash, float *delta, int rows, int ld, int accumulate, hipStream_t s);
+
 // qnet_input.hip: features + product of the DDQN graph model's layer 0 without the (B N) x 300 feature rows
 struct QnetArgs {
   const float *mesh;                  // [B][N][4]: x, y, z, mask token (0..3 as a float)

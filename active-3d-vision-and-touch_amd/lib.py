@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT_LIB: another build of the library (tools/asan_host.sh)
 SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "conv5f.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
-           "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip", "latent_nn.hip"]
+           "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip", "latent_nn.hip", "latent_policy.hip"]
 # Per-file extra flags (none at present; sample.hip / gcn_csr.hip rely on IEEE NaN semantics — the reference's NaN
 # scrubs, a3vt_check_finite — so fast-math style flags must never be applied globally).
 # chamfer.hip: keep the nearest-neighbour loop on scalar fp32 ops (the SLP vectoriser would re-pack it into v_pk_*_f32,
@@ -28,6 +28,23 @@ class AdjSplit(ctypes.Structure):
     """``a3vt_adj_split`` (include/a3vt.h): the fused vision + touch adjacency as P + a complete bipartite block."""
     _fields_ = [("rowptr", _vp), ("col", _vp), ("scale", _vp), ("cls", _vp),
                 ("max_degree", ctypes.c_int32), ("n_seam", ctypes.c_int32), ("n_centre", ctypes.c_int32)]
+
+
+class MlpLayer(ctypes.Structure):
+    """``a3vt_mlp_layer`` (include/a3vt.h): one Linear of a layer table, weight in torch's [out][in] layout."""
+    _fields_ = [("weight", _vp), ("bias", _vp), ("n_in", ctypes.c_int32), ("n_out", ctypes.c_int32), ("relu", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class Mlp(ctypes.Structure):
+    """``a3vt_mlp``: the layer table of ``a3vt_latent_policy_fwd`` / ``_bwd``."""
+    _fields_ = [("layer", MlpLayer * 16), ("n_layers", ctypes.c_int32), ("concat_at", ctypes.c_int32), ("latent_size", ctypes.c_int32),
+                ("transform", ctypes.c_int32), ("scale", ctypes.c_float), ("offset", ctypes.c_float)]
+
+
+class MlpGrads(ctypes.Structure):
+    """``a3vt_mlp_grads``: where ``a3vt_latent_policy_bwd`` writes (or adds) each layer's gradients."""
+    _fields_ = [("dweight", _vp * 16), ("dbias", _vp * 16)]
 
 
 # name -> (restype, argtypes); mirrors include/a3vt.h one to one.
@@ -111,6 +128,12 @@ SIGNATURES = {
     "a3vt_latent_nn_tile": (_i, []),
     "a3vt_latent_nn_query_floats": (_i, []),
     "a3vt_latent_nn_cached_rows": (_i, []),
+    "a3vt_latent_policy_limit": (_i, [_i]),
+    "a3vt_latent_policy_stash_floats": (_i, [_vp]),
+    "a3vt_latent_policy_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "a3vt_action_value_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "a3vt_latent_policy_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "a3vt_latent_policy_launches": (_i, [_vp, _i]),
     "a3vt_qnet_input_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "a3vt_qnet_input_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "a3vt_qnet_input_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i,

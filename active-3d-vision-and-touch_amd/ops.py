@@ -1175,6 +1175,272 @@ def latent_nearest(bank, bank_actions, queries, taken, k):
     return idx, dist, action, rank
 
 
+# csrc/kernels.h's kPolicyMaxRows / kPolicyMaxWidth / kPolicyMaxLayers (a3vt_latent_policy_limit returns the library's own): rows
+# of a call (and steps of the loss), every layer's in and out, layers of a table.
+LATENT_POLICY_MAX = dict(rows=4096, width=1024, layers=16)
+
+
+def policy_launches(reset=False):
+    """Kernel launches of ``a3vt_latent_policy_fwd`` / ``a3vt_action_value_loss`` / ``a3vt_latent_policy_bwd`` since the last
+    reset (a test hook, as ``path_counts``)."""
+    buf = (ctypes.c_longlong * 3)()
+    _lib.load().a3vt_latent_policy_launches(buf, 1 if reset else 0)
+    return dict(zip(("fwd", "loss", "bwd"), (int(x) for x in buf)))
+
+
+class PolicyTable:
+    """The layer table of ``latent_policy``: ``layers`` = [(weight (out, in), bias (out,), relu), ..] in evaluation order, the
+    input of layer ``concat_at`` being cat(previous output, latent, first_latent); ``transform`` None (the last layer's output as
+    it is) or ``(scale, offset)`` for ``sigmoid(z) * scale - offset``.  The tensors are used in place; ``struct()`` is the
+    ``a3vt_mlp`` of their current addresses."""
+
+    def __init__(self, layers, concat_at, transform=None):
+        self.layers = [(w, b, bool(r)) for w, b, r in layers]
+        self.concat_at = int(concat_at)
+        self.transform = None if transform is None else (float(transform[0]), float(transform[1]))
+        if not self.layers:
+            raise RuntimeError("a3vt: latent_policy wants at least one layer")
+        for l, (w, b, _) in enumerate(self.layers):
+            if not (isinstance(w, torch.Tensor) and isinstance(b, torch.Tensor) and w.dim() == 2 and b.shape == (w.shape[0],)):
+                raise RuntimeError(f"a3vt: latent_policy layer {l} wants weight (out, in) and bias (out,)")
+        if not 1 <= self.concat_at < len(self.layers):
+            raise RuntimeError(f"a3vt: latent_policy concat_at={self.concat_at} outside 1..{len(self.layers) - 1}")
+        extra = self.layers[self.concat_at][0].shape[1] - self.layers[self.concat_at - 1][0].shape[0]
+        if extra < 2 or extra % 2:
+            raise RuntimeError(f"a3vt: latent_policy layer {self.concat_at} takes {extra} columns beside the previous output, not 2 * latent_size")
+        self.latent_size = extra // 2
+        for l in range(1, len(self.layers)):
+            want = self.layers[l - 1][0].shape[0] + (extra if l == self.concat_at else 0)
+            if self.layers[l][0].shape[1] != want:
+                raise RuntimeError(f"a3vt: latent_policy layer {l} in={self.layers[l][0].shape[1]} does not chain (the rows before it give {want})")
+        self.in_width, self.num_actions = self.layers[0][0].shape[1], self.layers[-1][0].shape[0]
+        self.stash_floats = sum(w.shape[0] for w, _, _ in self.layers)
+        self._key, self._struct = None, None
+
+    def params(self):
+        return [t for w, b, _ in self.layers for t in (w, b)]
+
+    def in_limits(self):
+        """Whether the kernels take this table: fp32 contiguous parameters on one GPU, sizes inside ``LATENT_POLICY_MAX``,
+        weight rows on 16-byte boundaries where the kernel loads them so."""
+        lim = LATENT_POLICY_MAX
+        dev = self.layers[0][0].device
+        if len(self.layers) > lim["layers"] or len(self.layers) < 2 or 3 * self.latent_size > lim["width"]:
+            return False
+        for w, b, _ in self.layers:
+            if not (w.is_cuda and w.device == dev and b.device == dev and w.dtype == torch.float32 and b.dtype == torch.float32
+                    and w.is_contiguous() and b.is_contiguous() and max(w.shape) <= lim["width"]
+                    and w.data_ptr() % (16 if w.shape[1] % 4 == 0 else 4) == 0):
+                return False
+        return True
+
+    def struct(self):
+        key = tuple(t.data_ptr() for t in self.params())
+        if key != self._key:
+            m = _lib.Mlp()
+            for l, (w, b, relu) in enumerate(self.layers):
+                m.layer[l] = _lib.MlpLayer(w.data_ptr(), b.data_ptr(), w.shape[1], w.shape[0], 1 if relu else 0, 0)
+            m.n_layers, m.concat_at, m.latent_size = len(self.layers), self.concat_at, self.latent_size
+            m.transform = 0 if self.transform is None else 1
+            m.scale, m.offset = self.transform or (1.0, 0.0)
+            self._key, self._struct = key, m
+        return self._struct
+
+
+def _policy_inputs(table, mask, latent, first_latent, taken):
+    """Shapes and dtypes of a ``latent_policy`` call (both forms) -> E."""
+    for t, name in ((mask, "mask"), (latent, "latent"), (first_latent, "first_latent"), (taken, "taken")):
+        if t is None and name == "taken":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2:
+            raise RuntimeError(f"a3vt: latent_policy `{name}` must be a 2-d torch.float32 tensor")
+        if t.device != mask.device:
+            raise RuntimeError(f"a3vt: latent_policy `{name}` is on {t.device}, the mask on {mask.device}")
+    E = mask.shape[0]
+    if mask.shape != (E, table.in_width) or latent.shape != (E, table.latent_size) or first_latent.shape != (E, table.latent_size):
+        raise RuntimeError(f"a3vt: latent_policy wants mask ({E}, {table.in_width}) and latents ({E}, {table.latent_size}), got "
+                           f"{tuple(mask.shape)}, {tuple(latent.shape)}, {tuple(first_latent.shape)}")
+    if taken is not None and taken.shape != (E, table.num_actions):
+        raise RuntimeError(f"a3vt: latent_policy taken must be ({E}, {table.num_actions}), got {tuple(taken.shape)}")
+    if E < 1:
+        raise RuntimeError("a3vt: latent_policy rows=0")
+    return E
+
+
+def policy_supported(table, mask):
+    """Whether ``latent_policy`` runs the kernels for these operands (else the torch form of the same contract runs)."""
+    return bool(mask.is_cuda and table.in_limits() and table.layers[0][0].device == mask.device
+                and 1 <= mask.shape[0] <= LATENT_POLICY_MAX["rows"])
+
+
+def choose_action_torch(values, taken):
+    """The action choice of ``a3vt_latent_policy_fwd`` on torch ops: per row the lowest value among ``taken == 0``, a tie to
+    the lower index, NaN after +inf, -1 when nothing is open -> (E,) int32."""
+    order = torch.sort(values.detach(), dim=1, stable=True).indices       # (ascending, NaN last, equal values keep their order)
+    ok = (taken == 0).gather(1, order)
+    first = ok.int().argmax(dim=1, keepdim=True)
+    chosen = order.gather(1, first).squeeze(1).to(torch.int32)
+    return torch.where(ok.any(dim=1), chosen, torch.full_like(chosen, -1))
+
+
+def _latent_policy_torch(table, mask, latent, first_latent, taken):
+    """The contract of ``a3vt_latent_policy_fwd`` on torch ops (CPU tensors, tables outside the kernel's limits)."""
+    _policy_inputs(table, mask, latent, first_latent, taken)
+    x = mask
+    for l, (w, b, relu) in enumerate(table.layers):
+        if l == table.concat_at:
+            x = torch.cat((x, latent, first_latent), dim=-1)
+        x = torch.nn.functional.linear(x, w, b)
+        if relu:
+            x = torch.relu(x)
+    if table.transform is not None:
+        x = torch.sigmoid(x) * table.transform[0] - table.transform[1]
+    return x, (None if taken is None else choose_action_torch(x, taken))
+
+
+def latent_policy_fwd(table, mask, latent, first_latent, taken=None, stash=False):
+    """One ``a3vt_latent_policy_fwd`` launch, outside autograd -> (values (E, A), action (E,) int32 or None, stash or None)."""
+    E = _policy_inputs(table, mask, latent, first_latent, taken)
+    L = _lib.load()
+    mask, latent, first_latent = _req(mask, "mask"), _req(latent, "latent"), _req(first_latent, "first_latent")
+    taken = None if taken is None else _req(taken, "taken")
+    dev = mask.device
+    values = torch.empty((E, table.num_actions), dtype=torch.float32, device=dev)
+    action = None if taken is None else torch.empty(E, dtype=torch.int32, device=dev)
+    kept = torch.empty((E, table.stash_floats), dtype=torch.float32, device=dev) if stash else None
+    _lib.check(L.a3vt_latent_policy_fwd(ctypes.byref(table.struct()), _lib.ptr(mask), _lib.ptr(latent), _lib.ptr(first_latent),
+                                        _lib.ptr(taken), E, _lib.ptr(values), _lib.ptr(action), _lib.ptr(kept), _stream()),
+               "latent_policy_fwd")
+    return values, action, kept
+
+
+def latent_policy_bwd(table, mask, latent, first_latent, dvalues, stash, grads, accumulate):
+    """The two ``a3vt_latent_policy_bwd`` launches: ``grads`` = [(dweight, dbias), ..] per layer, written (``accumulate`` False)
+    or added to (True) in place."""
+    E = _policy_inputs(table, mask, latent, first_latent, None)
+    L = _lib.load()
+    mask, latent, first_latent = _req(mask, "mask"), _req(latent, "latent"), _req(first_latent, "first_latent")
+    dvalues, stash = _req(dvalues, "dvalues"), _req(stash, "stash")
+    if dvalues.shape != (E, table.num_actions) or stash.shape != (E, table.stash_floats) or len(grads) != len(table.layers):
+        raise RuntimeError("a3vt: latent_policy_bwd operand shapes disagree")
+    g = _lib.MlpGrads()
+    for l, ((dw, db), (w, b, _)) in enumerate(zip(grads, table.layers)):
+        dw, db = _req(dw, "dweight"), _req(db, "dbias")
+        if dw.shape != w.shape or db.shape != b.shape or dw.data_ptr() != grads[l][0].data_ptr() or db.data_ptr() != grads[l][1].data_ptr():
+            raise RuntimeError(f"a3vt: latent_policy_bwd gradient {l} must be contiguous and of its parameter's shape")
+        g.dweight[l], g.dbias[l] = dw.data_ptr(), db.data_ptr()
+    delta = workspace("latent_policy_delta", E * table.stash_floats * 4, mask.device)
+    _lib.check(L.a3vt_latent_policy_bwd(ctypes.byref(table.struct()), ctypes.byref(g), _lib.ptr(mask), _lib.ptr(latent),
+                                        _lib.ptr(first_latent), _lib.ptr(dvalues), _lib.ptr(stash), _lib.ptr(delta), E,
+                                        1 if accumulate else 0, _stream()), "latent_policy_bwd")
+
+
+class LatentPolicyFn(torch.autograd.Function):
+    """``latent_policy`` under autograd: the forward launch keeps the stash, the backward's two launches write fresh gradient
+    tensors (accumulate off).  Only the parameters carry gradients."""
+
+    @staticmethod
+    def forward(ctx, table, mask, latent, first_latent, taken, need_bwd, *params):
+        values, action, kept = latent_policy_fwd(table, mask, latent, first_latent, taken, stash=need_bwd)
+        if need_bwd:
+            ctx.table = table
+            ctx.save_for_backward(mask, latent, first_latent, kept)
+        if action is None:
+            action = torch.empty(0, dtype=torch.int32, device=values.device)
+        ctx.mark_non_differentiable(action)
+        return values, action
+
+    @staticmethod
+    def backward(ctx, dvalues, _daction):
+        mask, latent, first_latent, kept = ctx.saved_tensors
+        table = ctx.table
+        grads = [(torch.empty_like(w), torch.empty_like(b)) for w, b, _ in table.layers]
+        latent_policy_bwd(table, mask, latent, first_latent, dvalues.contiguous(), kept, grads, accumulate=False)
+        return (None,) * 6 + tuple(t for pair in grads for t in pair)
+
+
+def latent_policy(table, mask, latent, first_latent, taken=None):
+    """The value network of the supervised policy (reference ``policies/supervised/model.py:46-58`` and the masking loop of
+    ``train.py:119-128``) -> ``(values (E, A), action (E,) int32 or None)``: ``table`` (a ``PolicyTable``) applied to ``mask``
+    (E, in), the concat with ``latent`` / ``first_latent`` (E, latent_size), the output transform; with ``taken`` (E, A) also the
+    index of the lowest value among ``taken == 0`` (tie: lower index; NaN after +inf; -1 when none is open).  GPU operands inside
+    ``LATENT_POLICY_MAX`` run ``a3vt_latent_policy_fwd`` (csrc/latent_policy.hip: one launch; under autograd the backward is two);
+    everything else takes the same contract on torch ops.  There are no gradients for mask, latent or first_latent."""
+    if not policy_supported(table, mask):
+        return _latent_policy_torch(table, mask, latent, first_latent, taken)
+    params = table.params()
+    values, action = LatentPolicyFn.apply(table, mask, latent, first_latent, taken, _wants_grad(*params), *params)
+    return values, (None if taken is None else action)
+
+
+def _action_value_check(values, actions, targets):
+    """Shapes, dtypes and the action range of ``action_value_loss`` (both forms) -> (actions on the values' device, T, E, A).
+    ``actions`` on the host (a NumPy array or a CPU tensor) are checked there; on the GPU the check costs a host sync."""
+    if isinstance(actions, np.ndarray):
+        actions = torch.from_numpy(np.ascontiguousarray(actions))
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() != 2:
+        raise RuntimeError("a3vt: action_value_loss `values` must be a 2-d torch.float32 tensor")
+    if not isinstance(targets, torch.Tensor) or targets.dtype != torch.float32 or targets.device != values.device:
+        raise RuntimeError("a3vt: action_value_loss `targets` must be a torch.float32 tensor on the values' device")
+    if not isinstance(actions, torch.Tensor) or actions.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("a3vt: action_value_loss `actions` must be an int32 / int64 tensor or array")
+    E, A = values.shape
+    if actions.dim() != 2 or actions.shape[1] != E or targets.shape != actions.shape or actions.shape[0] < 1 or E < 1:
+        raise RuntimeError(f"a3vt: action_value_loss wants actions and targets (T, {E}), got {tuple(actions.shape)} and {tuple(targets.shape)}")
+    if bool(((actions < 0) | (actions >= A)).any()):
+        raise RuntimeError(f"a3vt: action_value_loss actions outside [0, {A})")
+    lim = LATENT_POLICY_MAX
+    if actions.shape[0] > lim["rows"] or E > lim["rows"] or A > lim["width"]:
+        raise RuntimeError(f"a3vt: action_value_loss steps={actions.shape[0]} rows={E} num_actions={A} outside {lim}")
+    return actions.to(values.device, torch.int32).contiguous(), actions.shape[0], E, A
+
+
+def _action_value_loss_torch(values, actions, targets):
+    """The contract of ``a3vt_action_value_loss`` on torch ops -> (loss, dvalues); ``loss`` carries autograd."""
+    actions, T, E, A = _action_value_check(values, actions, targets)
+    idx = actions.long()
+    pred = values.gather(1, idx.t()).t()                                     # (T, E): values[e][actions[t][e]]
+    loss = ((targets - pred) ** 2).mean()
+    with torch.no_grad():
+        dvalues = torch.zeros_like(values)
+        for t in range(T):                                                   # (repeated pairs add up in t order)
+            dvalues.scatter_add_(1, idx[t].unsqueeze(1), ((pred[t] - targets[t]) * (2.0 / (T * E))).unsqueeze(1))
+    return loss, dvalues
+
+
+class ActionValueLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, actions, targets):
+        L = _lib.load()
+        T, E = actions.shape
+        values, targets = _req(values, "values"), _req(targets, "targets")
+        loss = torch.empty((), dtype=torch.float32, device=values.device)
+        dvalues = torch.empty_like(values)
+        _lib.check(L.a3vt_action_value_loss(_lib.ptr(values), _lib.ptr(actions), _lib.ptr(targets), T, E, values.shape[1], _lib.ptr(loss),
+                                            _lib.ptr(dvalues), _stream()), "action_value_loss")
+        ctx.save_for_backward(dvalues)
+        ctx.mark_non_differentiable(dvalues)
+        return loss, dvalues
+
+    @staticmethod
+    def backward(ctx, gloss, _gd):
+        (dvalues,) = ctx.saved_tensors
+        return gloss * dvalues, None, None
+
+
+def action_value_loss(values, actions, targets):
+    """The supervised trainer's loss (reference ``policies/supervised/train.py:148-155``) -> ``(loss, dvalues)``:
+    ``loss = mean_{t,e} (targets[t][e] - values[e][actions[t][e]])^2`` for ``values`` (E, A), ``actions`` (T, E) integers and
+    ``targets`` (T, E), and ``dvalues`` (E, A) its gradient, repeated (e, a) pairs added in t order.  An action outside [0, A) is
+    refused (checked on the host: hand ``actions`` over as a NumPy array or CPU tensor to keep the device queue running).
+    GPU values run ``a3vt_action_value_loss`` (one launch); CPU values take the same contract on torch ops.  ``loss`` carries
+    autograd towards ``values``."""
+    if not values.is_cuda:
+        return _action_value_loss_torch(values, actions, targets)
+    actions, T, E, A = _action_value_check(values, actions, targets)
+    return ActionValueLossFn.apply(values, actions, targets)
+
+
 class QnetInputFn(torch.autograd.Function):
     """Features + layer 0 of the DDQN graph model on ``a3vt_qnet_input_fwd/bwd`` (csrc/qnet_input.hip).  ``mesh`` (B, N, 4);
     the composites ``comp_s`` (B, npad), ``comp_t`` (4, npad), ``comp_c`` (50, npad) come padded to npad = pad4(h) columns."""

@@ -545,6 +545,71 @@ int a3vt_latent_nn_tile(void);
 int a3vt_latent_nn_query_floats(void);
 int a3vt_latent_nn_cached_rows(void);
 
+/* ---------------------------------------------------------------------------------------------
+ * The supervised latent policy's value network (policies/supervised/model.py, train.py:119-158), fp32 throughout.
+ *
+ * The network is a table of at most 16 layers, read on the host and passed to the kernels by value.  Layer l computes
+ * y[o] = act(sum_i weight[o][i] x[i] + bias[o]) with weight [out][in] row-major (torch's Linear layout, used in place) and act = ReLU
+ * when relu != 0.  The input of layer 0 is mask[e] (layer[0].in columns).  The input of layer concat_at (1 <= concat_at < n_layers) is
+ * cat(output of the layer before, latent[e], first_latent[e]), latent and first_latent [rows][latent_size]; every other layer reads
+ * the layer before it, so in must equal that layer's out (at concat_at: out + 2 * latent_size).  transform 0 leaves the last layer's
+ * output z as it is (DDQN's Latent_Model); transform 1 gives sigmoid(z) * scale - offset, sigmoid(z) = 1 / (1 + expf(-z)), the product
+ * and the difference rounded separately.
+ *
+ * Arithmetic contract of the forward.  Each output neuron is ONE fixed-order sum: lane l of a 64-lane wave owns the columns
+ * W (64 i + l) .. W (64 i + l) + W - 1, i = 0, 1, .., with W = 4 (16-byte loads) when in % 4 == 0 and W = 1 otherwise; it adds its
+ * products to a zero accumulator in ascending column order, one fused multiply-add per term; the 64 partial sums are added by the
+ * butterfly v += shfl_xor(v, 32), 16, 8, 4, 2, 1; the bias is added last; then the ReLU (x < 0 ? 0 : x, a NaN stays).  A row's result
+ * therefore depends neither on rows nor on the row's position: the same bits for a row evaluated alone, with rows appended, or
+ * permuted.  Activations stay in LDS between layers; a row is one workgroup.
+ *
+ * a3vt_latent_policy_fwd: one launch.  values [rows][A], A = the last layer's out, always written, unmasked.  With `taken`
+ * ([rows][A] fp32) `action` [rows] int32 is required and receives the action choice: the index of the lowest value among the actions
+ * with taken[e][a] == 0; a tie (-0 == +0 included) goes to the lower index, a NaN sorts after +inf, -1 when no action is open — the
+ * ordering rule of a3vt_latent_nearest.  With `stash` ([rows][a3vt_latent_policy_stash_floats(net)]) every layer's post-activation
+ * row is kept for the backward, layer after layer; for transform 1 the last layer's entry is sigmoid(z).
+ *
+ * a3vt_action_value_loss: one launch.  values [rows][A], actions [steps][rows] int32, targets [steps][rows] ->
+ * loss[0] = (1 / (steps rows)) sum_{t,e} (targets[t][e] - values[e][actions[t][e]])^2, summed in a fixed order, and dvalues [rows][A]
+ * = its gradient: zero, then for t ascending dvalues[e][a] += (values[e][a] - targets[t][e]) * (2 / (steps rows)), so repeated (e, a)
+ * pairs add up in t order.  The caller guarantees 0 <= actions < A (the Python layer refuses others); the kernel skips such a pair
+ * rather than index outside the row.
+ *
+ * a3vt_latent_policy_bwd: two launches.  (1) per row: delta of the last layer = dvalues * scale * s (1 - s) for transform 1 (s from
+ * the stash), dvalues otherwise; then delta_{l-1}[i] = relu'(stash_{l-1}[i] > 0) * sum_o weight_l[o][i] delta_l[o], one thread per
+ * column i, o ascending, one fused multiply-add per term; at concat_at only the columns of the previous layer flow on.  All deltas go
+ * to `delta` (the stash's shape).  (2) over (layer, slab of 8 output rows): dweight[o][i] = sum_e delta[e][o] x[e][i] (fused
+ * multiply-adds) and dbias[o] = sum_e delta[e][o], e ascending; accumulate != 0 adds the sums to what the gradient tensors hold,
+ * accumulate == 0 overwrites.  There are no gradients for mask, latent or first_latent.
+ *
+ * Limits (a3vt_latent_policy_limit: 0 rows and steps 4096, 1 every in / out — so also out + 2 * latent_size — 1024, 2 layers 16).
+ * Anything else, layers that do not chain, a null or misaligned pointer (weights 16 bytes where in % 4 == 0, everything else 4)
+ * returns non-zero with a message that names the value, and launches nothing.  No atomics, no fence between workgroups, no host
+ * synchronisation, no allocation: the same bits on every call.  a3vt_latent_policy_launches: kernel launches of the three entry
+ * points since the last reset ([0] forward, [1] loss, [2] backward); returns 3. */
+typedef struct a3vt_mlp_layer {
+  const float *weight, *bias;
+  int32_t in, out, relu, reserved;
+} a3vt_mlp_layer;
+typedef struct a3vt_mlp {
+  a3vt_mlp_layer layer[16];
+  int32_t n_layers, concat_at, latent_size, transform;
+  float scale, offset;
+} a3vt_mlp;
+typedef struct a3vt_mlp_grads {
+  float *dweight[16], *dbias[16];
+} a3vt_mlp_grads;
+int a3vt_latent_policy_limit(int which);
+int a3vt_latent_policy_stash_floats(const a3vt_mlp *net);   /* per row; 0 for a table the entry points refuse */
+int a3vt_latent_policy_fwd(const a3vt_mlp *net, const float *mask, const float *latent, const float *first_latent, const float *taken,
+                           int rows, float *values, int32_t *action, float *stash, void *stream);
+int a3vt_action_value_loss(const float *values, const int32_t *actions, const float *targets, int steps, int rows, int num_actions,
+                           float *loss, float *dvalues, void *stream);
+int a3vt_latent_policy_bwd(const a3vt_mlp *net, const a3vt_mlp_grads *grads, const float *mask, const float *latent,
+                           const float *first_latent, const float *dvalues, const float *stash, float *delta, int rows, int accumulate,
+                           void *stream);
+int a3vt_latent_policy_launches(long long *counts /*[3]*/, int reset);
+
 /* Graph_Model's features and layer 0 (policies/DDQN/model.py:100-118) without the (batch * n_vert) x 300 feature rows:
  *   y = relu(layer0([a_b | PE(p) | E[token]])) = relu(agg(S[b] + T[token] + relu(L2(relu(L1(nerf(p) ++ p)))) C))
  * with the composites S = a Wa + b3 Wp [batch][npad], T = E Wm [4][npad], C = W3^T Wp [50][npad] formed by the caller

@@ -1,0 +1,231 @@
+"""This package's supervised ``Engine`` replays ``g20_supervised.npz`` — what the REFERENCE engine did on the CPU
+(``golden/make_golden_supervised.py``): two training iterations of step 0, one of step 1 after a move by model 0, one validation
+episode — under every combination of ``fused_policy`` and ``batched_targets``.
+
+Bounds: equal random draws, moves and validation actions; values, targets, loss, stepped weights and scores within 1e-4 relative
+(``helpers.rel_err``: the largest difference over the largest reference entry), the bound of the g18 and g19 tests.  The generator
+asserts that at every decision of the fixture the two lowest open values are more than 1e-2 apart, one hundred times that, so
+equal actions follow from the value bound.  Every test prints the differences it measured; on an MI355X, the worst over the four
+combinations: values 1.6e-6, targets 3.0e-6, loss 3.5e-6, stepped weights 1.0e-7, scores 1.2e-7; ``zero_grad`` moves the second
+step's weights by 2.1e-3."""
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import supervised_util as su
+
+pytestmark = pytest.mark.gpu
+
+from a3vt_amd import ops  # noqa: E402
+
+TOL = 1e-4
+
+
+@pytest.fixture(scope="module")
+def golden():
+    from golden_util import load
+    return load(su.FIXTURE)
+
+
+@pytest.fixture(autouse=True)
+def restore_process_flags():
+    """``ActiveTouch.seed`` sets torch's convolution flags process-wide, as the reference does; other tests get them back."""
+    b = torch.backends.cudnn
+    kept = (b.deterministic, b.benchmark)
+    yield
+    b.deterministic, b.benchmark = kept
+
+
+@pytest.fixture(scope="module")
+def locations(cuda, golden, tmp_path_factory):
+    """The checkpoint directories of this package's models built by the fixture's recipe (checksums asserted)."""
+    import env_util as eu
+    import touch_util as tu
+    from golden_util import state_sha256
+    from a3vt_amd.pterotactyl.reconstruction.autoencoder import model as auto_model
+    from a3vt_amd.pterotactyl.reconstruction.touch import model as touch_model
+    from a3vt_amd.pterotactyl.reconstruction.vision import model as vision_model
+    from a3vt_amd.pterotactyl.utility import utils
+    bn = {k[3:]: torch.from_numpy(golden[k]) for k in golden.files if k.startswith("bn:")}
+    models = eu.build_models(su.ENV_CASE, touch_model, vision_model, auto_model, utils, "vision_charts", bn=bn)
+    for kind, (_, net) in models.items():
+        sd = tu.non_bn_state(net.state_dict()) if kind == "touch" else net.state_dict()
+        assert (state_sha256(sd) == golden[f"sha:{kind}"]).all(), f"the seeded {kind} model is not the fixture's"
+    return eu.write_models(str(tmp_path_factory.mktemp("g20")), models)
+
+
+@pytest.fixture(scope="module")
+def sensor_records(golden):
+    tables = su.status_tables()
+    for name, t in tables.items():
+        assert np.array_equal(t, golden["status:" + name])
+    return su.records(tables)
+
+
+def replay(golden, locations, sensor_records, monkeypatch, tmp_path, **knobs):
+    """The fixture's sequence on this package's engine -> (engine, per-iteration log, moves, validation observations)."""
+    from golden_util import state_sha256
+    from a3vt_amd.pterotactyl.policies import environment, recorded
+    from a3vt_amd.pterotactyl.policies.supervised import train as st
+    monkeypatch.setattr(environment.ActiveTouch, "get_loaders", lambda self: None)
+    monkeypatch.chdir(tmp_path)                                   # results/ and experiments/checkpoint/ are made in the working directory
+    engine = st.Engine(su.engine_args(**knobs, **locations), sampler=recorded.RecordedSampler(sensor_records))
+    engine.env = environment.ActiveTouch(engine.args, sampler=engine.sampler)
+    engine.env.score_samples = (torch.from_numpy(golden["face_idx"].astype(np.int32)), torch.from_numpy(golden["u"]), torch.from_numpy(golden["v"]))
+    engine.policy = SimpleNamespace(reset=lambda: None)
+    torch.manual_seed(int(golden["policy_seed"]))
+    engine.models = engine.make_models()
+    sd = {f"{i}.{k}": v for i, m in enumerate(engine.models) for k, v in m.state_dict().items()}
+    assert (state_sha256(sd) == golden["sha:policy"]).all(), "the seeded policy models are not the fixture's"
+    assert all(m.fused_policy == bool(knobs.get("fused_policy")) for m in engine.models)
+    iterations, moves = [], []
+    update, choose = engine.update, engine.choose
+
+    def logged_update(obs, random_actions, target):
+        loss, values = update(obs, random_actions, target)
+        iterations.append(dict(random_actions=random_actions.copy(), target=target.clone(), values=values.clone(), loss=loss.clone(),
+                               mask=obs["mask"].clone()))
+        return loss, values
+
+    def logged_choose(i, obs):
+        values, action = choose(i, obs)
+        moves.append((i, values.clone(), action.clone()))
+        return values, action
+
+    engine.update, engine.choose = logged_update, logged_choose
+    stepped = {}
+    for step, loader in ((0, su.batches("train")[:2]), (1, su.batches("train")[2:])):
+        engine.step = step
+        engine.start_step()
+        np.random.seed(su.NP_SEED + step)
+        engine.train(loader)
+        engine.save()
+        stepped[step] = {k: v.detach().cpu() for k, v in engine.models[step].state_dict().items()}
+    train_moves = list(moves)
+    del moves[:]
+    seen = []
+    reset, step_fn = engine.env.reset, engine.env.step
+    engine.env.reset = lambda batch: seen.append(reset(batch)) or seen[-1]
+    engine.env.step = lambda a: (lambda r: seen.append(r[0]) or r)(step_fn(a))
+    with torch.no_grad():
+        engine.validate(su.batches("valid"))
+    return SimpleNamespace(engine=engine, iterations=iterations, train_moves=train_moves, valid_moves=list(moves), seen=seen, stepped=stepped)
+
+
+def compare(golden, r, what, weights=True):
+    from helpers import rel_err
+    worst = {}
+
+    def within(name, got, want):
+        e = rel_err(torch.as_tensor(got).float().cpu(), torch.from_numpy(np.asarray(want)).float())
+        worst[name] = max(worst.get(name, 0.0), e)
+        assert e < TOL, f"{what}: {name} differs by {e:.2e} (relative)"
+
+    assert len(r.iterations) == 3
+    for n, it in enumerate(r.iterations):
+        key = f"train:{n}:"
+        assert np.array_equal(it["random_actions"], golden[key + "random_actions"]), n
+        assert torch.equal(it["mask"], torch.from_numpy(golden[key + "mask"]))
+        within("target", it["target"], golden[key + "target"])
+        within("values", it["values"], golden[key + "values"])
+        within("loss", it["loss"].reshape(1), golden[key + "loss"].reshape(1))
+    assert len(r.train_moves) == 1 and r.train_moves[0][0] == 0
+    assert np.array_equal(r.train_moves[0][2].numpy(), golden["train:2:moved"])
+    if weights:
+        for step, sd in r.stepped.items():
+            for k, v in sd.items():
+                if k in su.STORED_WEIGHTS:
+                    within("weights", v, golden[f"w:{step}:{k}"])
+                want = golden[f"wsum:{step}:{k}"]
+                e = float(np.abs(su.weight_sums(v.numpy()) - want).max() / want[1])
+                worst["weight sums"] = max(worst.get("weight sums", 0.0), e)
+                assert e < TOL, f"{what}: the sums of {k} of model {step} differ by {e:.2e} of the sum of magnitudes"
+    assert len(r.seen) == 1 + su.BUDGET and len(r.valid_moves) == su.BUDGET
+    for i, obs in enumerate(r.seen):
+        within("score", obs["score"], golden[f"valid:{i}:score"])
+        assert torch.equal(obs["mask"], torch.from_numpy(golden[f"valid:{i}:mask"]))
+        if i:
+            model, values, action = r.valid_moves[i - 1]
+            assert model == i - 1 and np.array_equal(action.numpy(), golden[f"valid:{i}:actions"]), (i, action)
+            within("values", values, golden[f"valid:{i}:values"])
+    assert np.array_equal(r.engine.chosen.numpy(), np.stack([golden[f"valid:{i}:actions"] for i in (1, 2)], axis=1))
+    assert abs(float(r.engine.current_loss) - float(golden["current_loss"])) < TOL
+    print(f"{what}: worst relative differences {({k: f'{v:.2e}' for k, v in worst.items()})}")
+    return worst
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "modules"])
+@pytest.mark.parametrize("batched", [True, False], ids=["batched", "check_step"])
+def test_engine_replays_the_reference(cuda, golden, locations, sensor_records, monkeypatch, tmp_path, fused, batched):
+    ops.policy_launches(reset=True)
+    r = replay(golden, locations, sensor_records, monkeypatch, tmp_path, fused_policy=fused, batched_targets=batched)
+    counts = ops.policy_launches()
+    compare(golden, r, f"fused_policy={fused} batched_targets={batched}")
+    for step in range(su.BUDGET):
+        assert os.path.exists(os.path.join(r.engine.checkpoint_dir, f"model_{step}"))
+    # the policy's own launches: three updates (forward, loss, two of the backward; Adam is the fifth) and three choices
+    assert counts == ({"fwd": 3 + 3, "loss": 3, "bwd": 6} if fused else {"fwd": 0, "loss": 0, "bwd": 0})
+    assert r.engine.optimizer.library_steps == 1                  # (step 1's optimizer: one iteration, one launch)
+    assert r.engine.copied == [((2,), torch.int32)] * 3
+
+
+def test_a_fused_update_is_five_launches(cuda, golden, locations, sensor_records, monkeypatch, tmp_path):
+    r = replay(golden, locations, sensor_records, monkeypatch, tmp_path, fused_policy=True, batched_targets=True)
+    engine, it = r.engine, r.iterations[-1]
+    obs = {"mask": it["mask"], "latent": r.seen[0]["latent"], "first_latent": r.seen[0]["first_latent"]}
+    before = engine.optimizer.library_steps
+    ops.policy_launches(reset=True)
+    engine.update(obs, it["random_actions"], it["target"])
+    counts = ops.policy_launches()
+    assert counts == {"fwd": 1, "loss": 1, "bwd": 2} and engine.optimizer.library_steps - before == 1
+    assert sum(counts.values()) + 1 == 5
+
+
+def test_zero_grad_differs_from_the_reference_s_second_iteration(cuda, golden, locations, sensor_records, monkeypatch, tmp_path):
+    """The reference never zeroes the gradient, so its second step applies the sum of both iterations' gradients.  With
+    ``zero_grad`` the first iteration and everything the second one computes before its step are the fixture's; the weights it
+    leaves are not."""
+    from helpers import rel_err
+    for fused in (True, False):
+        where = tmp_path / ("fused" if fused else "modules")
+        where.mkdir()
+        r = replay(golden, locations, sensor_records, monkeypatch, where, fused_policy=fused, batched_targets=True, zero_grad=True)
+        for n in (0, 1):
+            assert rel_err(r.iterations[n]["values"].cpu(), torch.from_numpy(golden[f"train:{n}:values"])) < TOL
+        k = su.STORED_WEIGHTS[0]
+        e = rel_err(r.stepped[0][k], torch.from_numpy(golden[f"w:0:{k}"]))
+        print(f"zero_grad, fused_policy={fused}: {k} of model 0 differs from the fixture by {e:.2e} (relative)")
+        assert e > 10 * TOL
+
+
+def test_one_host_tensor_of_E_integers_leaves_a_model_call(cuda, golden, locations, sensor_records, monkeypatch, tmp_path):
+    """With the knob on, every ``Engine.choose`` copies exactly one tensor to the host — E int32 — and nothing else synchronises
+    inside it: ``Tensor.cpu`` / ``numpy`` / ``item`` / ``tolist`` / conversions on device tensors are counted while it runs."""
+    from a3vt_amd.pterotactyl.policies.supervised import train as st
+    copies = []
+    inner = st.Engine.choose
+    originals = {name: getattr(torch.Tensor, name) for name in ("cpu", "item", "tolist", "numpy", "__bool__", "__int__", "__float__")}
+
+    def counted(name):
+        def method(self, *a, **k):
+            if self.is_cuda:
+                copies[-1].append((name, tuple(self.shape), self.dtype))
+            return originals[name](self, *a, **k)
+        return method
+
+    def watched(self, i, obs):
+        copies.append([])
+        for name in originals:
+            setattr(torch.Tensor, name, counted(name))
+        try:
+            return inner(self, i, obs)
+        finally:
+            for name, fn in originals.items():
+                setattr(torch.Tensor, name, fn)
+
+    monkeypatch.setattr(st.Engine, "choose", watched)
+    replay(golden, locations, sensor_records, monkeypatch, tmp_path, fused_policy=True, batched_targets=True)
+    assert len(copies) == 3 and all(c == [("cpu", (2,), torch.int32)] for c in copies), copies
