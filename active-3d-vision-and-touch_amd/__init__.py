@@ -40,6 +40,7 @@ def install_as_pterotactyl():
         "pterotactyl.policies.baselines.baselines": ".pterotactyl.policies.baselines.baselines",
         "pterotactyl.policies.replay": ".pterotactyl.policies.replay",
         "pterotactyl.policies.DDQN.ddqn": ".pterotactyl.policies.DDQN.ddqn",
+        "pterotactyl.policies.DDQN.train": ".pterotactyl.policies.DDQN.train",
         "pterotactyl.policies.supervised.model": ".pterotactyl.policies.supervised.model",
         "pterotactyl.policies.supervised.train": ".pterotactyl.policies.supervised.train",
     }

@@ -1454,6 +1454,105 @@ int a3vt_latent_policy_launches(long long *counts, int reset) {
   return 3;
 }
 
+// ---- DDQN's Latent_Model on the same layer table (ddqn_latent.hip) ---------------------------------------------------------------
+namespace {
+std::atomic<long long> g_ddqn_latent_launches[2];
+
+// The table's rules plus the learner's: transform 0, at most kTdMaxActions outputs -> floats of a stash row, or -1 (message set).
+int ddqn_latent_net_check(const char *who, const a3vt_mlp *net) {
+  const int ld = policy_net_check(who, net);
+  if (ld < 0) return -1;
+  const int A = net->layer[net->n_layers - 1].out;
+  if (net->transform != 0 || A > kTdMaxActions) {
+    set_error("%s: transform=%d (0: a Q network has no output squashing) num_actions=%d (1..%d) unsupported", who, net->transform, A,
+              kTdMaxActions);
+    return -1;
+  }
+  return ld;
+}
+bool ddqn_latent_batch_ok(const char *who, const char *name, int v) {
+  if (v >= 1 && v <= kTdMaxBatch) return true;
+  set_error("%s: %s=%d (1..%d) unsupported", who, name, v, kTdMaxBatch);
+  return false;
+}
+}  // namespace
+
+size_t a3vt_ddqn_latent_scratch_bytes(const a3vt_mlp *online, int batch) {
+  const int ld = ddqn_latent_net_check("ddqn_latent_scratch_bytes", online);
+  if (ld < 0 || !ddqn_latent_batch_ok("ddqn_latent_scratch_bytes", "batch", batch)) return 0;
+  return (size_t)batch * (2 * (size_t)online->layer[online->n_layers - 1].out + 2 * (size_t)ld) * sizeof(float);
+}
+
+int a3vt_ddqn_latent_q(const a3vt_mlp *net, const float *mask, const float *latent, const float *first_latent, const float *mask_penalty,
+                       int rows, float *q, int32_t *action, void *stream) {
+  if (ddqn_latent_net_check("ddqn_latent_q", net) < 0 || !ddqn_latent_batch_ok("ddqn_latent_q", "rows", rows)) return -1;
+  A3VT_CHECK_ARG(mask && latent && first_latent && q);
+  A3VT_CHECK_ARG((mask_penalty && action) || (!mask_penalty && !action));
+  A3VT_CHECK_ARG(aligned_to(mask, 4) && aligned_to(latent, 4) && aligned_to(first_latent, 4) && aligned_to(mask_penalty, 4) &&
+                 aligned_to(q, 4) && aligned_to(action, 4));
+  g_ddqn_latent_launches[0].fetch_add(1, std::memory_order_relaxed);
+  return launch_ddqn_latent_q(policy_net_of(net), mask, latent, first_latent, mask_penalty, rows, q, action, static_cast<hipStream_t>(stream));
+}
+
+int a3vt_ddqn_latent_update(const a3vt_mlp *online, const a3vt_mlp *target_net, const a3vt_mlp_grads *grads, const float *mask,
+                            const float *mask_n, const float *latent, const float *latent_n, const float *first_latent,
+                            const float *actions, const float *rewards, const float *denom, int batch, int budget, float gamma,
+                            float *q_cur, int32_t *best_next, float *target, float *diff, float *loss, void *scratch, void *stream) {
+  const int ld = ddqn_latent_net_check("ddqn_latent_update (online)", online);
+  if (ld < 0 || ddqn_latent_net_check("ddqn_latent_update (target)", target_net) < 0 ||
+      !ddqn_latent_batch_ok("ddqn_latent_update", "batch", batch))
+    return -1;
+  if (online->n_layers != target_net->n_layers || online->concat_at != target_net->concat_at ||
+      online->latent_size != target_net->latent_size) {
+    set_error("ddqn_latent_update: the target net has n_layers=%d concat_at=%d latent_size=%d, the online net %d %d %d", target_net->n_layers,
+              target_net->concat_at, target_net->latent_size, online->n_layers, online->concat_at, online->latent_size);
+    return -1;
+  }
+  if (online->layer[0].in != online->layer[online->n_layers - 1].out) {   // (mask is the network's input AND the table of taken actions)
+    set_error("ddqn_latent_update: layer 0 in=%d is not num_actions=%d (mask feeds the network and penalises the actions)",
+              online->layer[0].in, online->layer[online->n_layers - 1].out);
+    return -1;
+  }
+  for (int l = 0; l < online->n_layers; ++l) {
+    const a3vt_mlp_layer &a = online->layer[l], &b = target_net->layer[l];
+    if (a.in != b.in || a.out != b.out || (a.relu != 0) != (b.relu != 0)) {
+      set_error("ddqn_latent_update: layer %d of the target net is in=%d out=%d relu=%d, of the online net in=%d out=%d relu=%d", l, b.in, b.out,
+                b.relu, a.in, a.out, a.relu);
+      return -1;
+    }
+  }
+  A3VT_CHECK_ARG(grads && mask && mask_n && latent && latent_n && first_latent && actions && rewards);
+  A3VT_CHECK_ARG(q_cur && best_next && target && diff && loss && scratch);
+  A3VT_CHECK_ARG(aligned_to(mask, 4) && aligned_to(mask_n, 4) && aligned_to(latent, 4) && aligned_to(latent_n, 4) &&
+                 aligned_to(first_latent, 4) && aligned_to(actions, 4) && aligned_to(rewards, 4) && aligned_to(denom, 4));
+  A3VT_CHECK_ARG(aligned_to(q_cur, 4) && aligned_to(best_next, 4) && aligned_to(target, 4) && aligned_to(diff, 4) && aligned_to(loss, 4) &&
+                 aligned_to(scratch, 4));
+  PolicyGrads g;
+  memcpy(&g, grads, sizeof(g));
+  for (int l = 0; l < online->n_layers; ++l) {
+    if (!g.dw[l] || !g.db[l] || !aligned_to(g.dw[l], 4) || !aligned_to(g.db[l], 4)) {
+      set_error("ddqn_latent_update: layer %d dweight / dbias null or misaligned", l);
+      return -1;
+    }
+  }
+  DdqnLatentArgs a{};
+  a.mask = mask, a.mask_n = mask_n, a.latent = latent, a.latent_n = latent_n, a.first_latent = first_latent;
+  a.actions = actions, a.rewards = rewards, a.denom = denom;
+  a.batch = batch, a.budget = budget, a.ld = ld, a.gamma = gamma;
+  a.q_cur = q_cur, a.diff = diff, a.target = target, a.loss = loss, a.best_next = best_next;
+  a.scratch = static_cast<float *>(scratch);
+  g_ddqn_latent_launches[1].fetch_add(3, std::memory_order_relaxed);
+  return launch_ddqn_latent_update(policy_net_of(online), policy_net_of(target_net), g, a, static_cast<hipStream_t>(stream));
+}
+
+int a3vt_ddqn_latent_launches(long long *counts, int reset) {
+  for (int i = 0; i < 2; ++i) {
+    if (counts) counts[i] = g_ddqn_latent_launches[i].load(std::memory_order_relaxed);
+    if (reset) g_ddqn_latent_launches[i].store(0, std::memory_order_relaxed);
+  }
+  return 2;
+}
+
 namespace {
 struct QnetLayout {
   size_t za, heavy, ga, dz, db_slab, slab, total;

@@ -10,8 +10,7 @@
 // The reference walks the batch in a Python loop (one device sync per sample) around a dozen small launches.  Here one workgroup
 // does the batch: a wave per sample (lanes over the actions), then the mean as a fixed-order tree over the squares kept in LDS —
 // no atomics, the same bits on every call.  B <= 4096, A <= 304.
-#include "kernels.h"
-#include "prims.h"
+#include "policy_dev.h"   // td_sample, td_loss_tree: the sample rule and the loss tree, shared with ddqn_latent.hip
 
 namespace a3vt {
 
@@ -26,52 +25,13 @@ __global__ __launch_bounds__(256) void ddqn_td_kernel(const float *__restrict__ 
   __shared__ float sq[kTdMaxBatch];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int b = wave; b < batch; b += 4) {
-    const float *mb = mask + (size_t)b * na, *qb = q_no + (size_t)b * na;
-    float touched = 0.f, best = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int a = lane; a < na; a += 64) {
-      const float mk = mb[a];
-      touched += mk;
-      const float q = mk > 0.f ? -1e10f : qb[a];
-      if (q > best || arg == 0x7fffffff) {   // strict: the lowest index of this lane's columns wins a tie
-        best = q;
-        arg = a;
-      }
-    }
-    touched = wave_sum(touched);   // the mask holds 0 / 1: the sum is exact in any order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ob = __shfl_xor(best, off, 64);
-      const int oa = __shfl_xor(arg, off, 64);
-      if (oa != 0x7fffffff && (arg == 0x7fffffff || ob > best || (ob == best && oa < arg))) {
-        best = ob;
-        arg = oa;
-      }
-    }
-    if (lane == 0) {
-      int act = (int)actions[b];
-      act = act < 0 ? 0 : (act >= na ? na - 1 : act);   // (an action outside the table is the caller's error: stay inside the row)
-      float r = rewards[b];
-      if (denom) r = r / denom[b];
-      const float next = touched < done_at ? q_nt[(size_t)b * na + arg] : 0.f;
-      const float t = __fadd_rn(__fmul_rn(gamma, next), r);   // the reference's two roundings (no fused multiply-add)
-      const float d = q_cur[(size_t)b * na + act] - t;
-      best_next[b] = arg;
-      target[b] = t;
-      diff[b] = d;
-      sq[b] = d * d;
-    }
+    const size_t row = (size_t)b * na;
+    const float d = td_sample(q_cur + row, q_no + row, q_nt + row, mask + row, actions, rewards, denom, b, na, done_at, gamma, lane, diff,
+                              best_next, target);
+    if (lane == 0) sq[b] = d * d;
   }
   __syncthreads();
-  // mean of the squares: pairwise tree in a fixed order (element i takes i + stride)
-  int n = batch;
-  while (n > 1) {
-    const int half = (n + 1) >> 1;
-    for (int i = threadIdx.x; i + half < n; i += 256) sq[i] += sq[i + half];
-    __syncthreads();
-    n = half;
-  }
-  if (threadIdx.x == 0) loss[0] = sq[0] / (float)batch;
+  td_loss_tree(sq, batch, loss);
 }
 
 __global__ void ddqn_td_bwd_kernel(const float *__restrict__ diff, const float *__restrict__ actions,
@@ -81,7 +41,7 @@ __global__ void ddqn_td_bwd_kernel(const float *__restrict__ diff, const float *
   const int b = i / na, a = i - b * na;
   int act = (int)actions[b];
   act = act < 0 ? 0 : (act >= na ? na - 1 : act);
-  dq[i] = a == act ? grad_loss[0] * 2.f * diff[b] / (float)batch : 0.f;
+  dq[i] = a == act ? td_dq(grad_loss[0], diff[b], batch) : 0.f;
 }
 
 }  // namespace

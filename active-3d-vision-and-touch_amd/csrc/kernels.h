@@ -407,6 +407,22 @@ int launch_action_value_loss(const float *values, const int32_t *actions, const 
 int launch_policy_bwd(const PolicyNet &net, const PolicyGrads &grads, const float *mask, const float *latent, const float *first_latent,
                       const float *dvalues, const float *stash, float *delta, int rows, int ld, int accumulate, hipStream_t s);
 
+// ddqn_latent.hip: DDQN's Latent_Model (a PolicyNet with transform 0) — the action choice as one launch, an update's three
+// forwards / TD and deltas / gradients and loss as three.  The device code is policy_dev.h's, shared with latent_policy.hip and ddqn.hip.
+struct DdqnLatentArgs {
+  const float *mask, *mask_n, *latent, *latent_n, *first_latent;   // [batch][in0], [batch][latent_size]
+  const float *actions, *rewards, *denom;                          // [batch]; denom may be null
+  int batch, budget, ld;                                           // ld: floats of a stash row
+  float gamma;
+  float *q_cur, *diff, *target, *loss;                             // [batch][A], [batch], [batch], [1]
+  int32_t *best_next;                                              // [batch]
+  float *scratch;                                                  // q_next_online, q_next_target [batch][A]; stash, delta [batch][ld]
+};
+int launch_ddqn_latent_q(const PolicyNet &net, const float *mask, const float *latent, const float *first_latent, const float *penalty,
+                         int rows, float *q, int32_t *action, hipStream_t s);
+int launch_ddqn_latent_update(const PolicyNet &online, const PolicyNet &target_net, const PolicyGrads &grads, const DdqnLatentArgs &a,
+                              hipStream_t s);
+
 // qnet_input.hip: features + product of the DDQN graph model's layer 0 without the (B N) x 300 feature rows
 struct QnetArgs {
   const float *mesh;                  // [B][N][4]: x, y, z, mask token (0..3 as a float)

@@ -22,43 +22,15 @@
 //   policy_bwd_grad_kernel     a workgroup owns kPolicySlab output rows of one layer: dW[o][i] = sum_e delta[e][o] in[e][i] and
 //                        db[o] = sum_e delta[e][o], e ascending, one thread per element.
 // No atomics, no fences between workgroups, no host synchronisation: the same bits on every call.
-#include "kernels.h"
-#include "prims.h"
+// The row forward, the delta chain and the gradient slab are policy_dev.h's: ddqn_latent.hip runs the same sums.
+#include "policy_dev.h"
 
 namespace a3vt {
 
 namespace {
 
 using u64 = unsigned long long;
-constexpr int kFwdThreads = 1024, kFwdWaves = kFwdThreads / 64, kNeurons = 4;
-constexpr int kLossThreads = 256, kLossRows = 16, kGradThreads = 256;
-
-// One lane's share of sum_c w[c] x[c] for kNeurons neighbouring weight rows (x in LDS, 16-byte aligned; w rows `in` floats apart).
-template <int W>
-__device__ __forceinline__ void dot_share(const float *__restrict__ w, const float *x, int in, int rows, int lane, float (&acc)[kNeurons]) {
-#pragma unroll
-  for (int r = 0; r < kNeurons; ++r) acc[r] = 0.f;
-  for (int c = W * lane; c < in; c += 64 * W) {
-    if (W == 4) {
-      const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + c);
-#pragma unroll
-      for (int r = 0; r < kNeurons; ++r) {
-        if (r < rows) {   // (wave-uniform)
-          const f32x4 wv = *reinterpret_cast<const f32x4 *>(w + (size_t)r * in + c);
-          acc[r] = __fmaf_rn(wv[0], xv[0], acc[r]);
-          acc[r] = __fmaf_rn(wv[1], xv[1], acc[r]);
-          acc[r] = __fmaf_rn(wv[2], xv[2], acc[r]);
-          acc[r] = __fmaf_rn(wv[3], xv[3], acc[r]);
-        }
-      }
-    } else {
-      const float xv = x[c];
-#pragma unroll
-      for (int r = 0; r < kNeurons; ++r)
-        if (r < rows) acc[r] = __fmaf_rn(w[(size_t)r * in + c], xv, acc[r]);
-    }
-  }
-}
+constexpr int kLossThreads = 256, kLossRows = 16;
 
 // value -> a key that orders as the contract does: numbers ascending (-0 == +0), then every NaN
 __device__ __forceinline__ unsigned order_key(float v) {
@@ -83,48 +55,9 @@ __global__ __launch_bounds__(kFwdThreads) void policy_fwd_kernel(PolicyNet net, 
                                                                  const float *__restrict__ taken, float *__restrict__ values,
                                                                  int32_t *__restrict__ action, float *__restrict__ stash, int ld) {
   __shared__ __attribute__((aligned(16))) float buf[2][kPolicyMaxWidth];
-  const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int in0 = net.layer[0].in, ls = net.latent_size, n = net.n_layers;
-  for (int i = tid; i < in0; i += kFwdThreads) buf[0][i] = mask[(size_t)e * in0 + i];
-  int cur = 0, off = 0;
-  for (int l = 0; l < n; ++l) {
-    const PolicyLayer L = net.layer[l];
-    if (l == net.concat_at) {   // cat(previous output, latent, first_latent): the previous layer wrote [0, p)
-      const int p = L.in - 2 * ls;
-      for (int i = tid; i < 2 * ls; i += kFwdThreads)
-        buf[cur][p + i] = i < ls ? latent[(size_t)e * ls + i] : first_latent[(size_t)e * ls + i - ls];
-    }
-    __syncthreads();   // (the input row is complete; the other row has been consumed)
-    const float *x = buf[cur];
-    float *y = buf[cur ^ 1];
-    const bool last = l == n - 1;
-    for (int o0 = wave * kNeurons; o0 < L.out; o0 += kFwdWaves * kNeurons) {
-      const int rows = min(kNeurons, L.out - o0);
-      float acc[kNeurons];
-      if (L.in % 4 == 0)
-        dot_share<4>(L.w + (size_t)o0 * L.in, x, L.in, rows, lane, acc);
-      else
-        dot_share<1>(L.w + (size_t)o0 * L.in, x, L.in, rows, lane, acc);
-#pragma unroll
-      for (int r = 0; r < kNeurons; ++r) {
-        if (r >= rows) break;
-        float z = wave_sum(acc[r]) + L.b[o0 + r];
-        if (L.relu) z = z < 0.f ? 0.f : z;   // (a NaN stays a NaN)
-        float kept = z;                      // what the backward wants of this layer
-        if (last && net.transform) {
-          kept = 1.f / (1.f + expf(-z));
-          z = __fsub_rn(__fmul_rn(kept, net.scale), net.offset);
-        }
-        if (lane == 0) {
-          y[o0 + r] = z;
-          if (stash) stash[(size_t)e * ld + off + o0 + r] = kept;
-          if (last) values[(size_t)e * L.out + o0 + r] = z;
-        }
-      }
-    }
-    cur ^= 1;
-    off += L.out;
-  }
+  const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ls = net.latent_size, n = net.n_layers;
+  const int cur = policy_row_forward(net, mask + (size_t)e * net.layer[0].in, latent + (size_t)e * ls, first_latent + (size_t)e * ls,
+                                     values + (size_t)e * net.layer[n - 1].out, stash ? stash + (size_t)e * ld : nullptr, buf);
   if (!action) return;
   __syncthreads();
   if (wave != 0) return;
@@ -181,37 +114,8 @@ __global__ __launch_bounds__(kFwdThreads) void policy_bwd_delta_kernel(PolicyNet
                                                                        const float *__restrict__ stash, float *__restrict__ delta,
                                                                        int ld) {
   __shared__ float d[2][kPolicyMaxWidth];
-  const int e = blockIdx.x, tid = threadIdx.x, n = net.n_layers;
-  const float *act = stash + (size_t)e * ld;
-  float *del = delta + (size_t)e * ld;
-  int off = ld - net.layer[n - 1].out, cur = 0;
-  {
-    const PolicyLayer L = net.layer[n - 1];
-    for (int i = tid; i < L.out; i += kFwdThreads) {
-      float g = dvalues[(size_t)e * L.out + i];
-      const float a = act[off + i];
-      if (net.transform) g = (g * net.scale) * (a * (1.f - a));   // (the stash keeps the sigmoid itself)
-      if (L.relu) g = a > 0.f ? g : 0.f;
-      d[0][i] = g;
-      del[off + i] = g;
-    }
-  }
-  for (int l = n - 1; l >= 1; --l) {
-    const PolicyLayer L = net.layer[l], P = net.layer[l - 1];
-    const int poff = off - P.out;
-    __syncthreads();   // (delta_l is complete; the other row has been consumed)
-    for (int i = tid; i < P.out; i += kFwdThreads) {   // at the concat only the first P.out input columns flow on
-      const float *__restrict__ w = L.w + i;
-      float acc = 0.f;
-#pragma unroll 4
-      for (int o = 0; o < L.out; ++o) acc = __fmaf_rn(w[(size_t)o * L.in], d[cur][o], acc);
-      if (P.relu) acc = act[poff + i] > 0.f ? acc : 0.f;
-      d[cur ^ 1][i] = acc;
-      del[poff + i] = acc;
-    }
-    cur ^= 1;
-    off = poff;
-  }
+  const int e = blockIdx.x;
+  policy_row_delta(net, dvalues + (size_t)e * net.layer[net.n_layers - 1].out, stash + (size_t)e * ld, delta + (size_t)e * ld, ld, d);
 }
 
 __global__ __launch_bounds__(kGradThreads) void policy_bwd_grad_kernel(PolicyNet net, PolicyGrads grads, const float *__restrict__ mask,
@@ -219,40 +123,7 @@ __global__ __launch_bounds__(kGradThreads) void policy_bwd_grad_kernel(PolicyNet
                                                                        const float *__restrict__ first_latent,
                                                                        const float *__restrict__ stash, const float *__restrict__ delta,
                                                                        int E, int ld, int accumulate) {
-  int b = blockIdx.x, l = 0, off = 0;
-  while (b >= cdiv(net.layer[l].out, kPolicySlab)) {   // (the grid is the sum of the layers' slab counts)
-    b -= cdiv(net.layer[l].out, kPolicySlab);
-    off += net.layer[l].out;
-    ++l;
-  }
-  const PolicyLayer L = net.layer[l];
-  const int o0 = b * kPolicySlab, rows = min(kPolicySlab, L.out - o0), ls = net.latent_size;
-  const int p = l == net.concat_at ? L.in - 2 * ls : L.in;   // input columns that come from the previous layer's row
-  float *__restrict__ dw = grads.dw[l], *__restrict__ db = grads.db[l];
-  for (int idx = threadIdx.x; idx < rows * L.in; idx += kGradThreads) {
-    const int o = o0 + idx / L.in, i = idx % L.in;
-    const float *src;
-    int stride;
-    if (l == 0) {
-      src = mask + i, stride = L.in;
-    } else if (i < p) {
-      src = stash + (off - p) + i, stride = ld;
-    } else if (i < p + ls) {
-      src = latent + (i - p), stride = ls;
-    } else {
-      src = first_latent + (i - p - ls), stride = ls;
-    }
-    const float *__restrict__ dl = delta + off + o;
-    float acc = 0.f;
-    for (int e = 0; e < E; ++e) acc = __fmaf_rn(dl[(size_t)e * ld], src[(size_t)e * stride], acc);
-    const size_t at = (size_t)o * L.in + i;
-    dw[at] = accumulate ? dw[at] + acc : acc;
-    if (i == 0) {
-      float accb = 0.f;
-      for (int e = 0; e < E; ++e) accb += dl[(size_t)e * ld];
-      db[o] = accumulate ? db[o] + accb : accb;
-    }
-  }
+  policy_grad_slab(net, grads, mask, latent, first_latent, stash, delta, E, ld, accumulate, blockIdx.x);
 }
 
 }  // namespace
@@ -276,9 +147,7 @@ int launch_policy_bwd(const PolicyNet &net, const PolicyGrads &grads, const floa
                       const float *dvalues, const float *stash, float *delta, int rows, int ld, int accumulate, hipStream_t s) {
   A3VT_LAUNCH(policy_bwd_delta_kernel, dim3(rows), dim3(kFwdThreads), 0, s, net, dvalues, stash, delta, ld);
   A3VT_CHECK_LAUNCH();
-  int slabs = 0;
-  for (int l = 0; l < net.n_layers; ++l) slabs += cdiv(net.layer[l].out, kPolicySlab);
-  A3VT_LAUNCH(policy_bwd_grad_kernel, dim3(slabs), dim3(kGradThreads), 0, s, net, grads, mask, latent, first_latent, stash, delta, rows, ld,
+  A3VT_LAUNCH(policy_bwd_grad_kernel, dim3(policy_grad_slabs(net)), dim3(kGradThreads), 0, s, net, grads, mask, latent, first_latent, stash, delta, rows, ld,
               accumulate);
   A3VT_CHECK_LAUNCH();
   return 0;

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT_LIB: another build of the library (tools/asan_host.sh)
 SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "conv5f.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
-           "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip", "latent_nn.hip", "latent_policy.hip"]
+           "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip", "latent_nn.hip", "latent_policy.hip", "ddqn_latent.hip"]
 # Per-file extra flags (none at present; sample.hip / gcn_csr.hip rely on IEEE NaN semantics — the reference's NaN
 # scrubs, a3vt_check_finite — so fast-math style flags must never be applied globally).
 # chamfer.hip: keep the nearest-neighbour loop on scalar fp32 ops (the SLP vectoriser would re-pack it into v_pk_*_f32,
@@ -134,6 +134,11 @@ SIGNATURES = {
     "a3vt_action_value_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "a3vt_latent_policy_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "a3vt_latent_policy_launches": (_i, [_vp, _i]),
+    "a3vt_ddqn_latent_scratch_bytes": (_sz, [_vp, _i]),
+    "a3vt_ddqn_latent_q": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "a3vt_ddqn_latent_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_float,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "a3vt_ddqn_latent_launches": (_i, [_vp, _i]),
     "a3vt_qnet_input_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "a3vt_qnet_input_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "a3vt_qnet_input_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i,
@@ -158,7 +163,7 @@ def build(force=False, verbose=False):
 
 def _build(force, verbose, lib_path, objdir):
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "prims.h", "gemm_tile.h")] + \
+    deps = srcs + [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "prims.h", "policy_dev.h", "gemm_tile.h")] + \
         [os.path.join(_HERE, "..", "include", "a3vt.h")]
     force = force or os.environ.get("A3VT_FORCE_BUILD", "0") not in ("", "0")   # prove on any box that it compiles
     if not force and os.path.exists(lib_path) and all(

@@ -1441,6 +1441,119 @@ def action_value_loss(values, actions, targets):
     return ActionValueLossFn.apply(values, actions, targets)
 
 
+# ---- DDQN's Latent_Model on the layer table (csrc/ddqn_latent.hip) -----------------------------------------------------------
+
+def ddqn_latent_launches(reset=False):
+    """Kernel launches of ``a3vt_ddqn_latent_q`` / ``a3vt_ddqn_latent_update`` since the last reset (a test hook)."""
+    buf = (ctypes.c_longlong * 2)()
+    _lib.load().a3vt_ddqn_latent_launches(buf, 1 if reset else 0)
+    return dict(zip(("q", "update"), (int(x) for x in buf)))
+
+
+def ddqn_latent_supported(table, mask):
+    """Whether the two ``ddqn_latent`` ops run the kernels for these operands (else the torch form of the same contract runs):
+    what ``policy_supported`` asks, no output transform, the mask as wide as the action table, A <= 304."""
+    return bool(policy_supported(table, mask) and table.transform is None and table.in_width == table.num_actions
+                and table.num_actions <= LATENT_NN_MAX["num_actions"])
+
+
+def _ddqn_latent_q_torch(table, mask, latent, first_latent, mask_penalty):
+    q, _ = _latent_policy_torch(table, mask, latent, first_latent, None)
+    if mask_penalty is None:
+        return q, None
+    return q, q.detach().masked_fill(mask_penalty > 0, -1e10).max(1)[1].to(torch.int32)
+
+
+def ddqn_latent_q(table, mask, latent, first_latent, mask_penalty=None):
+    """DDQN's ``Latent_Model`` -> ``(q (E, A), action (E,) int32 or None)``: ``q`` unpenalised; with ``mask_penalty`` (E, A) also
+    ``argmax(mask_penalty > 0 ? -1e10 : q)``, the lowest index on a tie (index 0 when every action is taken).  No autograd.  GPU
+    operands inside the limits run ``a3vt_ddqn_latent_q`` (one launch; ``q`` has the bits of ``latent_policy_fwd``'s values);
+    everything else takes the same contract on torch ops."""
+    if mask_penalty is not None and (mask_penalty.dtype != torch.float32 or mask_penalty.shape != (mask.shape[0], table.num_actions)
+                                     or mask_penalty.device != mask.device):
+        raise RuntimeError(f"a3vt: ddqn_latent_q mask_penalty must be a float32 ({mask.shape[0]}, {table.num_actions}) tensor on the mask's device")
+    if not ddqn_latent_supported(table, mask):
+        with torch.no_grad():
+            return _ddqn_latent_q_torch(table, mask, latent, first_latent, mask_penalty)
+    E = _policy_inputs(table, mask, latent, first_latent, None)
+    L = _lib.load()
+    mask, latent, first_latent = _req(mask, "mask"), _req(latent, "latent"), _req(first_latent, "first_latent")
+    pen = None if mask_penalty is None else _req(mask_penalty, "mask_penalty")
+    q = torch.empty((E, table.num_actions), dtype=torch.float32, device=mask.device)
+    action = None if pen is None else torch.empty(E, dtype=torch.int32, device=mask.device)
+    _lib.check(L.a3vt_ddqn_latent_q(ctypes.byref(table.struct()), _lib.ptr(mask), _lib.ptr(latent), _lib.ptr(first_latent), _lib.ptr(pen), E,
+                                    _lib.ptr(q), _lib.ptr(action), _stream()), "ddqn_latent_q")
+    return q, action
+
+
+def _ddqn_latent_update_torch(online, target, grads, mask, mask_n, latent, latent_n, first_latent, actions, rewards, denom, budget, gamma):
+    """The contract of ``a3vt_ddqn_latent_update`` composed from the torch forms of the existing ops."""
+    params = [p.detach().requires_grad_(True) for p in online.params()]
+    live = PolicyTable([(params[2 * l], params[2 * l + 1], r) for l, (_, _, r) in enumerate(online.layers)], online.concat_at, online.transform)
+    q_cur, _ = _latent_policy_torch(live, mask, latent, first_latent, None)
+    with torch.no_grad():
+        q_no, _ = _latent_policy_torch(online, mask_n, latent_n, first_latent, None)
+        q_nt, _ = _latent_policy_torch(target, mask_n, latent_n, first_latent, None)
+    loss, best, tgt = _ddqn_td_torch(q_cur, q_no, q_nt, mask, actions, rewards, denom, budget, gamma)
+    got = torch.autograd.grad(loss, params)
+    with torch.no_grad():
+        for l, (dw, db) in enumerate(grads):
+            dw.copy_(got[2 * l])
+            db.copy_(got[2 * l + 1])
+        act = actions.long().clamp(0, q_cur.shape[1] - 1)
+        diff = q_cur.detach().gather(1, act.unsqueeze(1)).squeeze(1) - tgt
+    return loss.detach(), q_cur.detach(), best, tgt, diff
+
+
+def ddqn_latent_update(online, target, grads, mask, mask_n, latent, latent_n, first_latent, actions, rewards, denom, budget, gamma):
+    """The device work of one double-DQN update of a ``Latent_Model`` (reference ``policies/DDQN/ddqn.py:81-115`` and the backward)
+    -> ``(loss, q_cur (B, A), best_next int32 (B,), target (B,), diff (B,))``; ``grads`` = [(dweight, dbias), ..] per layer of
+    ``online`` are OVERWRITTEN with the loss gradient.  ``online`` / ``target``: two ``PolicyTable`` of the same sizes, no transform.
+    No autograd.  GPU operands inside the limits run ``a3vt_ddqn_latent_update``: three launches, no host sync, every output with
+    the bits of ``latent_policy_fwd`` x 3, ``ddqn_td``, its backward under a unit gradient and ``latent_policy_bwd(accumulate=False)``.
+    Everything else takes the same contract on torch ops."""
+    B = _policy_inputs(online, mask, latent, first_latent, None)
+    _policy_inputs(online, mask_n, latent_n, first_latent, None)
+    if [(tuple(w.shape), r) for w, _, r in online.layers] != [(tuple(w.shape), r) for w, _, r in target.layers] or \
+            online.concat_at != target.concat_at:
+        raise RuntimeError("a3vt: ddqn_latent_update wants an online and a target table of the same layers")
+    for t, name in ((actions, "actions"), (rewards, "rewards"), (denom, "denom")):
+        if t is None and name == "denom":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != (B,) or t.device != mask.device:
+            raise RuntimeError(f"a3vt: ddqn_latent_update `{name}` must be a float32 ({B},) tensor on the mask's device")
+    if len(grads) != len(online.layers):
+        raise RuntimeError("a3vt: ddqn_latent_update wants one (dweight, dbias) pair per layer")
+    for l, ((dw, db), (w, b, _)) in enumerate(zip(grads, online.layers)):
+        if dw.shape != w.shape or db.shape != b.shape or dw.dtype != torch.float32 or db.dtype != torch.float32 or \
+                not (dw.is_contiguous() and db.is_contiguous()) or dw.device != w.device or db.device != b.device:
+            raise RuntimeError(f"a3vt: ddqn_latent_update gradient {l} must be contiguous float32 and of its parameter's shape and device")
+    if not (ddqn_latent_supported(online, mask) and target.in_limits() and target.layers[0][0].device == mask.device
+            and target.transform is None and B <= LATENT_POLICY_MAX["rows"]):
+        return _ddqn_latent_update_torch(online, target, grads, mask, mask_n, latent, latent_n, first_latent, actions, rewards, denom,
+                                         budget, gamma)
+    L = _lib.load()
+    mask, mask_n, latent, latent_n, first_latent = (_req(t, n) for t, n in ((mask, "mask"), (mask_n, "mask_n"), (latent, "latent"),
+                                                                            (latent_n, "latent_n"), (first_latent, "first_latent")))
+    actions, rewards = _req(actions, "actions"), _req(rewards, "rewards")
+    denom = None if denom is None else _req(denom, "denom")
+    g = _lib.MlpGrads()
+    for l, (dw, db) in enumerate(grads):
+        g.dweight[l], g.dbias[l] = dw.data_ptr(), db.data_ptr()
+    dev, A = mask.device, online.num_actions
+    q_cur = torch.empty((B, A), dtype=torch.float32, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    tgt, diff = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    scratch = workspace("ddqn_latent", B * (2 * A + 2 * online.stash_floats) * 4, dev)
+    _lib.check(L.a3vt_ddqn_latent_update(ctypes.byref(online.struct()), ctypes.byref(target.struct()), ctypes.byref(g), _lib.ptr(mask),
+                                         _lib.ptr(mask_n), _lib.ptr(latent), _lib.ptr(latent_n), _lib.ptr(first_latent),
+                                         _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(denom), B, int(budget), float(gamma),
+                                         _lib.ptr(q_cur), _lib.ptr(best), _lib.ptr(tgt), _lib.ptr(diff), _lib.ptr(loss),
+                                         _lib.ptr(scratch), _stream()), "ddqn_latent_update")
+    return loss, q_cur, best, tgt, diff
+
+
 class QnetInputFn(torch.autograd.Function):
     """Features + layer 0 of the DDQN graph model on ``a3vt_qnet_input_fwd/bwd`` (csrc/qnet_input.hip).  ``mesh`` (B, N, 4);
     the composites ``comp_s`` (B, npad), ``comp_t`` (4, npad), ``comp_c`` (50, npad) come padded to npad = pad4(h) columns."""

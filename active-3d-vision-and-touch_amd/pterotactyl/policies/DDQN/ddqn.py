@@ -8,9 +8,16 @@ do the batches a host replay memory hands over (a replay built with ``device=`` 
 
 New knob (no reference counterpart): ``args.fused_q_input`` — ``Graph_Model``'s features and layer 0 on ``ops.qnet_input``.  When
 ``args`` does not carry it, ``get_model`` sets it to ``FUSED_Q_INPUT_DEFAULT``: on, because ``tools/ddqn_bench.py`` measured the fused
-update's p90 below the unfused one's p10 on an MI355X (``profiles/ddqn_update_ab.txt``)."""
+update's p90 below the unfused one's p10 on an MI355X (``profiles/ddqn_update_ab.txt``).
+
+New knob: ``args.fused_q_latent`` — off unless ``args`` sets it (``DDQN.train.Engine`` sets it).  With it a ``Latent_Model`` on the
+GPU is updated without autograd: ``ops.ddqn_latent_update`` (three launches: the three forwards side by side, TD and deltas,
+gradients and loss) writes the gradients into ``p.grad`` tensors this learner owns, overwritten every update, then the same
+one-launch Adam follows; ``get_action`` is ``ops.ddqn_latent_q`` (one launch: values and the penalised argmax) and one copy of E
+int32.  ``last_q`` / ``last_best_next`` / ``last_target`` stay, and the only sync of an update is still the ``loss.item()``."""
 import random
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -34,6 +41,8 @@ class DDQN(nn.Module):
         self.replay = replay
         self.optimizer = _optim.Adam(self.model.parameters(), lr=args.lr, grad_clamp=1.0)
         self.random_sampler = baselines.random_sampler(self.args)
+        self._latent_grads = None      # (table, [(dweight, dbias), ..]): the p.grad tensors of the fused latent update
+        self.copied = []               # (shape, dtype) of every tensor a fused action choice brought to the host (tests)
 
     @property
     def device(self):
@@ -71,6 +80,8 @@ class DDQN(nn.Module):
         batch = {k: v.to(dev, torch.float32) for k, v in batch.items()}    # (a device replay hands these over in place)
         norm = self.args.normalization
         denom = batch["first_score"] if norm == "first" else (batch["score"] if norm == "current" else None)
+        if self._fused_latent(batch["mask"]) and isinstance(getattr(target_net, "model", None), model.Latent_Model):
+            return self._fused_latent_update(batch, denom, target_net)
         q_cur = self.forward(batch, penalize=False)
         with torch.no_grad():
             q_next_online = self.forward(batch, next=True, penalize=False)     # penalised by the CURRENT mask inside ddqn_td
@@ -84,6 +95,34 @@ class DDQN(nn.Module):
         self.optimizer.step()          # clamps every gradient to [-1, 1] in place, then Adam
         return loss.item()
 
+    def _fused_latent(self, mask):
+        return isinstance(self.model, model.Latent_Model) and self.model.fused_q_latent and torch.is_tensor(mask) and \
+            self.model.fused_ok(mask)
+
+    def _owned_grads(self, table):
+        """The gradient tensors of the fused update: ``p.grad`` of the table's parameters, kept here and overwritten every update
+        (so the optimizer's pointer table stays the same from step to step)."""
+        if self._latent_grads is None or self._latent_grads[0] is not table or \
+                any(w.grad is not dw or b.grad is not db for (w, b, _), (dw, db) in zip(table.layers, self._latent_grads[1])):
+            grads = []
+            for w, b, _ in table.layers:
+                w.grad, b.grad = torch.zeros_like(w), torch.zeros_like(b)
+                grads.append((w.grad, b.grad))
+            self._latent_grads = (table, grads)
+        return self._latent_grads[1]
+
+    def _fused_latent_update(self, batch, denom, target_net):
+        net = self.model
+        table = net.table()
+        mask, latent, first_latent = net.inputs(batch)
+        mask_n, latent_n, _ = net.inputs(batch, next=True)
+        with torch.no_grad():
+            loss, self.last_q, self.last_best_next, self.last_target, _ = _ops.ddqn_latent_update(
+                table, target_net.model.table(), self._owned_grads(table), mask, mask_n, latent, latent_n, first_latent,
+                batch["actions"], batch["rewards"], denom, self.args.budget, self.args.gamma)
+        self.optimizer.step()          # clamps every gradient to [-1, 1] in place, then Adam
+        return loss.item()
+
     def forward(self, obs, next=False, penalize=True):
         value = self.model(obs, next=next)
         if penalize:
@@ -94,6 +133,14 @@ class DDQN(nn.Module):
         sample = random.random()
         if sample < eps_threshold or give_random:
             return self.random_sampler.get_action(obs["mask"])
+        if isinstance(self.model, model.Latent_Model) and self.model.fused_q_latent:
+            mask, latent, first_latent = self.model.inputs(obs)
+            if self.model.fused_ok(mask):
+                self.model.eval()
+                _, action = _ops.ddqn_latent_q(self.model.table(), mask, latent, first_latent, mask)
+                action = action.cpu()
+                self.copied.append((tuple(action.shape), action.dtype))
+                return action.numpy().astype(np.int64)
         with torch.no_grad():
             self.model.eval()
             q_values = self(obs)

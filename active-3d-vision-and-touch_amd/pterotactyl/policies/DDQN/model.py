@@ -5,7 +5,13 @@
 (300 -> hidden_dim ... -> num_actions; the last aggregates every channel, no ReLU), max over vertices.  The graph
 layers run as ``a3vt_gcn_layer_fwd/bwd`` calls through ``vision.model.GCN_layer``; the adjacency is the dense
 ``adj['adj']`` the reference keeps (:68), converted to CSR once.  ``Latent_Model`` (:15-61) is a plain MLP over
-auto-encoder latents and stays on torch ops.
+auto-encoder latents.
+
+``args.fused_q_latent`` (new, no reference counterpart; off unless ``args`` sets it; ``DDQN.train.Engine`` sets it): the learner
+evaluates and updates ``Latent_Model`` through ``ops.ddqn_latent_q`` / ``ops.ddqn_latent_update`` (csrc/ddqn_latent.hip) on
+``table()``, the ``ops.PolicyTable`` of the module's own parameter tensors.  ``forward`` itself stays on the torch modules: the
+knob changes what ``DDQN.get_action`` and ``DDQN.update_parameters`` call, not this module's outputs.  Same parameters, same state
+dict; ``load_state_dict`` copies in place, so a table stays valid across target updates.
 
 ``args.fused_q_input`` (new, no reference counterpart; off unless set; ``DDQN.get_model`` sets it): the features and layer 0 run
 as ``ops.qnet_input`` (csrc/qnet_input.hip), which never forms the (B N) x 300 feature rows.  Same parameters, same state dict.
@@ -43,6 +49,26 @@ class Latent_Model(nn.Module):
                 mods.append(nn.ReLU())
             layers.append(nn.Sequential(*mods))
         self.model = nn.Sequential(*layers)
+        self.fused_q_latent = bool(getattr(args, "fused_q_latent", False))
+        self._table = None
+
+    def table(self):
+        """The ``ops.PolicyTable`` of this model's parameters, no output transform (rebuilt when a parameter tensor was replaced)."""
+        seqs = list(self.action_model) + list(self.model)
+        params = [t for seq in seqs for t in (seq[0].weight, seq[0].bias)]
+        if self._table is None or any(a is not b for a, b in zip(self._table.params(), params)):
+            self._table = _ops.PolicyTable([(seq[0].weight, seq[0].bias, len(seq) > 1) for seq in seqs], len(self.action_model), None)
+        return self._table
+
+    def inputs(self, obs, next=False):
+        """(mask, latent, first_latent) of an observation or a replay batch on the model's device, as float32."""
+        dev = self.model[0][0].weight.device
+        sfx = "_n" if next else ""
+        return _dev(obs["mask" + sfx], dev), _dev(obs["latent" + sfx], dev), _dev(obs["first_latent"], dev)
+
+    def fused_ok(self, mask):
+        """Whether the learner takes the fused ops for this input: the knob, a 2-d mask on the GPU, sizes inside the kernels'."""
+        return bool(self.fused_q_latent and mask.is_cuda and mask.dim() == 2 and _ops.ddqn_latent_supported(self.table(), mask))
 
     def forward(self, obs, next=False):
         dev = self.model[0][0].weight.device

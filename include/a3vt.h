@@ -610,6 +610,44 @@ int a3vt_latent_policy_bwd(const a3vt_mlp *net, const a3vt_mlp_grads *grads, con
                            void *stream);
 int a3vt_latent_policy_launches(long long *counts /*[3]*/, int reset);
 
+/* DDQN's Latent_Model (policies/DDQN/model.py:15-61) on the layer table above: an a3vt_mlp with transform 0 whose last layer has
+ * A <= 304 outputs (the actions).  The forward, the deltas and the gradients are the sums of a3vt_latent_policy_fwd / _bwd, the TD rule
+ * is a3vt_ddqn_td's — the same device code, not a second summation order.
+ *
+ * a3vt_ddqn_latent_q: one launch.  q [rows][A] always written, unpenalised: bit-identical to a3vt_latent_policy_fwd's values.  With
+ * mask_penalty ([rows][A] fp32; the observation's mask) `action` [rows] int32 is required and receives
+ * argmax_a (mask_penalty[e][a] > 0 ? -1e10 : q[e][a]) under a3vt_ddqn_td's rule: the lowest index on a tie, so index 0 when every
+ * action is taken.  mask_penalty and action are NULL together.
+ *
+ * a3vt_ddqn_latent_update: one update's device work as three launches.  `online` and `target_net` are two tables of the same layer
+ * sizes; mask, mask_n [batch][layer[0].in] (mask is also the [batch][A] table of taken actions: layer[0].in == A for this model, and
+ * the entry point reads A columns of it), latent, latent_n, first_latent [batch][latent_size]; actions [batch] fp32, clamped into
+ * [0, A) as in a3vt_ddqn_td; rewards [batch]; denom [batch] or NULL.
+ *   (1) a batch x 3 grid of workgroups, one role each: online(mask, latent) -> q_cur with the stash kept, online(mask_n, latent_n),
+ *       target_net(mask_n, latent_n); first_latent is shared.
+ *   (2) a workgroup per row: a3vt_ddqn_td's sample rule (penalised by the CURRENT mask, target = fadd(fmul(gamma, next), reward)) ->
+ *       best_next, target_out, diff; dq[a] = (1 * 2 * diff) / batch at the action and 0 elsewhere, kept in LDS; then the deltas of
+ *       a3vt_latent_policy_bwd (1), every term summed, zero ones too.
+ *   (3) a workgroup per (layer, slab of 8 rows): dweight / dbias of a3vt_latent_policy_bwd (2), overwriting; one more workgroup
+ *       reduces loss[0] = mean(diff^2) by a3vt_ddqn_td's pairwise tree.
+ * Every output (q_cur [batch][A], best_next, target_out, diff [batch], loss [1], the gradients) is bit-identical to
+ * a3vt_latent_policy_fwd x 3, a3vt_ddqn_td, a3vt_ddqn_td_bwd with grad_loss = 1 and a3vt_latent_policy_bwd with accumulate = 0 on the
+ * same operands.  scratch: a3vt_ddqn_latent_scratch_bytes(online, batch) bytes, caller-provided (0 for a refused table or batch).
+ *
+ * Limits: those of a3vt_latent_policy_* for the tables (widths <= 1024, 16 layers) and of a3vt_ddqn_td (batch, rows <= 4096,
+ * A <= 304).  Anything else, transform != 0, tables that differ in a layer size, a null required pointer or a misaligned one (weights 16
+ * bytes where in % 4 == 0, everything else 4) returns non-zero with a message that names the value, and launches nothing.  No atomics,
+ * no fence between workgroups, no host synchronisation, no allocation: the same bits on every call.
+ * a3vt_ddqn_latent_launches: kernel launches since the last reset ([0] a3vt_ddqn_latent_q, [1] a3vt_ddqn_latent_update); returns 2. */
+size_t a3vt_ddqn_latent_scratch_bytes(const a3vt_mlp *online, int batch);
+int a3vt_ddqn_latent_q(const a3vt_mlp *net, const float *mask, const float *latent, const float *first_latent, const float *mask_penalty,
+                       int rows, float *q, int32_t *action, void *stream);
+int a3vt_ddqn_latent_update(const a3vt_mlp *online, const a3vt_mlp *target_net, const a3vt_mlp_grads *grads, const float *mask,
+                            const float *mask_n, const float *latent, const float *latent_n, const float *first_latent,
+                            const float *actions, const float *rewards, const float *denom, int batch, int budget, float gamma,
+                            float *q_cur, int32_t *best_next, float *target_out, float *diff, float *loss, void *scratch, void *stream);
+int a3vt_ddqn_latent_launches(long long *counts /*[2]*/, int reset);
+
 /* Graph_Model's features and layer 0 (policies/DDQN/model.py:100-118) without the (batch * n_vert) x 300 feature rows:
  *   y = relu(layer0([a_b | PE(p) | E[token]])) = relu(agg(S[b] + T[token] + relu(L2(relu(L1(nerf(p) ++ p)))) C))
  * with the composites S = a Wa + b3 Wp [batch][npad], T = E Wm [4][npad], C = W3^T Wp [50][npad] formed by the caller
