@@ -43,10 +43,13 @@ def install_as_pterotactyl():
         "pterotactyl.policies.DDQN.train": ".pterotactyl.policies.DDQN.train",
         "pterotactyl.policies.supervised.model": ".pterotactyl.policies.supervised.model",
         "pterotactyl.policies.supervised.train": ".pterotactyl.policies.supervised.train",
+        "pterotactyl.policies.dataset_specific.LEBA": ".pterotactyl.policies.dataset_specific.LEBA",
+        "pterotactyl.policies.dataset_specific.MFBA": ".pterotactyl.policies.dataset_specific.MFBA",
     }
     for parent in ("pterotactyl", "pterotactyl.reconstruction", "pterotactyl.reconstruction.vision",
                    "pterotactyl.reconstruction.autoencoder", "pterotactyl.policies", "pterotactyl.policies.DDQN",
                    "pterotactyl.policies.baselines", "pterotactyl.policies.supervised",
+                   "pterotactyl.policies.dataset_specific",
                    "pterotactyl.utility"):
         if parent not in sys.modules:
             try:

@@ -1338,6 +1338,43 @@ int a3vt_latent_nearest(const float *bank, const int32_t *bank_actions, int bank
                                scratch, static_cast<hipStream_t>(stream));
 }
 
+// ---- the dataset-specific policies' candidate tally (candidate_tally.hip) --------------------------------------------------------
+int a3vt_candidate_tally(const float *scores, const int32_t *candidates, const float *first_score, const float *taken, int K, int E, int A,
+                         double unvisited, double *sums, double *checks, double *votes, int32_t *best, float *best_score, void *stream) {
+  if (K < 1 || K > kTallyMaxCandidates || E < 1 || E > kTallyMaxElements || A < 1 || A > kTallyMaxActions) {
+    set_error("candidate_tally: K=%d (1..%d) E=%d (1..%d) A=%d (1..%d) unsupported", K, kTallyMaxCandidates, E, kTallyMaxElements, A,
+              kTallyMaxActions);
+    return -1;
+  }
+  const struct {
+    const char *name;
+    const void *p;
+    bool required;
+    unsigned align;
+    const char *why;
+  } ptrs[] = {{"scores", scores, true, 4, "required"},
+              {"candidates", candidates, true, 4, "required"},
+              {"first_score", first_score, sums != nullptr, 4, "required with sums"},
+              {"taken", taken, false, 4, ""},
+              {"sums", sums, checks != nullptr, 8, "sums and checks go together"},
+              {"checks", checks, sums != nullptr, 8, "sums and checks go together"},
+              {"votes", votes, false, 8, ""},
+              {"best", best, votes != nullptr, 4, "required with votes"},
+              {"best_score", best_score, false, 4, ""}};
+  for (const auto &a : ptrs) {
+    if (a.required && !a.p) {
+      set_error("candidate_tally: %s=NULL: %s", a.name, a.why);
+      return -1;
+    }
+    if (!aligned_to(a.p, a.align)) {
+      set_error("candidate_tally: %s=%p is not %u-byte aligned", a.name, a.p, a.align);
+      return -1;
+    }
+  }
+  return launch_candidate_tally(scores, candidates, first_score, taken, K, E, A, unvisited, sums, checks, votes, best, best_score,
+                                static_cast<hipStream_t>(stream));
+}
+
 // ---- the supervised latent policy's value network (latent_policy.hip) ------------------------------------------------------------
 namespace {
 static_assert(sizeof(a3vt_mlp) == sizeof(PolicyNet) && sizeof(a3vt_mlp_layer) == sizeof(PolicyLayer) &&

@@ -382,6 +382,13 @@ int launch_latent_nearest(const float *bank, const int32_t *bank_actions, int ba
                           const float *taken, int n_queries, int num_actions, int k, int32_t *idx, float *dist, int32_t *action,
                           int32_t *rank, void *scratch, hipStream_t s);
 
+// candidate_tally.hip: the dataset-specific policies' bookkeeping on one (K, E) score table (policies/dataset_specific/LEBA.py:115-128,
+// MFBA.py:95-99): greedy choice, LEBA's ratio sums and visit counts, MFBA's votes — one launch
+constexpr int kTallyMaxCandidates = 304, kTallyMaxElements = 1024, kTallyMaxActions = 304;
+int launch_candidate_tally(const float *scores, const int32_t *candidates, const float *first_score, const float *taken, int K, int E,
+                           int A, double unvisited, double *sums, double *checks, double *votes, int32_t *best, float *best_score,
+                           hipStream_t s);
+
 // latent_policy.hip: the supervised policy's value network (policies/supervised/model.py), its loss and its backward.  The layer
 // table travels by value in the kernel arguments (a3vt_mlp of include/a3vt.h, field for field).
 constexpr int kPolicyMaxLayers = 16;     // layers of a table

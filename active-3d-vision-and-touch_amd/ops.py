@@ -1175,6 +1175,128 @@ def latent_nearest(bank, bank_actions, queries, taken, k):
     return idx, dist, action, rank
 
 
+# csrc/kernels.h's kTallyMaxCandidates / kTallyMaxElements / kTallyMaxActions
+CANDIDATE_TALLY_MAX = dict(K=304, E=1024, A=304)
+
+
+def _candidate_tally_check(scores, candidates, first_score, taken, sums, checks, votes):
+    """Shapes, dtypes and limits of ``candidate_tally`` (both forms) -> (K, E, A)."""
+    def want(t, name, dtype):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"a3vt: candidate_tally `{name}` must be a {dtype} tensor, got "
+                             f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.device != scores.device and not (name == "candidates" and not t.is_cuda):
+            raise ValueError(f"a3vt: candidate_tally `{name}` is on {t.device}, the scores on {scores.device}")
+    want(scores, "scores", torch.float32)
+    want(candidates, "candidates", torch.int32)
+    if scores.dim() != 2 or candidates.shape != scores.shape:
+        raise ValueError(f"a3vt: candidate_tally wants scores (K, E) and candidates (K, E), got {tuple(scores.shape)} and "
+                         f"{tuple(candidates.shape)}")
+    K, E = scores.shape
+    state = [(t, name) for t, name in ((sums, "sums"), (checks, "checks"), (votes, "votes")) if t is not None]
+    if (sums is None) != (checks is None):
+        raise ValueError("a3vt: candidate_tally wants `sums` and `checks` together or neither")
+    for t, name in state:
+        want(t, name, torch.float64)
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"a3vt: candidate_tally `{name}` must be a contiguous (A,) tensor (it is updated in place), got "
+                             f"{tuple(t.shape)}")
+    if taken is not None:
+        want(taken, "taken", torch.float32)
+        if taken.dim() != 2 or taken.shape[0] != E:
+            raise ValueError(f"a3vt: candidate_tally `taken` must be ({E}, A), got {tuple(taken.shape)}")
+    widths = {name: int(t.shape[0]) for t, name in state}
+    if taken is not None:
+        widths["taken"] = int(taken.shape[1])
+    if not widths:
+        raise ValueError("a3vt: candidate_tally needs `taken` or a state tensor to know the number of actions A")
+    A = next(iter(widths.values()))
+    if any(w != A for w in widths.values()):
+        raise ValueError(f"a3vt: candidate_tally: the number of actions differs: {widths}")
+    if sums is not None:
+        want(first_score, "first_score", torch.float32)
+        if first_score.shape != (E,):
+            raise ValueError(f"a3vt: candidate_tally `first_score` must be ({E},), got {tuple(first_score.shape)}")
+    lim = CANDIDATE_TALLY_MAX
+    if not (1 <= K <= lim["K"] and 1 <= E <= lim["E"] and 1 <= A <= lim["A"]):
+        raise ValueError(f"a3vt: candidate_tally K={K} E={E} A={A} outside 1..{lim}")
+    return K, E, A
+
+
+def _candidate_tally_host(scores, candidates, first_score, taken, sums, checks, votes, unvisited):
+    """The contract of ``a3vt_candidate_tally`` (include/a3vt.h) on NumPy views of CPU tensors: the choice as a stable
+    lexicographic sort per element, the tally as the ordered walk it is."""
+    K, E = scores.shape
+    s, c = scores.numpy(), candidates.numpy()
+    A = (sums if sums is not None else votes).shape[0] if taken is None else taken.shape[1]
+    inside = (c >= 0) & (c < A)
+    open_ = inside.copy()
+    if taken is not None:
+        open_ &= taken.numpy()[np.arange(E)[None, :], np.clip(c, 0, A - 1)] == 0
+    nan = np.isnan(s)
+    rank = np.where(open_, nan.astype(np.int64), 2)                       # eligible number < eligible NaN < not eligible
+    value = np.where(nan | ~open_, 0.0, s.astype(np.float64))
+    best = np.full(E, -1, dtype=np.int32)
+    best_score = np.full(E, np.inf, dtype=np.float32)
+    for e in range(E):
+        k = np.lexsort((value[:, e], rank[:, e]))[0]                      # (stable: a tie, -0 == +0 included, goes to the lower k)
+        if open_[k, e]:
+            best[e], best_score[e] = c[k, e], s[k, e]
+    if sums is not None:
+        ratio = s / first_score.numpy()[None, :]                          # fp32 / fp32, correctly rounded
+        acc, n = sums.numpy(), checks.numpy()
+        for k in range(K):
+            for e in range(E):
+                a = c[k, e]
+                if not inside[k, e]:
+                    continue
+                acc[a] = np.float64(ratio[k, e]) if acc[a] == unvisited else np.float64(np.float32(acc[a]) + ratio[k, e])
+                n[a] += 1.0
+    if votes is not None:
+        v = votes.numpy()
+        for e in range(E):
+            if best[e] >= 0:
+                v[best[e]] += 1.0
+    return torch.from_numpy(best), torch.from_numpy(best_score)
+
+
+def candidate_tally(scores, candidates, first_score, taken, sums=None, checks=None, votes=None, unvisited=1e10):
+    """What the dataset-specific policies do with one swept batch's score table (reference ``policies/dataset_specific/LEBA.py:115-128``,
+    ``MFBA.py:95-99``) -> ``(best (E,) int32, best_score (E,) float32)``.  ``scores`` (K, E) float32 and ``candidates`` (K, E)
+    int32 (``candidates[k, e]``: the action candidate k tries on element e); ``taken`` (E, A) float32, non-zero = performed, or
+    None.  ``best[e]`` is the candidate of the lowest score among the pairs ``taken`` leaves open (ties to the lower k, NaN after
+    +inf, -1 / +inf when none is open).  ``sums`` / ``checks`` (A,) float64, updated IN PLACE: for k, then e, ascending, the
+    fp32 ratio ``scores[k, e] / first_score[e]`` replaces a sum that equals ``unvisited`` and is otherwise added to it in fp32,
+    and the action's count goes up by one.  ``votes`` (A,) float64, in place: one per element for its ``best``.  The whole
+    contract is in ``include/a3vt.h``.  GPU tensors run ``a3vt_candidate_tally`` (csrc/candidate_tally.hip: one launch, no host
+    synchronisation); CPU tensors take the same contract on NumPy.
+
+    A table with a candidate outside ``[0, A)`` is refused.  ``candidates`` may stay on the host beside GPU ``scores`` (the
+    policies build it there): it is then checked for free and uploaded.  A table already on the GPU is read back once for the
+    check, which waits for the device."""
+    K, E, A = _candidate_tally_check(scores, candidates, first_score, taken, sums, checks, votes)
+    low, high = int(candidates.min()), int(candidates.max())
+    if low < 0 or high >= A:
+        raise ValueError(f"a3vt: candidate_tally: candidates outside [0, {A}): min {low}, max {high}")
+    if not scores.is_cuda:
+        return _candidate_tally_host(scores, candidates, first_score, taken, sums, checks, votes, float(unvisited))
+    return _candidate_tally_launch(scores, candidates.to(scores.device), first_score, taken, sums, checks, votes, unvisited, K, E, A)
+
+
+def _candidate_tally_launch(scores, candidates, first_score, taken, sums, checks, votes, unvisited, K, E, A):
+    """The library call of ``candidate_tally`` on checked GPU tensors (the candidates' range is the caller's to vouch for)."""
+    L = _lib.load()
+    scores, candidates = scores.contiguous(), candidates.contiguous()
+    first_score = None if first_score is None or sums is None else first_score.contiguous()
+    taken = None if taken is None else taken.contiguous()
+    best = torch.empty(E, dtype=torch.int32, device=scores.device)
+    best_score = torch.empty(E, dtype=torch.float32, device=scores.device)
+    _lib.check(L.a3vt_candidate_tally(_lib.ptr(scores), _lib.ptr(candidates), _lib.ptr(first_score), _lib.ptr(taken), K, E, A,
+                                      float(unvisited), _lib.ptr(sums), _lib.ptr(checks), _lib.ptr(votes), _lib.ptr(best),
+                                      _lib.ptr(best_score), _stream()), "candidate_tally")
+    return best, best_score
+
+
 # csrc/kernels.h's kPolicyMaxRows / kPolicyMaxWidth / kPolicyMaxLayers (a3vt_latent_policy_limit returns the library's own): rows
 # of a call (and steps of the loss), every layer's in and out, layers of a table.
 LATENT_POLICY_MAX = dict(rows=4096, width=1024, layers=16)

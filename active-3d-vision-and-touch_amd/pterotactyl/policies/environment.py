@@ -228,9 +228,10 @@ class ActiveTouch:
         self.candidate_scores = scores
         return choose_actions(scores, candidates, self.current_data["mask"], full), scores
 
-    def score_candidates(self, candidates):
+    def score_candidates(self, candidates, to_host=True):
         """(K, E) host scores of K candidate action lists: what K ``check_step`` calls would score, as one batch of K*E meshes
-        (in chunks of ``args.candidate_chunk`` candidates).  The state is left alone."""
+        (in chunks of ``args.candidate_chunk`` candidates).  The state is left alone.  ``to_host=False`` leaves the table on
+        the device (for ``ops.candidate_tally``)."""
         K, E = len(candidates), self.args.env_batch_size
         chunk = getattr(self.args, "candidate_chunk", None) or K
         batch = self.current_data["batch"]
@@ -252,7 +253,8 @@ class ActiveTouch:
             score, _, _ = scoring.score_actions(self.deform, batch["img"], charts_list, gt, self.mesh_info["faces"],
                                                 self.args.number_points, self.args.loss_coeff, samples=samples)
             scores.append(score)
-        return torch.cat(scores).cpu()
+        scores = torch.cat(scores)
+        return scores.cpu() if to_host else scores
 
     # check the result of perfroming a specific action
     def check_step(self, actions):

@@ -546,6 +546,56 @@ int a3vt_latent_nn_query_floats(void);
 int a3vt_latent_nn_cached_rows(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * The dataset-specific policies' bookkeeping on one (K, E) score table (policies/dataset_specific/LEBA.py:115-128, MFBA.py:95-99).
+ *
+ * a3vt_candidate_tally makes one launch on `stream`.  It does no allocation, no host synchronisation and no atomics, and gives the
+ * same bits on every call.
+ *   scores      [K][E]
+ *   candidates  [K][E]: the action candidate k tries on element e
+ *   first_score [E], or NULL when sums is NULL
+ *   taken       [E][A] fp32, non-zero = performed (obs["mask"] as it is); NULL excludes nothing
+ *   unvisited   LEBA's sentinel, 1e10
+ *   sums, checks [A] in/out, both or neither
+ *   votes       [A] in/out or NULL
+ *   best, best_score [E] out; best required when votes is given
+ *
+ * Greedy choice.
+ * - best[e] is candidates[k][e] of the lowest scores[k][e] over k ascending.
+ * - Only pairs with taken == NULL or taken[e][a] == 0 are eligible.
+ * - A tie goes to the lower k.
+ * - A NaN ranks after +inf.  This is the ordering rule of a3vt_latent_nearest and a3vt_latent_policy_fwd.
+ * - The results are -1 and +inf when no pair is eligible.
+ * - For tables without NaN this is environment.choose_actions.
+ *
+ * LEBA tally (reference LEBA.py:115-128).
+ * - It runs for k ascending and, within k, e ascending, with a = candidates[k][e].
+ * - r = scores[k][e] / first_score[e] is one correctly rounded fp32 division (__fdiv_rn in the kernel; no compiler flag decides it).
+ * - If sums[a] == unvisited, compared in double, then sums[a] = (double)r.
+ * - Otherwise sums[a] = (double)((float)sums[a] + r).
+ * - The running sum is rounded to fp32 at every add and stored as a double.  That is what the reference computes: NumPy's
+ *   float64 scalar + a 0-d fp32 torch tensor defers to torch and returns an fp32 tensor.
+ * - checks[a] += 1.0 in double.
+ * - The taken mask plays no part in the tally.
+ *
+ * MFBA votes (MFBA.py:98-99).
+ * - For e ascending: votes[best[e]] += 1.0 in double when best[e] >= 0.
+ *
+ * Shared rules.
+ * - A candidate outside [0, A) is skipped by every rule and never indexes taken, sums, checks or votes.  The Python layer refuses
+ *   such a table.
+ * - All updates of one action happen in the stated order whatever the launch geometry.
+ *
+ * Limits.
+ * - 1 <= K <= 304.
+ * - 1 <= E <= 1024.
+ * - 1 <= A <= 304.
+ * - Pointers are 4-byte aligned, the doubles 8-byte aligned.
+ * - Anything else, or a missing required pointer, returns non-zero with a message in a3vt_last_error that names the argument and
+ *   its value.  Nothing is launched. */
+int a3vt_candidate_tally(const float *scores, const int32_t *candidates, const float *first_score, const float *taken, int K, int E, int A,
+                         double unvisited, double *sums, double *checks, double *votes, int32_t *best, float *best_score, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The supervised latent policy's value network (policies/supervised/model.py, train.py:119-158), fp32 throughout.
  *
  * The network is a table of at most 16 layers, read on the host and passed to the kernels by value.  Layer l computes

@@ -1,0 +1,195 @@
+"""The dataset-specific policies LEBA and MFBA (``policies/dataset_specific``) on the GPU against ``g22_dataset_specific.npz``,
+recorded from the reference's own engines (``tests/golden/make_golden_dataset_specific.py``): three sweeps each — full search,
+limited search, full search — over the two swept batches of five, then ``validate`` on two batches, with the fixture's sensor
+records injected through a ``RecordedSampler``; run with ``fused_tally`` on and off.
+
+Bounds.  ``chosen_actions``, ``checks``, ``counts`` and MFBA's per-batch greedy actions are equal.  ``action_scores`` and the
+validate scores are within 1e-4 relative (``helpers.rel_err``), the bound of the environment's scores against g18-g21.  The
+generator asserts that every decision of the reference has a gap one hundred times that (1e-2 between the two lowest eligible
+scores of a greedy decision and between the two lowest mean ratios of a sweep; one vote between the two most voted actions), so
+equal decisions follow from the score bound.  Largest differences seen on an MI355X: action_scores 1.5e-7, validate scores
+3.0e-7 (relative).
+
+Knob on against knob off, on the same injected draws: LEBA's ``action_scores`` and MFBA's ``counts`` are bit-equal after every
+sweep, and the checkpoint files hold equal data."""
+import numpy as np
+import pytest
+import torch
+
+import tally_util as tl
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def golden():
+    from golden_util import load
+    return load(tl.FIXTURE)
+
+
+@pytest.fixture(autouse=True)
+def restore_process_flags():
+    """``ActiveTouch.seed`` sets torch's convolution flags process-wide, as the reference does; other tests get them back."""
+    b = torch.backends.cudnn
+    kept = (b.deterministic, b.benchmark)
+    yield
+    b.deterministic, b.benchmark = kept
+
+
+@pytest.fixture(scope="module")
+def locations(cuda, golden, tmp_path_factory):
+    """The checkpoint directories of this package's models built by the fixture's recipe (checksums asserted)."""
+    import env_util as eu
+    import touch_util as tu
+    from golden_util import state_sha256
+    from a3vt_amd.pterotactyl.reconstruction.autoencoder import model as auto_model
+    from a3vt_amd.pterotactyl.reconstruction.touch import model as touch_model
+    from a3vt_amd.pterotactyl.reconstruction.vision import model as vision_model
+    from a3vt_amd.pterotactyl.utility import utils
+    bn = {k[3:]: torch.from_numpy(golden[k]) for k in golden.files if k.startswith("bn:")}
+    models = eu.build_models(tl.CASE, touch_model, vision_model, auto_model, utils, "vision_charts", bn=bn)
+    for kind, (_, net) in models.items():
+        sd = tu.non_bn_state(net.state_dict()) if kind == "touch" else net.state_dict()
+        assert (state_sha256(sd) == golden[f"sha:{kind}"]).all(), f"the seeded {kind} model is not the fixture's"
+    return eu.write_models(str(tmp_path_factory.mktemp("g22")), models)
+
+
+@pytest.fixture(scope="module")
+def recorded(golden):
+    """The fixture's sensor records and batches, built once."""
+    seed = int(golden["seed"])
+    return tl.records(seed), tl.batches(seed, "train"), tl.batches(seed, "valid")
+
+
+def run_engine(name, fused, golden, locations, recorded, monkeypatch, tmp_path):
+    """Three sweeps and a validation of this package's engine -> what the fixture stores, and the checkpoint after each sweep."""
+    from a3vt_amd.pterotactyl.policies import environment, recorded as rec
+    from a3vt_amd.pterotactyl.policies.dataset_specific import LEBA, MFBA
+    module = {"leba": LEBA, "mfba": MFBA}[name]
+    records, train, valid = recorded
+    monkeypatch.setattr(environment.ActiveTouch, "get_loaders", lambda self: None)
+    monkeypatch.chdir(tmp_path)
+    engine = module.Engine(tl.engine_args(False, fused_tally=fused, **locations), sampler=rec.RecordedSampler(records),
+                           loaders=(train, valid))
+    engine.env = environment.ActiveTouch(engine.args, sampler=engine.sampler)
+    engine.env.score_samples = (torch.from_numpy(golden["face_idx"].astype(np.int32)), torch.from_numpy(golden["u"]),
+                                torch.from_numpy(golden["v"]))
+    engine.chosen_actions, engine.step, engine.spot = [], 0, 0
+    engine.reset_state()
+    engine.checkpoint_dir = str(tmp_path)
+    engine.checkpoint = str(tmp_path / "actions.npy")
+    out, saved = {}, []
+    choose = engine.choose
+
+    def watched():
+        for attr in module.Engine.state_names:                  # the state a sweep is decided on
+            out[f"{name}:{engine.step}:{attr}"] = getattr(engine, attr)
+        return choose()
+
+    engine.choose = watched
+    if name == "mfba":
+        tally = {True: "tally_fused", False: "tally_loop"}[fused]
+        inner = getattr(engine, tally)
+
+        def logged():
+            inner()
+            out.setdefault(f"mfba:{engine.step}:actions", []).append(np.asarray(engine.greedy_actions).astype(np.int64))
+
+        setattr(engine, tally, logged)
+    with torch.no_grad():
+        for s in range(tl.SWEEPS):
+            engine.args.greedy_checks = tl.GREEDY_CHECKS[s]
+            engine.train(train)
+            engine.save()
+            saved.append(np.load(engine.checkpoint, allow_pickle=True).item())
+            out[f"{name}:{s}:chosen"] = np.array(engine.chosen_actions, dtype=np.int64)
+        engine.validate(valid)
+    out[f"{name}:valid:scores"] = engine.scores.numpy()
+    return out, saved, engine
+
+
+@pytest.fixture(scope="module")
+def runs():
+    """(engine name, knob) -> the run, shared by the comparisons below."""
+    return {}
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "loop"])
+@pytest.mark.parametrize("name", ["leba", "mfba"])
+def test_replays_the_reference(cuda, golden, locations, recorded, runs, monkeypatch, tmp_path, name, fused):
+    from helpers import rel_err
+    out, saved, engine = runs[(name, fused)] = run_engine(name, fused, golden, locations, recorded, monkeypatch, tmp_path)
+    assert engine.fused is fused
+    worst = {"action_scores": 0.0, "valid": 0.0}
+    for s in range(tl.SWEEPS):
+        assert np.array_equal(out[f"{name}:{s}:chosen"], golden[f"{name}:{s}:chosen"]), (s, out[f"{name}:{s}:chosen"])
+        if name == "leba":
+            assert np.array_equal(out[f"leba:{s}:checks"], golden[f"leba:{s}:checks"]), s
+            got, want = out[f"leba:{s}:action_scores"], golden[f"leba:{s}:action_scores"]
+            assert got.dtype == np.float64 and np.array_equal(got >= 1e10, want >= 1e10), s      # the same actions visited
+            seen = want < 1e10
+            e = rel_err(torch.from_numpy(got[seen]), torch.from_numpy(want[seen]))
+            worst["action_scores"] = max(worst["action_scores"], e)
+            assert e < 1e-4, f"sweep {s}: action_scores differ by {e:.2e} (relative)"
+        else:
+            assert np.array_equal(out[f"mfba:{s}:counts"], golden[f"mfba:{s}:counts"]), s
+            assert np.array_equal(np.stack(out[f"mfba:{s}:actions"]), golden[f"mfba:{s}:actions"]), s
+    e = rel_err(torch.from_numpy(out[f"{name}:valid:scores"]), torch.from_numpy(golden[f"{name}:valid:scores"]))
+    worst["valid"] = e
+    assert e < 1e-4, f"validate scores differ by {e:.2e} (relative)"
+    print(f"{name} {'fused' if fused else 'loop'}: chosen {list(out[f'{name}:{tl.SWEEPS - 1}:chosen'])}, worst relative errors {worst}")
+
+
+@pytest.mark.parametrize("name", ["leba", "mfba"])
+def test_knob_on_and_off_agree_bit_for_bit(cuda, golden, locations, recorded, runs, monkeypatch, tmp_path, name):
+    for fused in (True, False):
+        if (name, fused) not in runs:
+            (tmp_path / str(fused)).mkdir()
+            runs[(name, fused)] = run_engine(name, fused, golden, locations, recorded, monkeypatch, tmp_path / str(fused))
+    (on, saved_on, engine_on), (off, saved_off, engine_off) = runs[(name, True)], runs[(name, False)]
+    key = "action_scores" if name == "leba" else "counts"
+    for s in range(tl.SWEEPS):
+        assert np.array_equal(tl.bits(on[f"{name}:{s}:{key}"]), tl.bits(off[f"{name}:{s}:{key}"])), (s, key)
+    assert isinstance(engine_on._state[key], torch.Tensor) and engine_on._state[key].is_cuda and isinstance(engine_off._state[key], np.ndarray)
+    assert len(saved_on) == len(saved_off) == tl.SWEEPS
+    for a, b in zip(saved_on, saved_off):
+        assert set(a) == set(b)
+        for k in a:
+            x, y = np.asarray(a[k]), np.asarray(b[k])
+            assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), k
+
+
+def test_a_fused_leba_batch_copies_nothing_to_the_host(cuda, golden, locations, recorded, monkeypatch, tmp_path):
+    """With the knob on a swept LEBA batch leaves no device tensor for the host: ``Tensor.cpu`` / ``numpy`` / ``item`` / ``tolist``
+    and the scalar conversions on device tensors are counted inside ``tally_fused``; MFBA's copies exactly E int32."""
+    from a3vt_amd.pterotactyl.policies import environment, recorded as rec
+    from a3vt_amd.pterotactyl.policies.dataset_specific import LEBA, MFBA
+    records, train, _ = recorded
+    monkeypatch.setattr(environment.ActiveTouch, "get_loaders", lambda self: None)
+    originals = {n: getattr(torch.Tensor, n) for n in ("cpu", "item", "tolist", "numpy", "__bool__", "__int__", "__float__")}
+    for module, want in ((LEBA, []), (MFBA, [("cpu", (2,), torch.int32)])):
+        engine = module.Engine(tl.engine_args(False, fused_tally=True, **locations), sampler=rec.RecordedSampler(records))
+        env = engine.env = environment.ActiveTouch(engine.args, sampler=engine.sampler)
+        engine.chosen_actions = []
+        engine.reset_state()
+        env.reset(train[0])
+        copies = []
+        score = env.score_candidates
+        table = score([[k] * 2 for k in range(6)], to_host=False)                 # (scoring is the environment's; not counted)
+        env.score_candidates = lambda candidates, to_host=True: table
+
+        def counted(n):
+            def method(self, *a, **k):
+                if self.is_cuda:
+                    copies.append((n, tuple(self.shape), self.dtype))
+                return originals[n](self, *a, **k)
+            return method
+
+        for n in originals:
+            setattr(torch.Tensor, n, counted(n))
+        try:
+            engine.tally_fused()
+        finally:
+            for n, fn in originals.items():
+                setattr(torch.Tensor, n, fn)
+        assert copies == want, (module.__name__, copies)
