@@ -22,60 +22,26 @@ import torch.nn.functional as F
 
 from .... import ops as _ops
 from ...reconstruction.vision.model import GCN_layer, Mask_Encoder, Positional_Encoder, _csr_of, _cut_len  # noqa: F401
-from ...utility import utils
-
-
-def _action_embedding(num_in, out):
-    return nn.Sequential(nn.Sequential(nn.Linear(num_in, 200), nn.ReLU()),
-                         nn.Sequential(nn.Linear(200, 100), nn.ReLU()),
-                         nn.Sequential(nn.Linear(100, out)))
+from .. import _latent
 
 
 def _dev(t, device):
     return t.float().to(device)
 
 
-class Latent_Model(nn.Module):
+class Latent_Model(_latent.LatentInputs, nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
-        latent_size = utils.load_model_config(args.auto_location)[0].encoding_size
-        self.action_model = _action_embedding(args.num_actions, latent_size)
-        sizes = [latent_size * 3] + [args.hidden_dim] * (args.layers - 1) + [args.num_actions]
-        layers = []
-        for i in range(args.layers):
-            mods = [nn.Linear(sizes[i], sizes[i + 1])]
-            if i < args.layers - 1:
-                mods.append(nn.ReLU())
-            layers.append(nn.Sequential(*mods))
-        self.model = nn.Sequential(*layers)
+        self.action_model, self.model = _latent.latent_networks(args)
         self.fused_q_latent = bool(getattr(args, "fused_q_latent", False))
-        self._table = None
-
-    def table(self):
-        """The ``ops.PolicyTable`` of this model's parameters, no output transform (rebuilt when a parameter tensor was replaced)."""
-        seqs = list(self.action_model) + list(self.model)
-        params = [t for seq in seqs for t in (seq[0].weight, seq[0].bias)]
-        if self._table is None or any(a is not b for a, b in zip(self._table.params(), params)):
-            self._table = _ops.PolicyTable([(seq[0].weight, seq[0].bias, len(seq) > 1) for seq in seqs], len(self.action_model), None)
-        return self._table
-
-    def inputs(self, obs, next=False):
-        """(mask, latent, first_latent) of an observation or a replay batch on the model's device, as float32."""
-        dev = self.model[0][0].weight.device
-        sfx = "_n" if next else ""
-        return _dev(obs["mask" + sfx], dev), _dev(obs["latent" + sfx], dev), _dev(obs["first_latent"], dev)
 
     def fused_ok(self, mask):
         """Whether the learner takes the fused ops for this input: the knob, a 2-d mask on the GPU, sizes inside the kernels'."""
         return bool(self.fused_q_latent and mask.is_cuda and mask.dim() == 2 and _ops.ddqn_latent_supported(self.table(), mask))
 
     def forward(self, obs, next=False):
-        dev = self.model[0][0].weight.device
-        sfx = "_n" if next else ""
-        action_input = self.action_model(_dev(obs["mask" + sfx], dev))
-        full = torch.cat((action_input, _dev(obs["latent" + sfx], dev), _dev(obs["first_latent"], dev)), dim=-1)
-        return self.model(full)
+        return self.mlp(*self.inputs(obs, next))
 
 
 class Graph_Model(nn.Module):
@@ -87,7 +53,7 @@ class Graph_Model(nn.Module):
         input_size = 100
         self.adj = adj["adj"]      # dense (N,N), as the reference keeps it (:68)
         self._adj_info = adj       # the CSR handle is taken from / cached in this dict
-        self.action_model = _action_embedding(50, input_size)  # :75 (50 = number of candidate actions)
+        self.action_model = _latent.action_embedding(50, input_size)  # :75 (50 = number of candidate actions)
         self.positional_embedding = Positional_Encoder(input_size)
         self.mask_embedding = Mask_Encoder(input_size)
         sizes = [input_size * 3] + [args.hidden_dim] * (args.layers - 1) + [args.num_actions]

@@ -10,10 +10,10 @@ state of training is checkpointed (reference :44-77, :102-172, :175-257).
 ``check_values_and_save``, ``resume``, ``save``, ``load``) and attributes (``steps``, ``episode``, ``epoch``, ``epsilon``,
 ``best_loss``, ``current_loss``, ``env``, ``replay_memory``, ``policy``, ``target_net``, ``ave_reward``, ``ave_recon``,
 ``window_size``, ``results_dir``, ``checkpoint_dir``); ``sampler`` goes to ``ActiveTouch``, ``loaders=(train, valid)`` injects data.
-It is a plain class (the reference derives from ``submitit``'s ``Checkpointable``, which only matters to that scheduler), and
-``SummaryWriter`` falls back to a no-op stub when tensorboard is missing.  ``get_parser()`` carries every flag and default of the
-reference's ``__main__`` block (:351-524) and this package's: ``--data_root``, ``--pretrained_root``, ``--recorded`` as in the
-supervised parser, ``--replay_device``, ``--fused_q_latent`` / ``--no_fused_q_latent``.
+It derives from ``_core.EngineBase`` alone (the reference derives from ``submitit``'s ``Checkpointable``, which only matters to that
+scheduler), and ``utils.SummaryWriter`` is a no-op stub when tensorboard is missing.  ``get_parser()`` carries every flag and
+default of the reference's ``__main__`` block (:351-524) and this package's: ``--data_root``, ``--pretrained_root``, ``--recorded``
+(``_core.common_parser``), ``--replay_device``, ``--fused_q_latent`` / ``--no_fused_q_latent``.
 
 The loop is the reference's, order included: epsilon decays BEFORE the action once ``steps >= burn_in`` (:115-116); actions are
 random while ``steps < burn_in`` (:119); ``add_experience`` comes before ``update_parameters`` (:129-133); the target copy happens
@@ -23,8 +23,8 @@ compares ``best_loss >= current_loss`` (:261); ``load`` adds 1 to ``episode`` an
 reference's dict of nine keys (``dqn_weights``, ``target_weights``, ``args``, ``episode``, ``steps``, ``ave_reward``, ``ave_recon``,
 ``epsilon``, ``epoch``) in ``{best,recent}_model`` with ``{best,recent}_replay_buffer.pt`` beside it.  A pretrained policy is the
 FILE ``<pretrained_root>/policies/DDQN/{l|g}_{v_t_p|v_t_g|t_p|t_g}`` (``checkpoint["dqn_weights"]``), resolved by
-``(use_latent, use_img, finger)``; ``pretrained_root`` is ``args.pretrained_root`` or ``PTEROTACTYL_PRETRAINED``, as in the
-supervised engine (the reference reads it from inside its package).
+``(use_latent, use_img, finger)``; ``pretrained_root`` is ``args.pretrained_root`` or ``PTEROTACTYL_PRETRAINED``
+(``utils.pretrained_root``; the reference reads it from inside its package).
 
 ``args.fused_q_latent`` (this package's; ``None``: ``FUSED_Q_LATENT_DEFAULT``) is set before the learners are built: a
 ``Latent_Model`` on the GPU is then evaluated and updated by ``ops.ddqn_latent_q`` / ``ops.ddqn_latent_update`` (see ``ddqn.py``).
@@ -38,30 +38,19 @@ What differs from the reference, and why:
 * The third replay write of ``check_values_and_save`` (:272, ``replay_memory.save(self.checkpoint_dir)``) is dropped: it lands
   BESIDE the checkpoint directory (``<checkpoint_dir>_replay_buffer.pt``) and nothing ever reads it; ``save`` has written the
   ``best`` / ``recent`` buffers already.
-* ``visualize`` raises ``NotImplementedError`` (pyrender), as in the other engines.
+* ``visualize`` raises ``NotImplementedError`` (pyrender; ``_core.refuse_visualize``).
 * ``reset_pybullet`` goes through ``env.reset_pybullet()``, which already handles recorded samplers.
 * Checkpoints pickle ``args``, so they are read with ``weights_only=False``.
 * ``args.replay_device`` (default ``None``: the host, as the reference) is passed to ``ReplayMemory(device=)``.
 """
-import argparse
 import os
 
 import torch
-from torch.utils.data import DataLoader
 
 from ...utility import utils
-from .. import environment, replay
+from ...utility.utils import SummaryWriter
+from .. import _core, replay
 from . import ddqn
-
-try:
-    from torch.utils.tensorboard import SummaryWriter
-except Exception:  # tensorboard is optional
-    class SummaryWriter:
-        def __init__(self, *a, **k):
-            pass
-
-        def add_scalars(self, *a, **k):
-            pass
 
 # Whether the engine turns the fused latent Q-network on when args does not say: on only if the fused update's p90 lies below the
 # torch-module update's p10 at both measured sizes on an MI355X (tools/ddqn_latent_bench.py -> profiles/ddqn_latent_ab.txt).
@@ -71,23 +60,20 @@ except Exception:  # tensorboard is optional
 # (p90 0.250) against 0.381 (p10 0.375); a fused update is 3 launches + Adam's one.
 FUSED_Q_LATENT_DEFAULT = True
 
-POLICY_FILES = {(True, True): "v_t_p", (True, False): "v_t_g", (False, True): "t_p", (False, False): "t_g"}   # (use_img, finger)
 CHECKPOINT_KEYS = ("dqn_weights", "target_weights", "args", "episode", "steps", "ave_reward", "ave_recon", "epsilon", "epoch")
 
 
-class Engine:
-    num_workers = 4
+class Engine(_core.EngineBase):
+    shuffle_train = True
+    empty_train = ""           # (the reference's)
 
     def __init__(self, args, sampler=None, loaders=None):
-        self.args = args
-        self.sampler = sampler
-        self.loaders = loaders
+        super().__init__(args, sampler, loaders)     # (device: where the learners live)
         self.steps = 0
         self.episode = 0
         self.epoch = 0
         self.best_loss = 10000
         self.epsilon = self.args.epsilon_start
-        self.device = None      # where the learners live; None: the environment's device (the GPU)
         self.target_updates = []   # the values of `steps` at which the target net was copied (tests)
 
         self.results_dir = os.path.join("results", args.exp_type, args.exp_id)
@@ -95,9 +81,6 @@ class Engine:
         self.checkpoint_dir = os.path.join("experiments/checkpoint/", self.args.exp_type, self.args.exp_id)
         os.makedirs(self.checkpoint_dir, exist_ok=True)
         utils.save_config(self.checkpoint_dir, args)
-
-    def policy_device(self):
-        return utils._device() if self.device is None else torch.device(self.device)
 
     def make_learners(self):
         """The policy and its target (:47-52): the same weights, the target in eval mode, both on ``policy_device()``."""
@@ -111,10 +94,8 @@ class Engine:
         self.target_net.eval()
 
     def __call__(self):
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: the reference renders predictions and actions with pyrender, which this package "
-                                      "does not have; run without --visualize")
-        self.env = environment.ActiveTouch(self.args, sampler=self.sampler)
+        _core.refuse_visualize(self.args)
+        self.make_env()
         self.make_learners()
         self.writer = SummaryWriter(os.path.join("experiments/tensorboard/", self.args.exp_type))
         self.window_size = 1000
@@ -138,16 +119,6 @@ class Engine:
                 self.env.reset_pybullet()
                 self.check_values_and_save()
             self.epoch += 1
-
-    def get_loaders(self):
-        if self.loaders is not None:
-            return self.loaders
-        workers = getattr(self.args, "num_workers", self.num_workers)
-        train_loader = "" if self.args.eval else DataLoader(self.env.train_data, batch_size=self.args.env_batch_size, shuffle=True,
-                                                           num_workers=workers, collate_fn=self.env.train_data.collate)
-        valid_loader = DataLoader(self.env.valid_data, batch_size=self.args.env_batch_size, shuffle=False, num_workers=workers,
-                                  collate_fn=self.env.valid_data.collate)
-        return train_loader, valid_loader
 
     def train(self, dataloader):
         ave_reward = ave_recon = None
@@ -186,9 +157,14 @@ class Engine:
             self.writer.add_scalars("train_recon_|_", {self.args.exp_id: ave_recon}, self.steps)
             self.writer.add_scalars("train_reward_|_", {self.args.exp_id: ave_reward}, self.steps)
 
+    def take_step(self, t, obs):
+        action = self.policy.get_action(obs, eps_threshold=-1, give_random=False)       # greedy
+        with torch.no_grad():
+            obs, _, done = self.env.step(action)
+        return action, obs, done
+
     def validate(self, dataloader):
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: needs pyrender, which this package does not have")
+        _core.refuse_visualize(self.args)
         scores, actions, names = [], [], []
         print("*" * 30)
         print("Doing Validation")
@@ -196,34 +172,19 @@ class Engine:
             names += batch["names"]
             if v > self.args.valid_steps - 1 and not self.args.eval:
                 break
-            obs = self.env.reset(batch)
-            all_done = False
-            cur_scores, cur_actions = [obs["score"]], []
-            while not all_done:
-                action = self.policy.get_action(obs, eps_threshold=-1, give_random=False)       # greedy
-                with torch.no_grad():
-                    next_obs, reward, all_done = self.env.step(action)
-                obs = next_obs
-                cur_scores.append(obs["score"])
-                cur_actions.append(torch.FloatTensor(action))
-            scores.append(torch.stack(cur_scores).permute(1, 0))
-            actions.append(torch.stack(cur_actions).permute(1, 0))
-            print_score = (scores[-1][:, -1] / scores[-1][:, 0]).mean()
-            print_reward = ((scores[-1][:, 0] - scores[-1][:, -1]) / scores[-1][:, 0]).mean()
-            print(f"Valid || E: {self.epoch}, score: {print_score:.2f}, best score: {self.best_loss:.2f} reward = {print_reward:.2f}")
+            cur_scores, cur_actions = self.play(self.env.reset(batch), self.take_step)
+            scores.append(cur_scores)
+            actions.append(cur_actions)
+            now = _core.summary(cur_scores)
+            print(f"Valid || E: {self.epoch}, score: {now['score']:.2f}, best score: {self.best_loss:.2f} reward = {now['reward']:.2f}")
 
-        scores = torch.cat(scores)
-        actions = torch.cat(actions)
-        rewards = ((scores[:, 0] - scores[:, -1]) / scores[:, 0]).mean()
-        variation = torch.std(actions, dim=0).mean()
-        self.current_loss = (scores[:, -1] / scores[:, 0]).mean()
-        self.scores, self.chosen, self.names = scores, actions, names
-
-        message = f"Total Valid || E: {self.epoch}, score: {self.current_loss:.4f}, best score: {self.best_loss:.4f} reward = {rewards.mean():.2f}"
-        print("*" * len(message) + "\n" + message + "\n" + "*" * len(message))
+        total = self.report(scores, actions, names, f"Total Valid || E: {self.epoch}, score: {{score:.4f}}, "
+                                                    f"best score: {self.best_loss:.4f} reward = {{reward:.2f}}")
+        variation = torch.std(self.chosen, dim=0).mean()
+        self.current_loss = total["score"]
         if not self.args.eval:
             self.writer.add_scalars("Valid_recon_|_", {self.args.exp_id: self.current_loss}, self.steps)
-            self.writer.add_scalars("Valid_reward_|_", {self.args.exp_id: rewards.mean()}, self.steps)
+            self.writer.add_scalars("Valid_reward_|_", {self.args.exp_id: total["reward"]}, self.steps)
             self.writer.add_scalars("epsilon_|_", {self.args.exp_id: self.epsilon}, self.steps)
             self.writer.add_scalars("Valid_variation_|_", {self.args.exp_id: variation}, self.steps)
 
@@ -252,12 +213,8 @@ class Engine:
                     "epsilon": self.epsilon, "epoch": self.epoch}, path + "_model")
 
     def pretrained_location(self):
-        root = getattr(self.args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
-        if not root:
-            raise FileNotFoundError("a3vt: set args.pretrained_root or PTEROTACTYL_PRETRAINED to the directory the reference's "
-                                    "download_models.sh fills (pterotactyl/pretrained/)")
         prefix = "l" if self.args.use_latent else "g"
-        return os.path.join(root, "policies", "DDQN", f"{prefix}_{POLICY_FILES[(bool(self.args.use_img), bool(self.args.finger))]}")
+        return os.path.join(utils.pretrained_root(self.args), "policies", "DDQN", f"{prefix}_{_core.kind(self.args)}")
 
     def load(self, best=True):
         dev = self.policy_device()
@@ -280,39 +237,20 @@ class Engine:
 
 def get_parser():
     """The reference's flags and defaults (:351-522) and this package's."""
-    pretrained = os.environ.get("PTEROTACTYL_PRETRAINED", "")
-    parser = argparse.ArgumentParser()
+    parser = _core.common_parser(auto_location=True, pretrained=True, latent_flags=True)
     parser.add_argument("--cut", type=float, default=0.33, help="share of a GCN layer's features that is aggregated over neighbours (graph model)")
     parser.add_argument("--layers", type=int, default=4, help="layers of the Q-network")
     parser.add_argument("--hidden_dim", type=int, default=200, help="width of the Q-network's hidden layers")
     parser.add_argument("--epochs", type=int, default=1000, help="epochs to train for")
-    parser.add_argument("--limit_data", action="store_true", default=False, help="a small subset of the data (debugging)")
-    parser.add_argument("--finger", action="store_true", default=False, help="touch with one finger instead of four")
     parser.add_argument("--eval", action="store_true", default=False, help="evaluate the best checkpoint instead of training")
-    parser.add_argument("--touch_location", type=str, default=os.path.join(pretrained, "reconstruction/touch/best/"),
-                        help="checkpoint directory of the touch chart predictor")
-    parser.add_argument("--vision_location", type=str, default=os.path.join(pretrained, "reconstruction/vision/t_p/"),
-                        help="checkpoint directory of the mesh deformation model")
-    parser.add_argument("--auto_location", type=str, default=os.path.join(pretrained, "reconstruction/auto/t_p/"),
-                        help="checkpoint directory of the mesh auto-encoder")
-    parser.add_argument("--number_points", type=int, default=30000, help="surface points per Chamfer score")
-    parser.add_argument("--seed", type=int, default=0, help="random seed")
     parser.add_argument("--lr", type=float, default=0.0003, help="Adam's learning rate")
-    parser.add_argument("--env_batch_size", type=int, default=3, help="objects per environment batch")
-    parser.add_argument("--train_batch_size", type=int, default=16,
-                        help="transitions per Q-network update")
+    parser.add_argument("--train_batch_size", type=int, default=16, help="transitions per Q-network update")
     parser.add_argument("--exp_id", type=str, default="test", help="experiment name (checkpoint and results sub-directory)")
-    parser.add_argument("--exp_type", type=str, default="test", help="experiment group (checkpoint and results directory)")
-    parser.add_argument("--use_img", action="store_true", default=False, help="condition the reconstruction on the image")
     parser.add_argument("--patience", type=int, default=70, help="epochs without improvement tolerated (kept for the reference's flag set)")
-    parser.add_argument("--loss_coeff", type=float, default=9000.0, help="scale of the Chamfer score")
-    parser.add_argument("--num_grasps", type=int, default=5, help="touch slots of the reconstruction models")
-    parser.add_argument("--budget", type=int, default=5)
     parser.add_argument("--normalization", type=str, choices=["first", "current", "none"], default="first",
                         help="divide the reward by the first score, the current score, or nothing")
     parser.add_argument("--mem_capacity", type=int, default=300, help="transitions the replay memory holds")
     parser.add_argument("--burn_in", type=int, default=20, help="steps of random actions before the first update")
-    parser.add_argument("--num_actions", type=int, default=50, help="actions to choose from")
     parser.add_argument("--gamma", type=float, default=0, help="discount of the next state's value")
     parser.add_argument("--epsilon_start", type=float, default=1.0, help="epsilon at the start")
     parser.add_argument("--epsilon_decay", type=float, default=0.9999, help="factor applied to epsilon every step after burn-in")
@@ -320,16 +258,6 @@ def get_parser():
     parser.add_argument("--train_steps", type=int, default=20, help="training episodes per epoch")
     parser.add_argument("--valid_steps", type=int, default=10, help="validation episodes per epoch")
     parser.add_argument("--target_update", type=int, default=3000, help="steps between copies of the policy into the target network")
-    parser.add_argument("--use_latent", action="store_true", default=False, help="Q-network over auto-encoder latents (Latent_Model)")
-    parser.add_argument("--use_recon", action="store_true", default=False, help="Q-network over the predicted mesh (Graph_Model)")
-    parser.add_argument("--visualize", action="store_true", default=False, help="not built: needs pyrender")
-    parser.add_argument("--pretrained_recon", action="store_true", default=False,
-                        help="take the reconstruction models from the pretrained directory")
-    parser.add_argument("--pretrained", action="store_true", default=False, help="load the published policy of this configuration")
-    parser.add_argument("--data_root", type=str, default=None, help="dataset directory (default: PTEROTACTYL_DATA)")
-    parser.add_argument("--pretrained_root", type=str, default=None, help="pretrained/ directory (default: PTEROTACTYL_PRETRAINED)")
-    parser.add_argument("--recorded", type=str, default=None,
-                        help="replay touch signals from this dataset root's grasp_info/ (RecordedSampler) instead of simulating")
     parser.add_argument("--replay_device", type=str, default=None,
                         help="keep the replay memory on this device (default: the host, as the reference)")
     parser.add_argument("--fused_q_latent", dest="fused_q_latent", action="store_true", default=None,
@@ -339,12 +267,7 @@ def get_parser():
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
-    sampler = None
-    if args.recorded:
-        from ..recorded import RecordedSampler
-        sampler = RecordedSampler(args.recorded)
-    return Engine(args, sampler=sampler)()
+    return _core.run(Engine, get_parser(), argv)
 
 
 if __name__ == "__main__":

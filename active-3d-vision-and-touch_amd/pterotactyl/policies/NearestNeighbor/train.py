@@ -32,26 +32,23 @@ What differs from the reference, and why:
 * Actions outside ``[0, num_actions)`` are refused when they are appended or loaded, on the host.
 * ``train`` resumes from ``spot`` as the reference does: batches before ``spot`` are skipped and batch ``spot`` itself is swept
   AGAIN, so a bank saved after batch ``spot`` holds that batch's entries twice after a resume.  Kept as it is.
-* ``visualize`` raises ``NotImplementedError`` (pyrender), as the baseline runners do.
+* ``visualize`` raises ``NotImplementedError`` (pyrender; ``_core.refuse_visualize``).
+
+The flags, the ``main``, the loaders and the validation rollout every policy engine has are ``policies/_core.py``'s.
 """
-import argparse
 import os
 import random
 
 import numpy as np
 import torch
-from torch.utils.data import DataLoader
 
 from .... import ops
 from ...utility import utils
-from .. import environment
-from ..baselines import _runner
+from .. import _core
 
 # Whether validate() looks the bank up with the library call when args does not say: on only if the call's p90 host wall lies
 # below the reference loop's p10 on an MI355X (tools/nn_lookup_bench.py -> profiles/nn_lookup_ab.txt).
 FUSED_LOOKUP_DEFAULT = True
-
-BANK_FILES = {(False, True): "t_p.npy", (False, False): "t_g.npy", (True, True): "v_t_p.npy", (True, False): "v_t_g.npy"}   # (use_img, finger)
 
 
 class LatentBank:
@@ -150,16 +147,11 @@ def reference_lookup(latents, actions, obs_latents, mask, k):
     return out
 
 
-class Engine:
-    num_workers = 4
-
+class Engine(_core.EngineBase):
     def __init__(self, args, sampler=None, loaders=None):
-        self.args = args
-        self.sampler = sampler
-        self.loaders = loaders
+        super().__init__(args, sampler, loaders)     # (device: where the bank is searched)
         self.bank = LatentBank(args.num_actions)
         self.steps_chosen = 0
-        self.device = None          # where the bank is searched; None: the environment's device (the GPU)
 
     # the reference's attributes: the bank's host lists
     actions = property(lambda self: self.bank.actions)
@@ -167,10 +159,8 @@ class Engine:
     spot = property(lambda self: self.bank.spot, lambda self, v: setattr(self.bank, "spot", v))
 
     def __call__(self):
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: the reference renders predictions and actions with pyrender, which this package "
-                                      "does not have; run without --visualize")
-        self.env = environment.ActiveTouch(self.args, sampler=self.sampler)
+        _core.refuse_visualize(self.args)
+        self.make_env()
         self.bank = LatentBank(self.args.num_actions)
         train_loaders, valid_loaders = self.get_loaders()
         self.results_dir = os.path.join("results", self.args.exp_type)
@@ -184,16 +174,6 @@ class Engine:
                 return self.validate(valid_loaders)
             self.train(train_loaders)
             self.save()
-
-    def get_loaders(self):
-        if self.loaders is not None:
-            return self.loaders
-        workers = getattr(self.args, "num_workers", self.num_workers)
-        train_loader = [] if self.args.eval else DataLoader(self.env.train_data, batch_size=self.args.env_batch_size, shuffle=False,
-                                                           num_workers=workers, collate_fn=self.env.train_data.collate)
-        valid_loader = DataLoader(self.env.valid_data, batch_size=self.args.env_batch_size, shuffle=False, num_workers=workers,
-                                  collate_fn=self.env.valid_data.collate)
-        return train_loader, valid_loader
 
     def train(self, dataloader):
         """The reference's sweep (:73-98): ``random.sample`` of 40 % of the batches after ``random.seed(args.seed)``; per batch
@@ -215,9 +195,6 @@ class Engine:
             if v % 3 == 0:
                 self.save()
 
-    def lookup_device(self):
-        return utils._device() if self.device is None else torch.device(self.device)
-
     def choose(self, obs):
         """One step of the policy -> (E,) NumPy actions."""
         k = self.args.num_grasps * 5
@@ -238,42 +215,32 @@ class Engine:
                                f"every action stored with its {min(k, len(self.bank))} nearest latents")
         return action
 
+    def take_step(self, t, obs):
+        action = self.choose(obs)
+        obs, _, done = self.env.step(action)
+        self.steps_chosen += 1
+        return action, obs, done
+
     def validate(self, dataloader):
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: needs pyrender, which this package does not have")
+        _core.refuse_visualize(self.args)
         scores, actions, names = [], [], []
         self.bank.to(self.lookup_device())      # (an empty bank is refused here, before any episode)
         for batch in dataloader:
             names += batch["names"]
             obs = self.env.reset(batch)
-            all_done = False
-            cur_scores, cur_actions = [obs["score"]], []
             self.steps_chosen = 0
-            while not all_done:
-                action = self.choose(obs)
-                obs, reward, all_done = self.env.step(action)
-                self.steps_chosen += 1
-                cur_scores.append(obs["score"])
-                cur_actions.append(torch.FloatTensor(action))
-            scores.append(torch.stack(cur_scores).permute(1, 0))
-            actions.append(torch.stack(cur_actions).permute(1, 0))
-            now = _runner.summary(scores[-1])
+            cur_scores, cur_actions = self.play(obs, self.take_step)
+            scores.append(cur_scores)
+            actions.append(cur_actions)
+            now = _core.summary(cur_scores)
             print(f"Valid || score: {now['score']:.4f}, reward = {now['reward']:.4f}")
-        total = _runner.summary(torch.cat(scores))
-        message = f"Total Valid || score: {total['score']:.4f}, reward = {total['reward']:.4f}"
-        print("*" * len(message) + "\n" + message + "\n" + "*" * len(message))
-        self.scores, self.chosen, self.names = torch.cat(scores), torch.cat(actions), names
-        return total
+        return self.report(scores, actions, names)
 
     def bank_location(self):
         """Where ``load`` reads the bank from: the pretrained file by the reference's ``(use_img, finger)`` rule (:180-202), else
         the checkpoint, else the reference's separator-less name of it; None when there is none."""
         if self.args.pretrained:
-            root = getattr(self.args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
-            if not root:
-                raise FileNotFoundError("a3vt: set args.pretrained_root or PTEROTACTYL_PRETRAINED to the directory the reference's "
-                                        "download_models.sh fills (pterotactyl/pretrained/)")
-            return os.path.join(root, "policies", "NearestNeighbor", BANK_FILES[(bool(self.args.use_img), bool(self.args.finger))])
+            return os.path.join(utils.pretrained_root(self.args), "policies", "NearestNeighbor", _core.kind(self.args) + ".npy")
         for path in (self.checkpoint, self.checkpoint_dir + "actions.npy"):
             if os.path.exists(path):
                 return path
@@ -288,51 +255,19 @@ class Engine:
         self.bank.save(self.checkpoint)
 
 
+
+
 def get_parser():
     """The reference's flags and defaults (:223-311) and this package's."""
-    pretrained = os.environ.get("PTEROTACTYL_PRETRAINED", "")
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--limit_data", action="store_true", default=False, help="use less data, for debugging.")
-    parser.add_argument("--finger", action="store_true", default=False, help="use only one finger.")
-    parser.add_argument("--touch_location", type=str, default=os.path.join(pretrained, "reconstruction/touch/best/"),
-                        help="the location of the touch part prediction.")
-    parser.add_argument("--vision_location", type=str, default=os.path.join(pretrained, "reconstruction/vision/t_p/"),
-                        help="the location of the vision part prediction.")
-    parser.add_argument("--auto_location", type=str, default=os.path.join(pretrained, "reconstruction/auto/t_p/"),
-                        help="the location of the autoencoder part prediction.")
-    parser.add_argument("--number_points", type=int, default=30000, help="number of points sampled for the chamfer distance.")
-    parser.add_argument("--seed", type=int, default=0, help="Setting for the random seed.")
-    parser.add_argument("--env_batch_size", type=int, default=3, help="Size of the batch.")
-    parser.add_argument("--use_img", action="store_true", default=False, help="To use the image.")
-    parser.add_argument("--loss_coeff", type=float, default=9000.0, help="Coefficient for loss term.")
-    parser.add_argument("--num_grasps", type=int, default=5, help="Number of grasps to train with. ")
-    parser.add_argument("--num_actions", type=int, default=50, help="number of action options")
+    parser = _core.common_parser(auto_location=True, pretrained=True, greedy_checks=True)
     parser.add_argument("--eval", action="store_true", default=False, help="for evaluating on test set")
-    parser.add_argument("--budget", type=int, default=5, help="number of graspsp to perform")
-    parser.add_argument("--visualize", action="store_true", default=False, help="not built: needs pyrender")
-    parser.add_argument("--exp_type", type=str, default="test", help="The experiment group.")
-    parser.add_argument("--greedy_checks", type=int, default=50, help="Number of actions to check at each time step")
-    parser.add_argument("--pretrained_recon", action="store_true", default=False,
-                        help="use the pretrained reconstruction models to train")
-    parser.add_argument("--pretrained", action="store_true", default=False, help="use the pretrained policy")
-    parser.add_argument("--data_root", type=str, default=None, help="dataset directory (default: PTEROTACTYL_DATA)")
-    parser.add_argument("--pretrained_root", type=str, default=None, help="pretrained/ directory (default: PTEROTACTYL_PRETRAINED)")
-    parser.add_argument("--recorded", type=str, default=None,
-                        help="replay touch signals from this dataset root's grasp_info/ (RecordedSampler) instead of simulating")
     parser.add_argument("--no_fused_lookup", dest="fused_lookup", action="store_false", default=None,
                         help="look the bank up with the reference's per-element loop on torch ops")
     return parser
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
-    args.use_recon = False
-    args.use_latent = True
-    sampler = None
-    if args.recorded:
-        from ..recorded import RecordedSampler
-        sampler = RecordedSampler(args.recorded)
-    return Engine(args, sampler=sampler)()
+    return _core.run(Engine, get_parser(), argv, after_parse=_core.latent_only)
 
 
 if __name__ == "__main__":

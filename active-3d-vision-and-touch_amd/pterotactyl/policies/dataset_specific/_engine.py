@@ -1,20 +1,18 @@
 """What ``LEBA.py`` and ``MFBA.py`` share: the engine around the per-batch bookkeeping (the reference's two files repeat it line for
 line) — the sweep over 40 % of the training batches, the replay of the trajectory chosen so far, checkpoints, ``validate``, the
 flags.  A subclass says how its per-action state starts (``fresh_state``), what one swept batch adds to it (``tally_fused`` /
-``tally_loop``) and which action a finished sweep chooses (``choose``)."""
-import argparse
+``tally_loop``) and which action a finished sweep chooses (``choose``).  The parts every policy engine has are
+``policies/_core.py``'s."""
 import os
 import random
 import sys
 
 import numpy as np
 import torch
-from torch.utils.data import DataLoader
 
-from .. import environment
-from ..baselines import _runner
+from ...utility import utils
+from .. import _core
 
-KINDS = {(True, True): "v_t_p", (True, False): "v_t_g", (False, True): "t_p", (False, False): "t_g"}   # (use_img, finger)
 SAVE_EVERY = 20
 
 
@@ -24,15 +22,12 @@ def swept_batches(training_length, seed):
     return random.sample(range(training_length), int(training_length * 0.4))
 
 
-class SweepEngine:
+class SweepEngine(_core.EngineBase):
     name = None                # "LEBA" / "MFBA": the checkpoint directory and the pretrained files' prefix
     state_names = ()           # the per-action float64 arrays, in the checkpoint under these keys
-    num_workers = 4
 
     def __init__(self, args, sampler=None, loaders=None):
-        self.args = args
-        self.sampler = sampler
-        self.loaders = loaders
+        super().__init__(args, sampler, loaders)
         self._state = {}
 
     # ---- the per-action state: fp64 tensors on the environment's device with the knob on, NumPy arrays with it off ----------------
@@ -58,11 +53,8 @@ class SweepEngine:
 
     # ---- the reference's methods --------------------------------------------------------------------------------------------------
     def __call__(self):
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: the reference renders predictions and actions with utils.visualize_prediction and "
-                                      "utils.visualize_actions (pyrender), which this package's utils does not have; run without "
-                                      "--visualize")
-        self.env = environment.ActiveTouch(self.args, sampler=self.sampler)
+        _core.refuse_visualize(self.args)
+        self.make_env()
         data_loaders, valid_loaders = self.get_loaders()
         self.chosen_actions = []
         self.step = 0
@@ -80,16 +72,6 @@ class SweepEngine:
             for _ in range(self.step, self.args.num_grasps):
                 self.train(data_loaders)
                 self.save()
-
-    def get_loaders(self):
-        if self.loaders is not None:
-            return self.loaders
-        workers = getattr(self.args, "num_workers", self.num_workers)
-        train_loader = [] if self.args.eval else DataLoader(self.env.train_data, batch_size=self.args.env_batch_size, shuffle=False,
-                                                           num_workers=workers, collate_fn=self.env.train_data.collate)
-        valid_loader = DataLoader(self.env.valid_data, batch_size=self.args.env_batch_size, shuffle=False, num_workers=workers,
-                                  collate_fn=self.env.valid_data.collate)
-        return train_loader, valid_loader
 
     def train(self, dataloader):
         """One sweep (reference LEBA.py:83-143, MFBA.py:76-111): the next action of the trajectory.  Batches before ``spot`` are
@@ -112,41 +94,31 @@ class SweepEngine:
         self.spot = 0
         self.step += 1
 
+    def take_step(self, t, obs):
+        best_actions = np.array([self.chosen_actions[t] for _ in range(self.args.env_batch_size)])
+        obs, _, done = self.env.step(best_actions)
+        return best_actions, obs, done
+
     def validate(self, dataloader):
         """The fixed trajectory on every batch (reference LEBA.py:146-204) -> the closing figures; ``scores`` (n, steps + 1),
         ``chosen`` (n, steps) and ``names`` stay on the engine."""
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: needs utils.visualize_prediction / visualize_actions, which this package does not have")
+        _core.refuse_visualize(self.args)
         scores, actions, names = [], [], []
         for batch in dataloader:
             names += batch["names"]
-            obs = self.env.reset(batch)
-            cur_scores, cur_actions = [obs["score"]], []
-            for action in self.chosen_actions:
-                best_actions = np.array([action for _ in range(self.args.env_batch_size)])
-                obs, _, _ = self.env.step(best_actions)
-                cur_scores.append(obs["score"])
-                cur_actions.append(torch.FloatTensor(best_actions))
-            scores.append(torch.stack(cur_scores).permute(1, 0))
-            actions.append(torch.stack(cur_actions).permute(1, 0) if cur_actions else torch.zeros(self.args.env_batch_size, 0))
-            now = _runner.summary(scores[-1])
+            cur_scores, cur_actions = self.play(self.env.reset(batch), self.take_step, steps=len(self.chosen_actions))
+            scores.append(cur_scores)
+            actions.append(cur_actions)
+            now = _core.summary(cur_scores)
             print(f"Valid || score: {now['score']:.4f}, reward = {now['reward']:.4f}")
-        total = _runner.summary(torch.cat(scores))
-        message = f"Total Valid || score: {total['score']:.4f}, reward = {total['reward']:.4f}"
-        print("*" * len(message) + "\n" + message + "\n" + "*" * len(message))
-        self.scores, self.chosen, self.names = torch.cat(scores), torch.cat(actions), names
-        return total
+        return self.report(scores, actions, names)
 
     def location(self):
         """Where ``load`` reads from: the pretrained file by the reference's ``(use_img, finger)`` rule, else the checkpoint, else
         the reference's separator-less name of it; None when there is none."""
         if self.args.pretrained:
-            root = getattr(self.args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
-            if not root:
-                raise FileNotFoundError("a3vt: set args.pretrained_root or PTEROTACTYL_PRETRAINED to the directory the reference's "
-                                        "download_models.sh fills (pterotactyl/pretrained/)")
-            kind = KINDS[(bool(self.args.use_img), bool(self.args.finger))]
-            return os.path.join(root, "policies", "dataset_specific", f"{self.name}_{kind}.npy")
+            return os.path.join(utils.pretrained_root(self.args), "policies", "dataset_specific",
+                                f"{self.name}_{_core.kind(self.args)}.npy")
         for path in (self.checkpoint, self.checkpoint_dir + "actions.npy"):
             if os.path.exists(path):
                 return path
@@ -175,37 +147,8 @@ class SweepEngine:
 
 def get_parser():
     """The reference's flags and defaults (LEBA.py:259-342; MFBA's are the same) and this package's."""
-    pretrained = os.environ.get("PTEROTACTYL_PRETRAINED", "")
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--limit_data", action="store_true", default=False, help="use less data, for debugging.")
-    parser.add_argument("--finger", action="store_true", default=False, help="use only one finger.")
-    parser.add_argument("--touch_location", type=str, default=os.path.join(pretrained, "reconstruction/touch/best/"),
-                        help="the location of the touch part prediction.")
-    parser.add_argument("--vision_location", type=str, default=os.path.join(pretrained, "reconstruction/vision/t_p/"),
-                        help="the location of the vision part prediction.")
-    parser.add_argument("--auto_location", type=str, default=os.path.join(pretrained, "reconstruction/auto/t_p/"),
-                        help="the location of the autoencoder part prediction (with --use_latent).")
-    parser.add_argument("--number_points", type=int, default=30000, help="number of points sampled for the chamfer distance.")
-    parser.add_argument("--seed", type=int, default=0, help="Setting for the random seed.")
-    parser.add_argument("--env_batch_size", type=int, default=3, help="Size of the batch.")
-    parser.add_argument("--use_img", action="store_true", default=False, help="To use the image.")
-    parser.add_argument("--loss_coeff", type=float, default=9000.0, help="Coefficient for loss term.")
-    parser.add_argument("--num_grasps", type=int, default=5, help="Number of grasps to train with. ")
-    parser.add_argument("--num_actions", type=int, default=50)
-    parser.add_argument("--use_latent", action="store_true", default=False)
-    parser.add_argument("--use_recon", action="store_true", default=False)
+    parser = _core.common_parser(auto_location=True, pretrained=True, latent_flags=True, greedy_checks=True)
     parser.add_argument("--eval", action="store_true", default=False, help="Evaluate the trained model on the test set.")
-    parser.add_argument("--budget", type=int, default=5, help="number of graspsp to perform")
-    parser.add_argument("--visualize", action="store_true", default=False, help="not built: needs pyrender")
-    parser.add_argument("--exp_type", type=str, default="test", help="The experiment group.")
-    parser.add_argument("--greedy_checks", type=int, default=50, help="Number of actions to check at each time step")
-    parser.add_argument("--pretrained_recon", action="store_true", default=False,
-                        help="use the pretrained reconstruction models to train")
-    parser.add_argument("--pretrained", action="store_true", default=False, help="use the pretrained policy")
-    parser.add_argument("--data_root", type=str, default=None, help="dataset directory (default: PTEROTACTYL_DATA)")
-    parser.add_argument("--pretrained_root", type=str, default=None, help="pretrained/ directory (default: PTEROTACTYL_PRETRAINED)")
-    parser.add_argument("--recorded", type=str, default=None,
-                        help="replay touch signals from this dataset root's grasp_info/ (RecordedSampler) instead of simulating")
     parser.add_argument("--fused_tally", dest="fused_tally", action="store_true", default=None,
                         help="keep the per-action state on the GPU: one a3vt_candidate_tally launch per swept batch")
     parser.add_argument("--no_fused_tally", dest="fused_tally", action="store_false",
@@ -214,9 +157,4 @@ def get_parser():
 
 
 def run(engine_class, argv=None):
-    args = get_parser().parse_args(argv)
-    sampler = None
-    if args.recorded:
-        from ..recorded import RecordedSampler
-        sampler = RecordedSampler(args.recorded)
-    return engine_class(args, sampler=sampler)()
+    return _core.run(engine_class, get_parser(), argv)

@@ -152,10 +152,7 @@ class ActiveTouch:
 
     def pretrained_recon_models(self):
         if getattr(self.args, "pretrained_recon", False):
-            root = getattr(self.args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
-            if not root:
-                raise FileNotFoundError("a3vt: set args.pretrained_root or PTEROTACTYL_PRETRAINED to the directory the reference's "
-                                        "download_models.sh fills (pterotactyl/pretrained/)")
+            root = utils.pretrained_root(self.args)
             kind = ("v_t_" if self.args.use_img else "t_") + ("p" if self.args.finger else "g")     # :67-104
             self.args.touch_location = os.path.join(root, "reconstruction", "touch", "best") + "/"
             self.args.vision_location = os.path.join(root, "reconstruction", "vision", kind) + "/"

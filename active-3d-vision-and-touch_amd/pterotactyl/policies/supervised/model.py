@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .... import ops as _ops
-from ...utility import utils
+from .. import _latent
 
 
 def output_transform(args):
@@ -32,48 +32,23 @@ def output_transform(args):
     return 200.0, 100.0
 
 
-class Latent_Model(nn.Module):
+class Latent_Model(_latent.LatentInputs, nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
-        latent_size = utils.load_model_config(self.args.auto_location)[0].encoding_size
-
-        # for embedding previously performed actions
-        layers = []
-        layers.append(nn.Sequential(nn.Linear(self.args.num_actions, 200), nn.ReLU()))
-        layers.append(nn.Sequential(nn.Linear(200, 100), nn.ReLU()))
-        layers.append(nn.Sequential(nn.Linear(100, latent_size)))
-        self.action_model = nn.Sequential(*layers)
-
-        # MLP over [action embedding | current latent | first latent] -> a value for every action
-        hidden_sizes = [latent_size * 3] + [args.hidden_dim for _ in range(args.layers - 1)] + [self.args.num_actions]
-        layers = []
-        for i in range(args.layers):
-            if i < args.layers - 1:
-                layers.append(nn.Sequential(nn.Linear(hidden_sizes[i], hidden_sizes[i + 1]), nn.ReLU()))
-            else:
-                layers.append(nn.Sequential(nn.Linear(hidden_sizes[i], hidden_sizes[i + 1])))
-        self.model = nn.Sequential(*layers)
+        # the embedding of the performed actions, then the MLP over [it | current latent | first latent] -> a value per action
+        self.action_model, self.model = _latent.latent_networks(args)
         self.fused_policy = bool(getattr(args, "fused_policy", False))
-        self._table = None
 
     def table(self):
-        """The ``ops.PolicyTable`` of this model's parameters (rebuilt when a parameter tensor was replaced)."""
-        seqs = list(self.action_model) + list(self.model)
-        params = [t for seq in seqs for t in (seq[0].weight, seq[0].bias)]
-        if self._table is None or any(a is not b for a, b in zip(self._table.params(), params)):
-            self._table = _ops.PolicyTable([(seq[0].weight, seq[0].bias, len(seq) > 1) for seq in seqs], len(self.action_model),
-                                           output_transform(self.args))
-        return self._table
+        return super().table(output_transform(self.args))
 
     def _inputs(self, obs):
-        dev = self.model[0][0].weight.device
-        return tuple(obs[k].float().to(dev) for k in ("mask", "latent", "first_latent"))
+        return self.inputs(obs)
 
     def _modules_forward(self, mask, latent, first_latent):
-        full_input = torch.cat((self.action_model(mask), latent, first_latent), dim=-1)
         scale, offset = output_transform(self.args)
-        return torch.sigmoid(self.model(full_input)) * scale - offset
+        return torch.sigmoid(self.mlp(mask, latent, first_latent)) * scale - offset
 
     def _fused_ok(self, mask):
         return self.fused_policy and mask.is_cuda and mask.dim() == 2 and _ops.policy_supported(self.table(), mask)

@@ -33,37 +33,26 @@ What differs from the reference, and why:
   ``args.zero_grad=True`` (``--zero_grad``).
 * An element with no open action raises a ``RuntimeError`` naming element and step; the reference's ``argmin`` would return an
   action already performed.
-* ``visualize`` raises ``NotImplementedError`` (pyrender), as in the other engines.
+* ``visualize`` raises ``NotImplementedError`` (pyrender; ``_core.refuse_visualize``).
 * The bare ``except: continue`` around ``env.reset`` (:112-115, :183-186) is ``except Exception``.
 * The loss is read once per ``train`` call, not per iteration (the reference's per-iteration message synchronises with the device).
 * Pretrained policies resolve to ``<pretrained_root>/policies/supervised/{t_p,t_g,v_t_p,v_t_g}/`` (``args.pretrained_root`` or
   ``PTEROTACTYL_PRETRAINED``) by the reference's ``(use_img, finger)`` rule; the reference reads them from inside its package.
 """
-import argparse
 import json
 import os
 from collections import namedtuple
 
 import numpy as np
 import torch
-from torch.utils.data import DataLoader
 
 from .... import ops
 from .... import optim as a3vt_optim
 from ...utility import utils
-from .. import environment
+from ...utility.utils import SummaryWriter
+from .. import _core
 from ..baselines import baselines
 from . import model as learning_model
-
-try:
-    from torch.utils.tensorboard import SummaryWriter
-except Exception:  # tensorboard is optional
-    class SummaryWriter:
-        def __init__(self, *a, **k):
-            pass
-
-        def add_scalars(self, *a, **k):
-            pass
 
 # Whether the engine turns the fused value network on, and scores the training targets as one batch, when args does not say: each
 # on only if the new form's p90 lies below the old form's p10 on an MI355X (tools/supervised_bench.py ->
@@ -74,7 +63,6 @@ FUSED_POLICY_DEFAULT = True
 BATCHED_TARGETS_DEFAULT = True
 
 TRAINING_ACTIONS = 5        # the literal 5 of the reference's random draw (:135-137)
-POLICY_DIRS = {(False, True): "t_p", (False, False): "t_g", (True, True): "v_t_p", (True, False): "v_t_g"}   # (use_img, finger)
 
 
 def _knob(args, name, default):
@@ -106,13 +94,11 @@ class FusedUpdate:
         return loss, values
 
 
-class Engine:
-    num_workers = 4
+class Engine(_core.EngineBase):
+    shuffle_train = True
 
     def __init__(self, args, sampler=None, loaders=None):
-        self.args = args
-        self.sampler = sampler
-        self.loaders = loaders
+        super().__init__(args, sampler, loaders)     # (device: where the policy's models live)
         self.results_dir = os.path.join("results", args.exp_type, args.exp_id)
         os.makedirs(self.results_dir, exist_ok=True)
         self.checkpoint_dir = os.path.join("experiments/checkpoint/", args.exp_type, args.exp_id)
@@ -122,10 +108,6 @@ class Engine:
         self.copied = []        # (shape, dtype) of every tensor `choose` brought to the host (tests)
         self.last = {}          # the last train iteration's random actions, targets, values and loss (tests, the bench)
         self._update = None
-        self.device = None      # where the policy's models live; None: the environment's device (the GPU)
-
-    def policy_device(self):
-        return utils._device() if self.device is None else torch.device(self.device)
 
     def make_models(self):
         if getattr(self.args, "fused_policy", None) is None:
@@ -133,11 +115,9 @@ class Engine:
         return [learning_model.Latent_Model(self.args).to(self.policy_device()) for _ in range(self.args.budget)]
 
     def __call__(self):
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: the reference renders predictions and actions with pyrender, which this package "
-                                      "does not have; run without --visualize")
+        _core.refuse_visualize(self.args)
         # setup the environment, policy and data
-        self.env = environment.ActiveTouch(self.args, sampler=self.sampler)
+        self.make_env()
         self.policy = baselines.even_sampler(self.args)
         train_loaders, valid_loaders = self.get_loaders()
         self.step = 0
@@ -172,17 +152,6 @@ class Engine:
         self.epoch = 0
         self.best_loss = 10000
         self.last_improvement = 0
-
-    # load data using pytorch dataloader
-    def get_loaders(self):
-        if self.loaders is not None:
-            return self.loaders
-        workers = getattr(self.args, "num_workers", self.num_workers)
-        train_loader = [] if self.args.eval else DataLoader(self.env.train_data, batch_size=self.args.env_batch_size, shuffle=True,
-                                                           num_workers=workers, collate_fn=self.env.train_data.collate)
-        valid_loader = DataLoader(self.env.valid_data, batch_size=self.args.env_batch_size, shuffle=False, num_workers=workers,
-                                  collate_fn=self.env.valid_data.collate)
-        return train_loader, valid_loader
 
     def choose(self, i, obs):
         """Model ``i``'s step -> (values (E, A) on the device, actions (E,) host int32): the lowest value among the actions
@@ -256,9 +225,13 @@ class Engine:
             writer.add_scalars(f"train_loss_{self.step}", {self.args.exp_id: self.train_loss}, self.epoch)
 
     # perform the validation
+    def take_step(self, i, obs):
+        _, action = self.choose(i, obs)
+        obs, _, done = self.env.step(action.numpy())
+        return action.long(), obs, done
+
     def validate(self, dataloader, writer=None):
-        if getattr(self.args, "visualize", False):
-            raise NotImplementedError("visualize: needs pyrender, which this package does not have")
+        _core.refuse_visualize(self.args)
         scores, actions, names = [], [], []
         self.models[self.step].eval()
         for v, batch in enumerate(dataloader):
@@ -268,23 +241,13 @@ class Engine:
             except Exception:
                 continue
             self.policy.reset()
-            cur_scores, cur_actions = [obs["score"]], []
-            for i in range(self.step + 1):
-                _, action = self.choose(i, obs)
-                obs, _, _ = self.env.step(action.numpy())
-                cur_scores.append(obs["score"])
-                cur_actions.append(action.long())
-            scores.append(torch.stack(cur_scores).permute(1, 0))
-            actions.append(torch.stack(cur_actions).permute(1, 0))
-            print_score = (scores[-1][:, -1] / scores[-1][:, 0]).mean()
-            print_reward = ((scores[-1][:, 0] - scores[-1][:, -1]) / scores[-1][:, 0]).mean()
-            print(f"Valid || score: {print_score:.4f}, reward = {print_reward:.4f}")
-        scores = torch.cat(scores)
-        rewards = ((scores[:, 0] - scores[:, -1]) / scores[:, 0]).mean()
-        self.current_loss = (scores[:, -1] / scores[:, 0]).mean()
-        self.scores, self.chosen, self.names = scores, torch.cat(actions), names
-        message = f"Total Valid || step {self.step + 1} || score: {self.current_loss:.4f}, reward = {rewards:.4f}"
-        print("*" * len(message) + "\n" + message + "\n" + "*" * len(message))
+            cur_scores, cur_actions = self.play(obs, self.take_step, steps=self.step + 1)
+            scores.append(cur_scores)
+            actions.append(cur_actions)
+            now = _core.summary(cur_scores)
+            print(f"Valid || score: {now['score']:.4f}, reward = {now['reward']:.4f}")
+        total = self.report(scores, actions, names, f"Total Valid || step {self.step + 1} || score: {{score:.4f}}, reward = {{reward:.4f}}")
+        self.current_loss = total["score"]
         if not self.args.eval and writer is not None:
             writer.add_scalars(f"valid_loss_{self.step}", {self.args.exp_id: self.current_loss}, self.epoch)
 
@@ -304,11 +267,7 @@ class Engine:
         return None         # (as the reference: neither saved nor out of patience)
 
     def pretrained_location(self):
-        root = getattr(self.args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
-        if not root:
-            raise FileNotFoundError("a3vt: set args.pretrained_root or PTEROTACTYL_PRETRAINED to the directory the reference's "
-                                    "download_models.sh fills (pterotactyl/pretrained/)")
-        return os.path.join(root, "policies", "supervised", POLICY_DIRS[(bool(self.args.use_img), bool(self.args.finger))])
+        return os.path.join(utils.pretrained_root(self.args), "policies", "supervised", _core.kind(self.args))
 
     def load(self, train=False):
         if self.args.pretrained:
@@ -336,28 +295,10 @@ class Engine:
 
 def get_parser():
     """The reference's flags and defaults (:317-437) and this package's."""
-    pretrained = os.environ.get("PTEROTACTYL_PRETRAINED", "")
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--limit_data", action="store_true", default=False, help="use less data, for debugging.")
-    parser.add_argument("--finger", action="store_true", default=False, help="use only one finger.")
-    parser.add_argument("--touch_location", type=str, default=os.path.join(pretrained, "reconstruction/touch/best/"),
-                        help="the location of the touch part prediction.")
-    parser.add_argument("--vision_location", type=str, default=os.path.join(pretrained, "reconstruction/vision/t_p/"),
-                        help="the location of the vision part prediction.")
-    parser.add_argument("--auto_location", type=str, default=os.path.join(pretrained, "reconstruction/auto/t_p/"),
-                        help="the location of the autoencoder part prediction.")
-    parser.add_argument("--number_points", type=int, default=30000, help="number of points sampled for the chamfer distance.")
+    parser = _core.common_parser(auto_location=True, pretrained=True)
     parser.add_argument("--epoch", type=int, default=3000, help="number of epochs per step")
-    parser.add_argument("--seed", type=int, default=0, help="Setting for the random seed.")
-    parser.add_argument("--env_batch_size", type=int, default=3, help="Size of the batch.")
-    parser.add_argument("--use_img", action="store_true", default=False, help="To use the image.")
-    parser.add_argument("--loss_coeff", type=float, default=9000.0, help="Coefficient for loss term.")
-    parser.add_argument("--num_grasps", type=int, default=5, help="Number of grasps to train with. ")
-    parser.add_argument("--num_actions", type=int, default=50, help="number of action options")
     parser.add_argument("--eval", action="store_true", default=False, help="for evaluating on test set")
-    parser.add_argument("--budget", type=int, default=5, help="number of graspsp to perform")
     parser.add_argument("--exp_id", type=str, default="test", help="The experiment name.")
-    parser.add_argument("--exp_type", type=str, default="test", help="The experiment type.")
     parser.add_argument("--layers", type=int, default=4, help="Number of layers in the q network")
     parser.add_argument("--patience", type=int, default=25, help="number of epochs without progress before stopping")
     parser.add_argument("--training_actions", type=int, default=5,
@@ -366,14 +307,6 @@ def get_parser():
     parser.add_argument("--train_steps", type=int, default=200, help="number of training steps per epoch")
     parser.add_argument("--normalize", type=int, default=0, help="number of training steps per epoch")
     parser.add_argument("--lr", type=float, default=0.001, help="Initial learning rate.")
-    parser.add_argument("--visualize", action="store_true", default=False, help="not built: needs pyrender")
-    parser.add_argument("--pretrained_recon", action="store_true", default=False,
-                        help="use the pretrained reconstruction models to train")
-    parser.add_argument("--pretrained", action="store_true", default=False, help="use the pretrained policy")
-    parser.add_argument("--data_root", type=str, default=None, help="dataset directory (default: PTEROTACTYL_DATA)")
-    parser.add_argument("--pretrained_root", type=str, default=None, help="pretrained/ directory (default: PTEROTACTYL_PRETRAINED)")
-    parser.add_argument("--recorded", type=str, default=None,
-                        help="replay touch signals from this dataset root's grasp_info/ (RecordedSampler) instead of simulating")
     parser.add_argument("--fused_policy", dest="fused_policy", action="store_true", default=None,
                         help="evaluate and train the value network on the fused kernels")
     parser.add_argument("--no_fused_policy", dest="fused_policy", action="store_false", help="... on the torch modules")
@@ -386,14 +319,7 @@ def get_parser():
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
-    args.use_recon = False
-    args.use_latent = True
-    sampler = None
-    if args.recorded:
-        from ..recorded import RecordedSampler
-        sampler = RecordedSampler(args.recorded)
-    return Engine(args, sampler=sampler)()
+    return _core.run(Engine, get_parser(), argv, after_parse=_core.latent_only)
 
 
 if __name__ == "__main__":

@@ -23,27 +23,14 @@ import torch
 
 from . import model
 from ...utility import data_loaders, utils
+from ...utility.utils import SummaryWriter
 from .... import ops as _ops
 from .... import optim as a3vt_optim
-
-try:
-    from torch.utils.tensorboard import SummaryWriter
-except Exception:  # tensorboard is optional
-    class SummaryWriter:
-        def __init__(self, *a, **k):
-            pass
-
-        def add_scalars(self, *a, **k):
-            pass
 
 
 def pretrained_location(args):
     """Directory of the pretrained touch model (the reference: ``pretrained/reconstruction/touch/best/``)."""
-    root = getattr(args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
-    if not root:
-        raise FileNotFoundError("a3vt: set args.pretrained_root or PTEROTACTYL_PRETRAINED to the directory the reference's "
-                                "download_models.sh fills (pterotactyl/pretrained/)")
-    return os.path.join(root, "reconstruction", "touch", "best")
+    return os.path.join(utils.pretrained_root(args), "reconstruction", "touch", "best")
 
 
 class Engine:

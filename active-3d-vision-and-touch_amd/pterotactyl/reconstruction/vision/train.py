@@ -27,19 +27,10 @@ import torch.optim as optim
 
 from . import model
 from ...utility import data_loaders, utils
+from ...utility.utils import SummaryWriter
 from .... import distributed as adist
 from .... import ops as _ops
 from .... import optim as a3vt_optim
-
-try:
-    from torch.utils.tensorboard import SummaryWriter
-except Exception:  # tensorboard is optional
-    class SummaryWriter:
-        def __init__(self, *a, **k):
-            pass
-
-        def add_scalars(self, *a, **k):
-            pass
 
 
 def pretrained_location(args):
@@ -51,8 +42,9 @@ def pretrained_location(args):
     explicit = getattr(args, "pretrained_location", None)
     if explicit:
         return explicit
-    root = getattr(args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
-    if not root:
+    try:
+        root = utils.pretrained_root(args)
+    except FileNotFoundError:
         try:
             from pterotactyl import pretrained as _pre      # the reference's own package, when it is installed
             root = os.path.dirname(_pre.__file__)

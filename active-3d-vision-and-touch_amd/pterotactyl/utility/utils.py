@@ -12,6 +12,9 @@ Differences that callers can see:
 * sampling draws come from Philox4x32-10 seeded from torch's global CPU generator (so ``torch.manual_seed``
   still makes a run reproducible) instead of ``torch.multinomial`` / ``torch.rand`` on the device; pass
   ``samples=`` to inject explicit ``(face_idx, u, v)`` draws (parity tests).
+
+This package's own: ``pretrained_root(args)`` (where the reference's pretrained files are: every engine and trainer asks here) and
+``SummaryWriter`` (tensorboard's, or a no-op stub where tensorboard is missing).
 """
 import json
 import os
@@ -25,10 +28,30 @@ from ... import mesh as _mesh
 from ... import ops as _ops
 
 
+try:
+    from torch.utils.tensorboard import SummaryWriter
+except Exception:  # tensorboard is optional
+    class SummaryWriter:
+        def __init__(self, *a, **k):
+            pass
+
+        def add_scalars(self, *a, **k):
+            pass
+
+
 def _device():
     if not torch.cuda.is_available():
         raise RuntimeError("a3vt: no ROCm GPU visible — the MI355X path has no CPU fallback")
     return torch.device("cuda", torch.cuda.current_device())
+
+
+def pretrained_root(args):
+    """The directory the reference's ``download_models.sh`` fills: ``args.pretrained_root``, else ``$PTEROTACTYL_PRETRAINED``."""
+    root = getattr(args, "pretrained_root", None) or os.environ.get("PTEROTACTYL_PRETRAINED")
+    if not root:
+        raise FileNotFoundError("a3vt: set args.pretrained_root or PTEROTACTYL_PRETRAINED to the directory the reference's "
+                                "download_models.sh fills (pterotactyl/pretrained/)")
+    return root
 
 
 class AdjInfo(dict):
