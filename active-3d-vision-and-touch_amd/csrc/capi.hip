@@ -1375,6 +1375,95 @@ int a3vt_candidate_tally(const float *scores, const int32_t *candidates, const f
                                 static_cast<hipStream_t>(stream));
 }
 
+// ---- the rendered touch sampler (touch_render.hip) ---------------------------------------------------------------------------------
+namespace {
+struct TouchPtr {
+  const char *name;
+  const void *p;
+  bool required;
+  const char *why;
+};
+// The finish launch's own arguments (shared by both entries): 0, or -1 with the message set.
+int touch_finish_check(const char *who, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, const float *depth,
+                       const float *touch, const float *points, const int32_t *count, const int32_t *status) {
+  if (I < 1 || I > kTouchMaxImages) {
+    set_error("%s: I=%d outside 1..%d", who, I, kTouchMaxImages);
+    return -1;
+  }
+  if (!(max_depth > 0.f)) {
+    set_error("%s: max_depth=%g must be > 0", who, (double)max_depth);
+    return -1;
+  }
+  if (!(yfov > 0.f && (double)yfov < 3.14159265358979323846)) {
+    set_error("%s: yfov=%g outside (0, pi)", who, (double)yfov);
+    return -1;
+  }
+  const TouchPtr ptrs[] = {{"cam_pos", cam_pos, true, "required"},
+                           {"cam_rot", cam_rot, true, "required"},
+                           {"depth", depth, true, "required"},
+                           {"touch", touch, false, ""},
+                           {"points", points, count != nullptr, "points and count go together"},
+                           {"count", count, points != nullptr, "points and count go together"},
+                           {"status", status, true, "required"}};
+  for (const auto &a : ptrs) {
+    if (a.required && !a.p) {
+      set_error("%s: %s=NULL: %s", who, a.name, a.why);
+      return -1;
+    }
+    if (!aligned_to(a.p, 4)) {
+      set_error("%s: %s=%p is not 4-byte aligned", who, a.name, a.p);
+      return -1;
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+int a3vt_touch_finish(const float *depth, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float *touch,
+                      float *points, int32_t *count, int32_t *status, void *stream) {
+  if (touch_finish_check("touch_finish", cam_pos, cam_rot, I, max_depth, yfov, depth, touch, points, count, status)) return -1;
+  return launch_touch_finish(depth, cam_pos, cam_rot, I, max_depth, yfov, touch, points, count, status, static_cast<hipStream_t>(stream));
+}
+
+int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, const int32_t *face_offset, int M, const int32_t *image_mesh,
+                      const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float znear, float zfar, float *depth,
+                      float *touch, float *points, int32_t *count, int32_t *status, void *stream) {
+  if (M < 1 || M > kTouchMaxMeshes) {
+    set_error("touch_render: M=%d outside 1..%d", M, kTouchMaxMeshes);
+    return -1;
+  }
+  if (V < 0 || V > kTouchMaxIndex || F < 0 || F > kTouchMaxIndex) {
+    set_error("touch_render: V=%d F=%d outside 0..%d", V, F, kTouchMaxIndex);
+    return -1;
+  }
+  if (!(znear > 0.f)) {
+    set_error("touch_render: znear=%g must be > 0", (double)znear);
+    return -1;
+  }
+  if (!(znear < zfar)) {
+    set_error("touch_render: zfar=%g must be above znear=%g", (double)zfar, (double)znear);
+    return -1;
+  }
+  const TouchPtr ptrs[] = {{"verts", verts, V > 0, "required when V > 0"},
+                           {"faces", faces, F > 0, "required when F > 0"},
+                           {"face_offset", face_offset, true, "required"},
+                           {"image_mesh", image_mesh, true, "required"}};
+  for (const auto &a : ptrs) {
+    if (a.required && !a.p) {
+      set_error("touch_render: %s=NULL: %s", a.name, a.why);
+      return -1;
+    }
+    if (!aligned_to(a.p, 4)) {
+      set_error("touch_render: %s=%p is not 4-byte aligned", a.name, a.p);
+      return -1;
+    }
+  }
+  if (touch_finish_check("touch_render", cam_pos, cam_rot, I, max_depth, yfov, depth, touch, points, count, status)) return -1;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = launch_touch_depth(verts, V, faces, F, face_offset, M, image_mesh, cam_pos, cam_rot, I, yfov, znear, zfar, depth, s)) return rc;
+  return launch_touch_finish(depth, cam_pos, cam_rot, I, max_depth, yfov, touch, points, count, status, s);
+}
+
 // ---- the supervised latent policy's value network (latent_policy.hip) ------------------------------------------------------------
 namespace {
 static_assert(sizeof(a3vt_mlp) == sizeof(PolicyNet) && sizeof(a3vt_mlp_layer) == sizeof(PolicyLayer) &&

@@ -389,6 +389,17 @@ int launch_candidate_tally(const float *scores, const int32_t *candidates, const
                            int A, double unvisited, double *sums, double *checks, double *votes, int32_t *best, float *best_score,
                            hipStream_t s);
 
+// touch_render.hip: the rendered touch sampler (simulator/scene/instance.py:121-258) — a ray-cast depth map per finger view, then
+// status, gel image and contact points from it: two launches for a batch of views
+constexpr int kTouchRes = 121;            // the reference's point grid hard-codes it (instance.py:172-184)
+constexpr int kTouchFaceChunk = 256;      // faces culled, and survivors held in LDS, at a time
+constexpr int kTouchMaxImages = 1 << 16, kTouchMaxMeshes = 1 << 20, kTouchMaxIndex = 1 << 28;   // I, M, and V and F
+int launch_touch_depth(const float *verts, int V, const int32_t *faces, int F, const int32_t *face_offset, int M, const int32_t *image_mesh,
+                       const float *cam_pos, const float *cam_rot, int I, float yfov, float znear, float zfar, float *depth,
+                       hipStream_t s);
+int launch_touch_finish(const float *depth, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float *touch,
+                        float *points, int32_t *count, int32_t *status, hipStream_t s);
+
 // latent_policy.hip: the supervised policy's value network (policies/supervised/model.py), its loss and its backward.  The layer
 // table travels by value in the kernel arguments (a3vt_mlp of include/a3vt.h, field for field).
 constexpr int kPolicyMaxLayers = 16;     // layers of a table

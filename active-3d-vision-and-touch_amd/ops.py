@@ -1297,6 +1297,78 @@ def _candidate_tally_launch(scores, candidates, first_score, taken, sums, checks
     return best, best_score
 
 
+TOUCH_RES = 121                                     # csrc/kernels.h's kTouchRes
+TOUCH_DEFAULTS = dict(max_depth=0.025, yfov=40.0 / 180.0 * np.pi, znear=1e-4, zfar=10.0)   # the reference's sensor and camera
+
+
+def _touch_views(cam_pos, cam_rot):
+    cam_pos, cam_rot = _req(cam_pos, "cam_pos"), _req(cam_rot, "cam_rot")
+    I = cam_pos.shape[0]
+    if cam_pos.shape != (I, 3) or cam_rot.shape != (I, 3, 3) or I < 1:
+        raise ValueError(f"a3vt: touch_render wants cam_pos (I, 3) and cam_rot (I, 3, 3), I >= 1, got {tuple(cam_pos.shape)} and "
+                         f"{tuple(cam_rot.shape)}")
+    return cam_pos, cam_rot, I
+
+
+def _touch_outputs(I, device, want_touch, want_points):
+    pix = TOUCH_RES * TOUCH_RES
+    touch = torch.empty((I, TOUCH_RES, TOUCH_RES, 3), dtype=torch.float32, device=device) if want_touch else None
+    points = torch.empty((I, pix, 3), dtype=torch.float32, device=device) if want_points else None
+    count = torch.empty(I, dtype=torch.int32, device=device) if want_points else None
+    return touch, points, count, torch.empty(I, dtype=torch.int32, device=device)
+
+
+def _touch_result(depth, touch, points, count, status):
+    out = {"depth": depth, "status": status}
+    if touch is not None:
+        out["touch"] = touch
+    if points is not None:
+        out["points"], out["count"] = points, count
+    return out
+
+
+def touch_render(verts, faces, face_offset, image_mesh, cam_pos, cam_rot, max_depth=TOUCH_DEFAULTS["max_depth"],
+                 yfov=TOUCH_DEFAULTS["yfov"], znear=TOUCH_DEFAULTS["znear"], zfar=TOUCH_DEFAULTS["zfar"], want_touch=True,
+                 want_points=True):
+    """The rendered touch sampler's signals for I finger views over a table of M meshes (reference ``simulator/scene/instance.py``
+    ``:121-258``; ``a3vt_touch_render``, csrc/touch_render.hip: two launches on the current stream, no host synchronisation).
+    ``verts`` (V, 3) float32 and ``faces`` (F, 3) int32 with global indices, ``face_offset`` (M + 1,) int32, ``image_mesh`` (I,)
+    int32, ``cam_pos`` (I, 3) / ``cam_rot`` (I, 3, 3) float32: the finger frames as ``*_ref_frame.npy`` stores them.  Returns a dict:
+    ``depth`` (I, 121, 121), ``status`` (I,) int32 (1 = "touch"), with ``want_touch`` ``touch`` (I, 121, 121, 3) in 0..255, with
+    ``want_points`` ``points`` (I, 14641, 3) and ``count`` (I,) int32: view i's contact points are ``points[i, :count[i]]``, in
+    row-major pixel order; the rows after them are not written.  The whole contract is in ``include/a3vt.h``."""
+    verts, faces = _req(verts, "verts"), _req(faces, "faces", torch.int32)
+    face_offset, image_mesh = _req(face_offset, "face_offset", torch.int32), _req(image_mesh, "image_mesh", torch.int32)
+    cam_pos, cam_rot, I = _touch_views(cam_pos, cam_rot)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"a3vt: touch_render wants verts (V, 3) and faces (F, 3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    if face_offset.dim() != 1 or face_offset.numel() < 2 or image_mesh.shape != (I,):
+        raise ValueError(f"a3vt: touch_render wants face_offset (M + 1,), M >= 1, and image_mesh ({I},), got "
+                         f"{tuple(face_offset.shape)} and {tuple(image_mesh.shape)}")
+    depth = torch.empty((I, TOUCH_RES, TOUCH_RES), dtype=torch.float32, device=verts.device)
+    touch, points, count, status = _touch_outputs(I, verts.device, want_touch, want_points)
+    _lib.check(_lib.load().a3vt_touch_render(_lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], _lib.ptr(face_offset),
+                                             face_offset.numel() - 1, _lib.ptr(image_mesh), _lib.ptr(cam_pos), _lib.ptr(cam_rot), I,
+                                             float(max_depth), float(yfov), float(znear), float(zfar), _lib.ptr(depth), _lib.ptr(touch),
+                                             _lib.ptr(points), _lib.ptr(count), _lib.ptr(status), _stream()), "touch_render")
+    return _touch_result(depth, touch, points, count, status)
+
+
+def touch_finish(depth, cam_pos, cam_rot, max_depth=TOUCH_DEFAULTS["max_depth"], yfov=TOUCH_DEFAULTS["yfov"], want_touch=True,
+                 want_points=True):
+    """``touch_render``'s second launch alone (``a3vt_touch_finish``) on depth maps (I, 121, 121) the caller supplies — recorded
+    ones, or a test's: the same dict, ``depth`` as given."""
+    depth = _req(depth, "depth")
+    cam_pos, cam_rot, I = _touch_views(cam_pos, cam_rot)
+    if depth.shape != (I, TOUCH_RES, TOUCH_RES):
+        raise ValueError(f"a3vt: touch_finish wants depth ({I}, {TOUCH_RES}, {TOUCH_RES}), got {tuple(depth.shape)}")
+    touch, points, count, status = _touch_outputs(I, depth.device, want_touch, want_points)
+    _lib.check(_lib.load().a3vt_touch_finish(_lib.ptr(depth), _lib.ptr(cam_pos), _lib.ptr(cam_rot), I, float(max_depth), float(yfov),
+                                             _lib.ptr(touch), _lib.ptr(points), _lib.ptr(count), _lib.ptr(status), _stream()),
+               "touch_finish")
+    return _touch_result(depth, touch, points, count, status)
+
+
 # csrc/kernels.h's kPolicyMaxRows / kPolicyMaxWidth / kPolicyMaxLayers (a3vt_latent_policy_limit returns the library's own): rows
 # of a call (and steps of the loss), every layer's in and out, layers of a table.
 LATENT_POLICY_MAX = dict(rows=4096, width=1024, layers=16)

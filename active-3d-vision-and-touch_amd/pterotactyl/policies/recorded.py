@@ -30,19 +30,35 @@ FINGERS = 4
 NO_CONTACT = "no_intersection"
 
 
-def _tree_record(root, obj, action):
+def object_id(name):
+    """The id of a ``names`` entry of ``load_objects``: its basename."""
+    return os.path.basename(os.path.normpath(str(name)))
+
+
+def tree_frames(root, obj, action):
+    """The finger frames of one grasp in a dataset tree -> ``(pos (4, 3), rot (4, 3, 3), present (4,) bool)`` float32, zeros for
+    a finger without ``<finger>_ref_frame.npy``; None without the grasp's directory.  (Shared with ``rendered.py``.)"""
     d = os.path.join(root, "grasp_info", obj, str(action))
     if not os.path.isdir(d):
         return None
-    rec = {"touch": np.zeros((FINGERS, 121, 121, 3), np.float32), "pos": np.zeros((FINGERS, 3), np.float32),
-           "rot": np.zeros((FINGERS, 3, 3), np.float32), "status": [NO_CONTACT] * FINGERS}
+    pos, rot, present = np.zeros((FINGERS, 3), np.float32), np.zeros((FINGERS, 3, 3), np.float32), np.zeros(FINGERS, bool)
     for f in range(FINGERS):
         frame = os.path.join(d, f"{f}_ref_frame.npy")
         if not os.path.exists(frame):
             continue
         ref = np.load(frame, allow_pickle=True).item()
-        rec["pos"][f], rec["rot"][f] = np.asarray(ref["pos"]).reshape(3), np.asarray(ref["rot"]).reshape(3, 3)
-        touch = os.path.join(d, f"{f}_touch.npy")
+        pos[f], rot[f], present[f] = np.asarray(ref["pos"]).reshape(3), np.asarray(ref["rot"]).reshape(3, 3), True
+    return pos, rot, present
+
+
+def _tree_record(root, obj, action):
+    frames = tree_frames(root, obj, action)
+    if frames is None:
+        return None
+    pos, rot, present = frames
+    rec = {"touch": np.zeros((FINGERS, 121, 121, 3), np.float32), "pos": pos, "rot": rot, "status": [NO_CONTACT] * FINGERS}
+    for f in np.flatnonzero(present):
+        touch = os.path.join(root, "grasp_info", obj, str(action), f"{f}_touch.npy")
         if os.path.exists(touch):
             rec["touch"][f] = np.load(touch)
             rec["status"][f] = "touch"
@@ -62,7 +78,7 @@ class RecordedSampler:
         self.ids = []
 
     def load_objects(self, batch, from_dataset=True, scale=3.1):
-        self.ids = [os.path.basename(os.path.normpath(str(name))) for name in batch]
+        self.ids = [object_id(name) for name in batch]
 
     def record(self, obj, action):
         if isinstance(self.source, Mapping):

@@ -596,6 +596,61 @@ int a3vt_candidate_tally(const float *scores, const int32_t *candidates, const f
                          double unvisited, double *sums, double *checks, double *votes, int32_t *best, float *best_score, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The rendered touch sampler: from finger frames and triangles to every signal of simulator/scene/instance.py:121-258.
+ *
+ * A batch of I finger views over a table of M meshes.
+ *   verts       [V][3] fp32, the meshes' vertices concatenated
+ *   faces       [F][3] int32, indices into verts (already global), as stored: no duplicated or flipped copies are needed
+ *   face_offset [M + 1] int32: mesh m owns faces face_offset[m] .. face_offset[m + 1] - 1
+ *   image_mesh  [I] int32: the mesh view i looks at
+ *   cam_pos     [I][3], cam_rot [I][3][3]: the finger frame {"pos", "rot"} as the dataset's *_ref_frame.npy stores it
+ *   max_depth, yfov (radians), znear, zfar: the reference's 0.025, 40 degrees, 1e-4, 10
+ *   depth       [I][121][121] out
+ *   touch       [I][121][121][3] out, or NULL
+ *   points      [I][14641][3] out with count [I] int32 out: both or neither.  Rows from count[i] on are not written.
+ *   status      [I] int32 out: 1 = "touch", 0 = "no_touch"
+ *
+ * Depth (a3vt_touch_render's first launch).
+ * - The camera rotation is C = cam_rot . R_y(-90 deg) (instance.py:127-133): the camera looks along the finger's +x.
+ * - It is a pinhole at cam_pos looking down its -z.  Pixel (r, c), row 0 at the top, has the centre x = (c + 0.5) / 121 * 2 - 1,
+ *   y = 1 - (r + 0.5) / 121 * 2 and the ray (x tan(yfov / 2), y tan(yfov / 2), -1) in the eye frame.
+ * - depth[r][c] is the ray parameter (= -z in the eye frame) of the nearest triangle hit with znear <= depth <= zfar; 0 without one.
+ * - Casting is two-sided and inclusive on edges.  Across an edge that two faces share BY VERTEX INDEX it is watertight: no ray
+ *   passes between them.
+ * - This is ray casting at pixel centres.  It has not been compared with pyrender's rasteriser.
+ *
+ * Finish (the second launch; a3vt_touch_finish is that launch alone on depth maps the caller supplies).
+ * - Every comparison of a depth with max_depth is an fp32 comparison, as NumPy makes it for a float32 map.
+ * - status is 1 iff #(depth <= max_depth) - #(depth == 0) > 0 (instance.py:142).
+ * - touch is depth_to_touch (:207-258) in fp32: pixels with depth > max_depth or == 0 become 1; gel = -(d - max_depth), 0 where
+ *   d >= max_depth, then * 6 / max_depth / 30 + 0.4; the 7 x 7 mean with the boundary d c b a | a b c d of the map before any
+ *   write-back replaces the zeroed pixels; np.gradient (central differences, one-sided on the border); the normal (-zx, -zy, 1)
+ *   normalised; position (r / 121, c / 121, gel); lights (-0.5, 0.5, 1), (1.3, -0.4, 1), (1.3, 1.4, 1), one per channel;
+ *   clip(2 n . l, 0, 1) * 255.
+ * - points is depth_to_points (:154-204): with d as after the range step and xs = c - 60, ys = r - 60, the pixels with d < 1 give
+ *   C . (d |xs| / 60 tan(yfov / 2) sign(xs), -d |ys| / 60 tan(yfov / 2) sign(ys), -d) + cam_pos, in row-major pixel order.
+ *
+ * Both launches run on `stream`; no allocation, no host synchronisation, no environment variable, no atomics, every sum in a fixed
+ * order: the same bits on every call, and a view's outputs do not depend on what else is in the batch.
+ *
+ * What the host cannot check is made safe in the kernel, given V and F:
+ * - image_mesh[i] is clamped into [0, M).
+ * - face_offset entries are clamped into [0, F], and an end below its start counts as the start (an empty mesh).
+ * - A face with an index outside [0, V) is skipped.
+ *
+ * Limits.
+ * - 1 <= I <= 65536, 1 <= M <= 1048576, 0 <= V, F <= 268435456; verts may be NULL when V == 0, faces when F == 0.
+ * - max_depth > 0; 0 < znear < zfar; 0 < yfov < pi.
+ * - Pointers are 4-byte aligned.
+ * - Anything else, or a missing required pointer, returns non-zero with a message in a3vt_last_error that names the argument and
+ *   its value.  Nothing is launched. */
+int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, const int32_t *face_offset, int M, const int32_t *image_mesh,
+                      const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float znear, float zfar, float *depth,
+                      float *touch, float *points, int32_t *count, int32_t *status, void *stream);
+int a3vt_touch_finish(const float *depth, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float *touch,
+                      float *points, int32_t *count, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The supervised latent policy's value network (policies/supervised/model.py, train.py:119-158), fp32 throughout.
  *
  * The network is a table of at most 16 layers, read on the host and passed to the kernels by value.  Layer l computes
