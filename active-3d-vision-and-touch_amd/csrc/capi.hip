@@ -1844,7 +1844,9 @@ int a3vt_posenc_mask_fwd(const float *verts, const float *mask, int m, int input
 int a3vt_posenc_mask_bwd(const float *verts, const float *mask, int m, int input_size, const float *pe_params,
                          const float *grad_feats, int ld_feats, float *grad_verts, float *grad_params, float *scratch,
                          void *stream) {
-  A3VT_CHECK_ARG(verts && mask && pe_params && grad_feats && grad_verts && grad_params && scratch && m > 0);
+  // (any ld_feats >= input_size and any 4-byte-aligned grad_feats: the kernel takes 16-byte loads only where they are aligned)
+  A3VT_CHECK_ARG(verts && mask && pe_params && grad_feats && grad_verts && grad_params && scratch && m > 0 &&
+                 ld_feats >= input_size);
   ProfScope psc(PROF_ENC, static_cast<hipStream_t>(stream));
   return launch_posenc_bwd(verts, mask, m, input_size, pe_params, grad_feats, ld_feats, grad_verts, grad_params,
                            scratch, static_cast<hipStream_t>(stream));
@@ -1861,6 +1863,7 @@ size_t a3vt_posenc_wide_scratch_bytes(int m, int input_size, int need_backward) 
 int a3vt_posenc_wide_fwd(const float *verts, const float *mask, int m, int input_size, const float *pe_params, float *feats,
                          int ld_feats, float *acts, float *scratch, int gemm_bf16, void *stream) {
   A3VT_CHECK_ARG(verts && mask && pe_params && feats && acts && scratch && m > 0);
+  A3VT_CHECK_ARG(posenc_wide_supported(input_size) && ld_feats == input_size);   // before anything touches the device
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
   A3VT_CHECK_ARG(gemm_bf16 == GEMM_FP32 || gemm_bf16 == GEMM_BF16_OPERANDS);
@@ -1871,6 +1874,7 @@ int a3vt_posenc_wide_bwd(const float *verts, const float *mask, int m, int input
                          const float *grad_feats, int ld_feats, const float *acts, float *grad_verts, float *grad_params,
                          float *scratch, int gemm_bf16, void *stream) {
   A3VT_CHECK_ARG(verts && mask && pe_params && grad_feats && acts && grad_verts && grad_params && scratch && m > 0);
+  A3VT_CHECK_ARG(posenc_wide_supported(input_size) && ld_feats == input_size);
   const float *zeros = zero_page();
   A3VT_CHECK_ARG(zeros != nullptr);
   A3VT_CHECK_ARG(gemm_bf16 == GEMM_FP32 || gemm_bf16 == GEMM_BF16_OPERANDS);

@@ -1181,6 +1181,12 @@ int dw_num_slabs(int n_out) {
 int dw_images(const DwArgs &a) { return a.mode != GEMM_FP32X3 && dww_ok(a) ? dww_images() : dw_num_slabs(a.n_out); }
 int dw_slab_capacity(int n_out) { return dw_num_slabs(n_out) > dww_images() ? dw_num_slabs(n_out) : dww_images(); }
 
+// A 16-row stage of X | dZ0 | dZ1 rows (row-major operands) in 1 KB units, 48 at the most
+constexpr int kDwStageUnits = 48;
+bool dw_rows_fit(int ldx, int ldz0, int ldz1) {
+  return (16 * ldx + 255) / 256 + (16 * ldz0 + 255) / 256 + (16 * ldz1 + 255) / 256 <= kDwStageUnits;
+}
+
 int launch_dw(const DwArgs &a0, hipStream_t s) {
   if (a0.mode == GEMM_FP32X3) return launch_dw3(a0, s);   // split-operand mode (gcn_gemm3.hip)
   DwArgs a = a0;
@@ -1208,7 +1214,7 @@ int launch_dw(const DwArgs &a0, hipStream_t s) {
     return -1;
   }
   const int xin = nbq + (16 * wrm + 255) / 256, ain = (16 * a.ldz0 + 255) / 256, gin = (16 * a.ldz1 + 255) / 256;
-  if (xin + ain + gin > 48) {
+  if (xin + ain + gin > kDwStageUnits) {
     set_error("dw: rows too wide (%d + %d + %d floats)", a.ldx, a.ldz0, a.ldz1);
     return -1;
   }

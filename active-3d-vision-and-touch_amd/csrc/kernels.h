@@ -141,6 +141,8 @@ bool dw3_ok(const DwArgs &a);
 int launch_dw3(const DwArgs &a, hipStream_t s);
 // True when dw_kernel can take the first 4 * quads columns of a k_in-wide X quad-major (they must end where a wave's input tiles end).
 bool dw_quad_major_ok(int k_in, int quads);
+// True when dw_kernel can stage row-major rows of these lengths (X, dZ0, dZ1: floats per row).
+bool dw_rows_fit(int ldx, int ldz0, int ldz1);
 int launch_dw(const DwArgs &a, hipStream_t s);
 // gcn_dww.hip: the hidden layers' dW on hybrid rows, waves specialised (round 6); same slab images as launch_dw
 bool dww_ok(const DwArgs &a);

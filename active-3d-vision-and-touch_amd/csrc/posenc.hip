@@ -307,7 +307,10 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
 
   const int ntile = (m + 15) >> 4, nwave = gridDim.x * kPEBwdWaves;
   // a tile's inputs: the 16 x 52 gradient rows as 208 16-byte pieces (four per lane; columns >= I are zeroed), the
-  // lane's vertex l16 (its position and token)
+  // lane's vertex l16 (its position and token).  A piece is one 16-byte load only when every piece of every row is
+  // 16-byte aligned (ld % 4 == 0 and an aligned base; the same answer in every lane of the launch); any other
+  // ld >= I or base (ld = 50: odd rows sit 8 bytes off) takes the element loads.
+  const bool vec16 = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(gfeats) & 15) == 0;
   struct Inputs { f32x4 g[4]; float p[3]; int tok; bool live; };
   auto fetch = [&](int tile) {
     Inputs in;
@@ -317,7 +320,7 @@ __global__ __launch_bounds__(kPEBwdThreads, 2) void posenc_bwd_kernel(const floa
       const long long v = (long long)tile * 16 + r;
       f32x4 g = {0.f, 0.f, 0.f, 0.f};
       if (i < 208 && v < m) {
-        if (c4 * 4 + 3 < ld) {
+        if (vec16 && c4 * 4 + 3 < ld) {
           g = *reinterpret_cast<const f32x4 *>(gfeats + v * ld + c4 * 4);
         } else {
 #pragma unroll

@@ -255,8 +255,13 @@ static RowGemmArgs plain_gemm(const float *a, int lda, int k, const float *bt, i
 }  // namespace
 
 bool posenc_wide_supported(int input_size) {
-  // I / 4 and I / 2 whole, rows 16-byte aligned, and the widest augmented row within dw_kernel's 320 input channels
-  return input_size >= 16 && input_size % 8 == 0 && WideDims(input_size).LH2 <= 320 && input_size <= 1024;
+  // I / 4 and I / 2 whole, rows 16-byte aligned, the widest augmented row within dw_kernel's 320 input channels, and the
+  // last layer's weight gradient (H2' rows against I-wide gradient rows, the widest pair of the three) within the rows
+  // dw_kernel can stage: 496 is the largest such size.  (Without the last condition sizes up to 624 ran their forward and
+  // were refused by launch_dw in the backward.)
+  if (input_size < 16 || input_size % 8 != 0 || input_size > 1024) return false;
+  const WideDims d(input_size);
+  return d.LH2 <= 320 && dw_rows_fit(d.LH2, 4, d.I) && dw_rows_fit(d.LH1, 4, d.LH2) && dw_rows_fit(d.LE, 4, d.LH1);
 }
 size_t posenc_wide_acts_floats(int m, int input_size) { return wide_acts(WideDims(input_size), (size_t)m).total; }
 size_t posenc_wide_scratch_floats(int m, int input_size, int need_backward) {

@@ -223,14 +223,19 @@ size_t a3vt_posenc_param_count(int input_size);
 size_t a3vt_posenc_scratch_bytes(int m, int input_size);
 int a3vt_posenc_mask_fwd(const float *verts, const float *mask, int m, int input_size,
                          const float *pe_params, float *feats, int ld_feats, void *stream);
-/* grad_params has a3vt_posenc_param_count floats (overwritten); grad_verts [M][3] (overwritten). */
+/* grad_params has a3vt_posenc_param_count floats (overwritten); grad_verts [M][3] (overwritten).
+ * Row stride and alignment, both entries: any ld_feats >= input_size is accepted (a smaller one is refused), and feats /
+ * grad_feats need no more than a float's alignment.  Columns input_size .. ld_feats - 1 of feats are written as zeros;
+ * those of grad_feats are never used, whatever they hold.  The backward reads gradient rows in 16-byte pieces when
+ * ld_feats % 4 == 0 and grad_feats is 16-byte aligned (52, the models' stride), and element by element otherwise
+ * (ld_feats = 50 puts every odd row 8 bytes off): same result, the first is faster. */
 int a3vt_posenc_mask_bwd(const float *verts, const float *mask, int m, int input_size,
                          const float *pe_params, const float *grad_feats, int ld_feats,
                          float *grad_verts, float *grad_params, float *scratch, void *stream);
 
 /* The same encoder for wide inputs — input_size = 448 of the image models (model.py:180-190: 64 + 128 + 256 pooled channels)
  * — whose 133 k parameters do not fit the LDS-resident kernel above: every layer runs as one product on the fp32 matrix
- * pipe (csrc/posenc_wide.hip).  a3vt_posenc_wide_supported: input_size % 8 == 0, 16 <= input_size <= 630.  ld_feats must
+ * pipe (csrc/posenc_wide.hip).  a3vt_posenc_wide_supported: input_size % 8 == 0, 16 <= input_size <= 496.  ld_feats must
  * equal input_size.  `acts` (a3vt_posenc_wide_acts_bytes) receives the layer activations in the forward and is read by the
  * backward — the caller keeps it between the two calls; `scratch` (a3vt_posenc_wide_scratch_bytes) is free afterwards.
  * pe_params / grad_params: the packing of a3vt_posenc_mask_fwd.  Replaces the same reference lines.

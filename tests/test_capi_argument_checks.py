@@ -217,3 +217,70 @@ def test_sampling_entry_points_refuse_bad_arguments(L):
     assert L.a3vt_sample_points_fwd(*fwd(fi=FAKE, u=FAKE)) != 0 and "without u_in/v_in" in _err(L)
     assert L.a3vt_sample_points_fwd(*fwd(fi=FAKE, v=FAKE)) != 0 and "without u_in/v_in" in _err(L)
     assert L.a3vt_sample_points_fwd(*fwd(cdf=None)) != 0 and "cdf required" in _err(L)
+
+
+def test_posenc_entry_points_refuse_bad_arguments(L):
+    """The vertex-feature encoder's four entries (csrc/posenc.hip for input_size 50, csrc/posenc_wide.hip for the wide sizes):
+    NULL operands, an empty batch, a size the pair does not serve and a row stride the rows do not fit are refused before
+    anything is launched.  Rule of the narrow pair (include/a3vt.h): any ld_feats >= input_size, any float-aligned base — so a
+    stride of 50 and a base 8 bytes off a 16-byte boundary are NOT argument errors (the backward then loads element by
+    element; tests/test_gpu_posenc_edges.py runs both), and nothing here may pass such a call its fake pointers."""
+    fwd = lambda **kw: [kw.get("verts", FAKE), kw.get("mask", FAKE), kw.get("m", 100), kw.get("i", 50), kw.get("params", FAKE),   # noqa: E731
+                        kw.get("feats", FAKE), kw.get("ld", 52), None]
+    bwd = lambda **kw: [kw.get("verts", FAKE), kw.get("mask", FAKE), kw.get("m", 100), kw.get("i", 50), kw.get("params", FAKE),   # noqa: E731
+                        kw.get("gfeats", FAKE), kw.get("ld", 52), kw.get("gverts", FAKE), kw.get("gparams", FAKE),
+                        kw.get("scratch", FAKE), None]
+    wfwd = lambda **kw: [kw.get("verts", FAKE), kw.get("mask", FAKE), kw.get("m", 100), kw.get("i", 448), kw.get("params", FAKE),   # noqa: E731
+                         kw.get("feats", FAKE), kw.get("ld", kw.get("i", 448)), kw.get("acts", FAKE), kw.get("scratch", FAKE),
+                         kw.get("bf16", 0), None]
+    wbwd = lambda **kw: [kw.get("verts", FAKE), kw.get("mask", FAKE), kw.get("m", 100), kw.get("i", 448), kw.get("params", FAKE),   # noqa: E731
+                         kw.get("gfeats", FAKE), kw.get("ld", kw.get("i", 448)), kw.get("acts", FAKE), kw.get("gverts", FAKE),
+                         kw.get("gparams", FAKE), kw.get("scratch", FAKE), kw.get("bf16", 0), None]
+    for fn, args, operands in ((L.a3vt_posenc_mask_fwd, fwd, ("verts", "mask", "params", "feats")),
+                               (L.a3vt_posenc_mask_bwd, bwd, ("verts", "mask", "params", "gfeats", "gverts", "gparams", "scratch")),
+                               (L.a3vt_posenc_wide_fwd, wfwd, ("verts", "mask", "params", "feats", "acts", "scratch")),
+                               (L.a3vt_posenc_wide_bwd, wbwd, ("verts", "mask", "params", "gfeats", "acts", "gverts", "gparams",
+                                                               "scratch"))):
+        for name in operands:
+            assert fn(*args(**{name: None})) != 0, (fn.__name__, name)
+            assert "argument check failed" in _err(L)
+        for m in (0, -1):
+            assert fn(*args(m=m)) != 0, (fn.__name__, m)
+            assert "argument check failed" in _err(L)
+    # the narrow pair serves input_size 50 only, and a row must hold its 50 columns
+    for fn, args in ((L.a3vt_posenc_mask_fwd, fwd), (L.a3vt_posenc_mask_bwd, bwd)):
+        for i in (48, 52, 448):
+            assert fn(*args(i=i, ld=448)) != 0 and "input_size == 50 only" in _err(L), (fn.__name__, i)
+        for ld in (49, 48, 3, 0, -52):
+            assert fn(*args(ld=ld)) != 0 and "ld_feats >= input_size" in _err(L), (fn.__name__, ld)
+    # the wide pair: sizes it does not serve, and rows with pad columns (ld != input_size)
+    for fn, args in ((L.a3vt_posenc_wide_fwd, wfwd), (L.a3vt_posenc_wide_bwd, wbwd)):
+        for i in (8, 12, 50, 52, 504, 624, 632, 1032, 0, -16):
+            assert fn(*args(i=i)) != 0 and "posenc_wide_supported" in _err(L), (fn.__name__, i)
+        for i, ld in ((448, 452), (448, 444), (16, 20), (496, 512)):
+            assert fn(*args(i=i, ld=ld)) != 0 and "ld_feats == input_size" in _err(L), (fn.__name__, i, ld)
+
+
+def test_posenc_size_queries(L):
+    """a3vt_posenc_wide_supported: input_size % 8 == 0, 16 <= input_size <= 496 (the last layer's weight gradient must fit the
+    rows the weight-gradient kernel can stage; 504 .. 624 used to be admitted, ran their forward and failed in the backward);
+    the byte counts are 0 for every other size and for an empty batch."""
+    want = {8: 0, 16: 1, 24: 1, 52: 0, 448: 1, 496: 1, 504: 0, 624: 0, 632: 0, 1024: 0, 1032: 0}
+    for i, ok in want.items():
+        assert L.a3vt_posenc_wide_supported(i) == ok, i
+        for back in (0, 1):
+            assert (L.a3vt_posenc_wide_scratch_bytes(100, i, back) > 0) == bool(ok), (i, back)
+        assert (L.a3vt_posenc_wide_acts_bytes(100, i) > 0) == bool(ok), i
+        for m in (0, -1):
+            assert L.a3vt_posenc_wide_acts_bytes(m, i) == 0 and L.a3vt_posenc_wide_scratch_bytes(m, i, 1) == 0, (i, m)
+    assert [i for i in range(-8, 1100) if L.a3vt_posenc_wide_supported(i)] == list(range(16, 497, 8))
+    for i in (16, 448, 496):
+        for m in (1, 17, 300):
+            assert L.a3vt_posenc_wide_scratch_bytes(m, i, 1) > L.a3vt_posenc_wide_scratch_bytes(m, i, 0) > 0
+            # E' (68), H1' and H2' rows of every vertex fit the activation buffer
+            assert L.a3vt_posenc_wide_acts_bytes(m, i) >= 4 * m * (68 + (i // 4 + 5) + (i // 2 + 5))
+    # the narrow backward's scratch: one slab of packed gradients per workgroup, 4 x 16 vertices each, at most 512
+    n = L.a3vt_posenc_param_count(50)
+    for m, slabs in ((1, 1), (64, 1), (65, 2), (32768, 512), (32773, 512), (65557, 512)):
+        assert L.a3vt_posenc_scratch_bytes(m, 50) == slabs * n * 4, m
+    assert L.a3vt_posenc_scratch_bytes(0, 50) == n * 4 and L.a3vt_posenc_scratch_bytes(-5, 50) == n * 4      # never 0, never negative
