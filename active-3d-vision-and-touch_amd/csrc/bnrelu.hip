@@ -25,8 +25,6 @@ namespace {
 constexpr int kBnThreads = 256;
 constexpr int kBnMaxWgs = 1024;
 
-__device__ __forceinline__ float bn_relu(float r) { return (r > 0.f || r != r) ? r : 0.f; }   // NaN stays NaN (torch.relu)
-
 // piece `p` (8 consecutive elements) of a bf16 array of n_elem elements; elements past the end read as 0
 __device__ __forceinline__ void bn_load(const uint16_t *g, long long p, long long n_elem, float v[8]) {
   const long long e0 = p * 8;
@@ -281,7 +279,7 @@ __global__ __launch_bounds__(kBnThreads) void bnrelu_apply_kernel(BnFwd p) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[u][j] = bn_relu(fmaf(v[u][j], sc[j], sh[j]));
+      for (int j = 0; j < 8; ++j) v[u][j] = relu_nan(fmaf(v[u][j], sc[j], sh[j]));
       bn_store(p.y, q + u * stride, p.n_elem, v[u]);
     }
   }

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void conv5f_kernel(Conv5fArgs a) {
     const int oy = oy0 + r0 + rr;
     if (oy < a.Ho && ox < a.Wo) {
       f32x4 v = acc[rr] * sc + sh;
-      if (a.relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+      if (a.relu) v = f32x4{relu_nan(v[0]), relu_nan(v[1]), relu_nan(v[2]), relu_nan(v[3])};
       *reinterpret_cast<f32x4 *>(a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * COUT + c0) = v;
     }
   }

@@ -79,7 +79,7 @@ __device__ __forceinline__ float fold_h1(float bias, const float *w, const float
   float v = bias;
 #pragma unroll
   for (int i = 0; i < K; ++i) v = fmaf(w[i], g[i], v);
-  return fmaxf(v, 0.f);
+  return relu_nan(v);
 }
 // (dy W3)[c] of one row, the same chain in both backward kernels
 __device__ __forceinline__ float fold_t(const float *dy, float w0, float w1, float w2) {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void fold_fwd_kernel(FoldArgs p) {
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
-          const float h2 = fmaxf(acc[rb][cb][4 * q + t] + b2[t], 0.f);
+          const float h2 = relu_nan(acc[rb][cb][4 * q + t] + b2[t]);
 #pragma unroll
           for (int o = 0; o < 3; ++o) part[rb][o] = fmaf(h2, w3[o][t], part[rb][o]);
         }
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void fold_bwd_rows_kernel(FoldArgs p) {
         const f32x4 b2 = *reinterpret_cast<const f32x4 *>(p.b2 + n0);
         f32x4 h2;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) h2[t] = fmaxf(acc[0][cb][4 * q + t] + b2[t], 0.f);
+        for (int t = 0; t < 4; ++t) h2[t] = relu_nan(acc[0][cb][4 * q + t] + b2[t]);
         *reinterpret_cast<f32x4 *>(sB + (lane & 31) * kFLd + n0) = h2;
       }
     __syncthreads();

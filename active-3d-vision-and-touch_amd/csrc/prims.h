@@ -23,6 +23,10 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 __device__ __forceinline__ unsigned f32_bits(float v) { return __builtin_bit_cast(unsigned, v); }
 __device__ __forceinline__ float bits_f32(unsigned v) { return __builtin_bit_cast(float, v); }
 
+// ---- ReLU as torch.relu has it: a NaN stays a NaN (fmaxf returns the other operand, 0), -0 becomes +0, every other value keeps
+// its bits.  One unordered compare and a select.  (The GCN stack's epilogues keep their own NaN -> 0 form: DESIGN.md.)
+__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
+
 // ---- bf16: THE rounding rule of the library (round to nearest even, v_cvt_pk_bf16_f32) -------------------------------------
 __device__ __forceinline__ unsigned bf16_pack2(float a, float b) {  // two floats -> one packed pair, a in the low half
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2));

@@ -94,7 +94,7 @@ __device__ __forceinline__ void enc_tile(const EncLds &L, const float *__restric
       const float *w = L.w1 + i * kE, *e = L.e + row * kLdE;
 #pragma unroll 9
       for (int c = 0; c < kE; ++c) acc = fmaf(w[c], e[c], acc);
-      acc = fmaxf(acc, 0.f);
+      acc = relu_nan(acc);
     }
     L.h1[o] = acc;
   }
@@ -107,7 +107,7 @@ __device__ __forceinline__ void enc_tile(const EncLds &L, const float *__restric
       const float *w = L.w2 + k * kH1, *h = L.h1 + row * kLdH1;
 #pragma unroll 5
       for (int i = 0; i < kH1; ++i) acc = fmaf(w[i], h[i], acc);
-      acc = fmaxf(acc, 0.f);
+      acc = relu_nan(acc);
     }
     L.h2[o] = acc;
   }
@@ -172,14 +172,14 @@ __global__ __launch_bounds__(256) void qnet_fwd_kernel(QnetArgs a, int tiles_per
         } else if (col >= a.cut_len && col + 4 <= a.hidden && yvec) {
           f32x4 o;
 #pragma unroll
-          for (int t = 0; t < 4; ++t) o[t] = fmaxf(z[t], 0.f);
+          for (int t = 0; t < 4; ++t) o[t] = relu_nan(z[t]);
           st4(a.y + gr * a.ldy + col, o);
         } else {
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const int c = col + t;
             if (c < cpad) a.za[gr * a.ldza + c] = z[t];     // (pad columns of the aggregation's input rows are read: keep them finite)
-            if (c >= a.cut_len && c < a.hidden) a.y[gr * a.ldy + c] = fmaxf(z[t], 0.f);
+            if (c >= a.cut_len && c < a.hidden) a.y[gr * a.ldy + c] = relu_nan(z[t]);
           }
         }
       }

@@ -981,6 +981,9 @@ class FoldFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, bias_s, g, w1g, w2, b2, w3, b3):
+        if isinstance(g, torch.Tensor) and g.dim() == 3 and g.shape[2] == 2 and g.requires_grad:
+            # dg exists for k = 3 only; a None from backward would read as a zero gradient
+            raise RuntimeError("a3vt: fold: the k = 2 lattice has no gradient path")
         L = _lib.load()
         bias_s, g, w1g, w2, b2, w3, b3 = (_req(t, n) for t, n in ((bias_s, "bias_s"), (g, "g"), (w1g, "w1g"), (w2, "w2"), (b2, "b2"),
                                                                   (w3, "w3"), (b3, "b3")))

@@ -125,3 +125,24 @@ def test_repeatable_and_batch_invariant(cuda, shape):
         for b in (0, 2):
             alone = conv5f(xd[b:b + 1].contiguous(), wd, stride, geometry[3], scd, shd, 1)
             assert torch.equal(alone[0], y1[b]), f"sample {b} of a batch of 3 differs from the same sample alone"
+
+
+def test_relu_keeps_nan(cuda):
+    """The epilogue's ReLU keeps a NaN, as ``torch.relu`` does: a NaN in one sample's corner pixel gives the NaN pattern of the
+    unfused torch composition (conv2d, scale and shift, relu), and the other samples keep the bits of the clean run."""
+    shape, geometry = SHAPES[0], GEOMETRIES[1]
+    assert geometry == (5, 5, 3, 2)
+    x, w, scale, shift, _, _ = problem(shape, geometry)
+    bad = x.clone()
+    bad[1, 0, 0, 1] = float("nan")
+    wd, scd, shd = w.to(cuda), scale.to(cuda), shift.to(cuda)
+    clean = conv5f(x.to(cuda), wd, shape[2], geometry[3], scd, shd, 1)
+    y = conv5f(bad.to(cuda), wd, shape[2], geometry[3], scd, shd, 1)
+    ref = torch.nn.functional.conv2d(bad.permute(0, 3, 1, 2), w, stride=shape[2], padding=geometry[3])
+    ref = torch.relu(ref * scale[None, :, None, None] + shift[None, :, None, None]).permute(0, 2, 3, 1)
+    want = torch.isnan(ref)
+    assert want[1].any() and not want[1].all() and not want[0].any() and not want[2].any()
+    assert torch.isfinite(clean).all()
+    assert torch.equal(torch.isnan(y).cpu(), want)
+    assert torch.equal(y[0], clean[0]) and torch.equal(y[2], clean[2])
+    assert torch.equal(y[1][~want[1].to(cuda)], clean[1][~want[1].to(cuda)])

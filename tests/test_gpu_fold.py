@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from fold_ref import fold_restated, fp64_leaf
 from golden_util import load
 from helpers import assert_grad_close, make_args, rel_err
 
@@ -44,16 +45,11 @@ def _fused_decode(dec, code, points):
 
 def _fp64_decode(sd, code, points):
     """fp64 restatement (CPU): returns y (B, P, 3) and the leaves (code, parameters) it was computed from."""
-    code = code.detach().double().cpu().requires_grad_(True)
-    p = {k: v.detach().double().cpu().requires_grad_(True) for k, v in sd.items()}
+    code = fp64_leaf(code)
+    p = {k: fp64_leaf(v) for k, v in sd.items()}
     g = _lattice(points).double()[None].expand(code.size(0), -1, -1)
     for f in (1, 2):
-        w1, b1 = p[f"fold{f}.conv1.weight"][:, :, 0], p[f"fold{f}.conv1.bias"]
-        w2, b2 = p[f"fold{f}.conv2.weight"][:, :, 0], p[f"fold{f}.conv2.bias"]
-        w3, b3 = p[f"fold{f}.conv3.weight"][:, :, 0], p[f"fold{f}.conv3.bias"]
-        h1 = torch.relu((code @ w1[:, :512].T + b1)[:, None, :] + g @ w1[:, 512:].T)
-        h2 = torch.relu(h1 @ w2.T + b2)
-        g = h2 @ w3.T + b3
+        g = fold_restated(code, g, p, f"fold{f}.")[0]
     return g, code, p
 
 
