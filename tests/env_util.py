@@ -1,6 +1,11 @@
 """Helpers shared by the ActiveTouch tests and ``golden/make_golden_env.py``: the recipe of the fixture ``g18_active_touch.npz``
 (settings of its two cases, the seeded sensor records, how the three models are written to checkpoint directories) — everything
-that both the generator (which drives the REFERENCE environment) and the tests (which drive this package's) must build alike."""
+that both the generator (which drives the REFERENCE environment) and the tests (which drive this package's) must build alike.
+
+The policy fixtures g19 - g22 are built on the same recipe: ``objects``, ``batch_seed``, ``status_table``, ``records``, ``clouds``
+and ``batches`` are defined here once, with what the fixtures vary (seeds, the action count, the finger read, the idle rule) as
+arguments; ``nn_policy_util``, ``supervised_util`` and ``tally_util`` fill in their constants.  The last three functions are the
+set-up the GPU tests of g18 - g22 share."""
 import json
 import os
 from types import SimpleNamespace
@@ -44,44 +49,85 @@ def vision_args(case):
     return SimpleNamespace(finger=CASES[case]["finger"], **MODEL)
 
 
-def status_table(case):
-    """(E, num_actions, 4) int8 codes into ``STATUS``, seeded; re-drawn until the fingers the case reads (finger 1 alone with
-    ``finger``) show all three codes and no element has two actions without any contact: those leave the mesh as it is, so
-    their scores tie exactly, which the fixture's score-gap condition excludes."""
-    c = CASES[case]
-    g = np.random.default_rng(c["record_seed"])
+def objects(kind, b):
+    """The two object ids of batch ``b`` of the ``kind`` ("train" / "valid") loader of a per-batch fixture (g19 - g22)."""
+    return (f"{kind}{b}_0", f"{kind}{b}_1")
+
+
+def batch_seed(base, kind, b):
+    return base + (0 if kind == "train" else 50) + 7 * b
+
+
+def status_table(seed, num_actions, finger=False, idle_rule=True):
+    """(E, num_actions, 4) int8 codes into ``STATUS``, seeded; re-drawn until the fingers read (finger 1 alone with ``finger``)
+    show all three codes and, under ``idle_rule``, no element has two actions without any contact: those leave the mesh as it is,
+    so their scores tie exactly, which the fixtures' score-gap conditions exclude."""
+    g = np.random.default_rng(seed)
     while True:
-        t = g.integers(0, 3, (E, c["num_actions"], 4)).astype(np.int8)
-        seen = t[:, :, 1] if c["finger"] else t
-        idle = (seen.reshape(E, c["num_actions"], -1) == 0).all(axis=2).sum(axis=1)
-        if len(np.unique(seen)) == 3 and idle.max() <= 1:
+        t = g.integers(0, 3, (E, num_actions, 4)).astype(np.int8)
+        seen = t[:, :, 1] if finger else t
+        idle = (seen.reshape(E, num_actions, -1) == 0).all(axis=2).sum(axis=1)
+        if len(np.unique(seen)) == 3 and (not idle_rule or idle.max() <= 1):
             return t
 
 
-def records(case, table):
-    """The sensor records of a case, ``{(object id, action): record}`` in ``RecordedSampler``'s format: images uniform in
-    [0, 255) with fractional parts (so the finger branch's truncation through uint8 shows), frames from ``touch_util.frames``."""
-    c = CASES[case]
+def records(objs, num_actions, table, seed):
+    """The sensor records of one batch, ``{(object id, action): record}`` in ``RecordedSampler``'s format, record (e, a) from
+    ``seed + 100 e + a``: images uniform in [0, 255) with fractional parts (so the finger branch's truncation through uint8
+    shows), frames from ``touch_util.frames``."""
     out = {}
-    for e, obj in enumerate(OBJECTS):
-        for a in range(c["num_actions"]):
-            seed = c["record_seed"] + 100 * e + a
-            g = torch.Generator().manual_seed(seed)
-            rot, pos = tu.frames(4, seed)
+    for e, obj in enumerate(objs):
+        for a in range(num_actions):
+            s = seed + 100 * e + a
+            g = torch.Generator().manual_seed(s)
+            rot, pos = tu.frames(4, s)
             out[(obj, a)] = {"touch": torch.rand(4, 121, 121, 3, generator=g) * 255.0, "rot": rot, "pos": pos,
-                             "status": [STATUS[int(s)] for s in table[e, a]]}
+                             "status": [STATUS[int(code)] for code in table[e, a]]}
     return out
 
 
-def clouds(case):
+def clouds(seed):
     """(E, 900, 3) ground-truth clouds: points on seeded ellipsoids."""
-    g = torch.Generator().manual_seed(CASES[case]["cloud_seed"])
+    g = torch.Generator().manual_seed(seed)
     d = torch.randn(E, CLOUD, 3, generator=g)
     return d / d.norm(dim=-1, keepdim=True) * (0.05 + 0.11 * torch.rand(E, 1, 3, generator=g))
 
 
-def batch_of(gt):
-    return {"names": [f"/data/object_info/{o}" for o in OBJECTS], "gt_points": gt, "img": torch.zeros(E, 1)}
+def batch_of(gt, objs=OBJECTS):
+    return {"names": [f"/data/object_info/{o}" for o in objs], "gt_points": gt, "img": torch.zeros(E, 1)}
+
+
+# g18's own cases: one batch of ``OBJECTS``, table and records from the case's ``record_seed``, clouds from its ``cloud_seed``.
+
+def case_table(case):
+    c = CASES[case]
+    return status_table(c["record_seed"], c["num_actions"], finger=c["finger"])
+
+
+def case_records(case, table):
+    return records(OBJECTS, CASES[case]["num_actions"], table, CASES[case]["record_seed"])
+
+
+# The per-batch fixtures (g19 - g22): every batch of the "train" / "valid" loaders has its own two objects, status table, sensor
+# records and clouds, all drawn from ``batch_seed(base, kind, b)``; ``counts`` = {"train": batches, "valid": batches}.
+
+def status_tables(base, counts, num_actions, idle_rule=True):
+    return {f"{kind}{b}": status_table(batch_seed(base, kind, b), num_actions, idle_rule=idle_rule)
+            for kind, count in counts.items() for b in range(count)}
+
+
+def batch_records(base, counts, num_actions, tables):
+    """Every batch's sensor records in one mapping (``records`` from ``10 batch_seed``)."""
+    out = {}
+    for kind, count in counts.items():
+        for b in range(count):
+            out.update(records(objects(kind, b), num_actions, tables[f"{kind}{b}"], 10 * batch_seed(base, kind, b)))
+    return out
+
+
+def batches(base, kind, count):
+    """The ``kind`` loader as a list of batches: names, ``clouds`` from ``batch_seed + 3``, no image."""
+    return [batch_of(clouds(batch_seed(base, kind, b) + 3), objects(kind, b)) for b in range(count)]
 
 
 def write_checkpoint(directory, config, state):
@@ -127,3 +173,36 @@ def write_models(root, models):
     """Checkpoint directories of ``build_models``' result under ``root``: {"touch_location": ..., "vision_location": ...,
     "auto_location": ...}."""
     return {f"{kind}_location": write_checkpoint(os.path.join(root, kind), cfg, net.state_dict()) for kind, (cfg, net) in models.items()}
+
+
+# ---- what the GPU tests of g18 - g22 set up alike ---------------------------------------------------------------------------------
+
+def package_models(case, golden, directory, prefix=""):
+    """The checkpoint directories (``write_models``) under ``directory`` of this package's models built by ``build_models`` with
+    the BatchNorm tensors of the golden file, after asserting their checksums against its ``{prefix}sha:<kind>`` entries."""
+    from golden_util import state_sha256
+    from a3vt_amd.pterotactyl.reconstruction.autoencoder import model as auto_model
+    from a3vt_amd.pterotactyl.reconstruction.touch import model as touch_model
+    from a3vt_amd.pterotactyl.reconstruction.vision import model as vision_model
+    from a3vt_amd.pterotactyl.utility import utils
+    bn = {k[3:]: torch.from_numpy(golden[k]) for k in golden.files if k.startswith("bn:")}
+    models = build_models(case, touch_model, vision_model, auto_model, utils, "vision_charts", bn=bn)
+    for kind, (_, net) in models.items():
+        sd = tu.non_bn_state(net.state_dict()) if kind == "touch" else net.state_dict()
+        assert (state_sha256(sd) == golden[f"{prefix}sha:{kind}"]).all(), f"{prefix}the seeded {kind} model is not the fixture's"
+    return write_models(str(directory), models)
+
+
+def score_samples(golden, prefix=""):
+    """The injected surface draws of a golden file as ``ActiveTouch.score_samples`` takes them."""
+    return (torch.from_numpy(golden[prefix + "face_idx"].astype(np.int32)), torch.from_numpy(golden[prefix + "u"]),
+            torch.from_numpy(golden[prefix + "v"]))
+
+
+def kept_process_flags():
+    """Generator body of the ``restore_process_flags`` fixtures: ``ActiveTouch.seed`` sets torch's convolution flags
+    process-wide, as the reference does; other tests get them back."""
+    b = torch.backends.cudnn
+    kept = (b.deterministic, b.benchmark)
+    yield
+    b.deterministic, b.benchmark = kept

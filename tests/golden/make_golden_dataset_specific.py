@@ -27,18 +27,16 @@ Asserted here, the smallest values printed; the recipe is re-seeded until the re
 import importlib
 import os
 import sys
-import tempfile
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from make_golden import injected, ref, ref_chamfer_injected, save, state_checksum  # noqa: E402  (installs the import shim)
-from make_golden_env import StubSampler, install_simulator_stubs  # noqa: E402
+from make_golden import save  # noqa: E402  (installs the import shim)
+from make_golden_env import StubSampler, reference_setup  # noqa: E402
 import env_util as eu  # noqa: E402
 import tally_util as tl  # noqa: E402
-import touch_util as tu  # noqa: E402
 
 
 class PassThrough:
@@ -156,50 +154,26 @@ def run(name, mod, env_mod, seed, locations, root):
 
 
 def main():
-    install_simulator_stubs()
-    env_mod = importlib.import_module("pterotactyl.policies.environment")
-    env_mod.ActiveTouch.get_loaders = lambda self: None
-    engines = {"leba": importlib.import_module("pterotactyl.policies.dataset_specific.LEBA"),
-               "mfba": importlib.import_module("pterotactyl.policies.dataset_specific.MFBA")}
-    for mod in engines.values():
-        mod.tqdm = PassThrough
-    tm = importlib.import_module("pterotactyl.reconstruction.touch.model")
-    am = importlib.import_module("pterotactyl.reconstruction.autoencoder.model")
-    c = eu.CASES[tl.CASE]
-    models = eu.build_models(tl.CASE, tm, ref.model, am, ref.utils, os.path.join(ref.objects_dir, "vision_charts.obj"))
-    base = {"pytorch3d_restated": np.bool_(True)}
-    enc = models["touch"][1]
-    for k, v in enc.state_dict().items():
-        if tu.is_bn_key(k):
-            base["bn:" + k] = v.numpy().copy()
-    base["sha:touch"] = state_checksum(tu.non_bn_state(enc.state_dict()))
-    base["sha:vision"] = state_checksum(models["vision"][1].state_dict())
-    base["sha:auto"] = state_checksum(models["auto"][1].state_dict())
-    faces = models["vision"][1].adj_info["faces"]
-    samples = injected(eu.E, faces.shape[0], 700, c["sample_seed"])
-    base.update({"face_idx": torch.stack([s[0] for s in samples]).numpy().astype(np.int16),
-                 "u": torch.stack([s[1] for s in samples]).numpy(), "v": torch.stack([s[2] for s in samples]).numpy()})
-    ref.utils.chamfer_distance = lambda verts, f, g, num=1000, repeat=3: ref_chamfer_injected(verts, f, g, samples)
-    cwd = os.getcwd()
-    for attempt in range(200):
-        seed = tl.SEED + 100 * attempt
-        out = dict(base, seed=np.int64(seed))
-        StubSampler.records, StubSampler.log = tl.records(seed), []
-        with tempfile.TemporaryDirectory() as root:
-            os.chdir(root)
-            try:
-                locations = eu.write_models(root, models)
-                for name in ("mfba", "leba"):
-                    out.update(run(name, engines[name], env_mod, seed, locations, root))
-            except Unfit as e:
-                print(f"seed {seed}: {e}: re-seeding")
-                continue
-            finally:
-                os.chdir(cwd)
-        if seed != tl.SEED:
-            print(f"set tally_util.SEED = {seed}: the first seed the conditions hold for")
-        save(tl.FIXTURE, **out)
-        return
+    with reference_setup(tl.CASE) as setup:
+        engines = {"leba": importlib.import_module("pterotactyl.policies.dataset_specific.LEBA"),
+                   "mfba": importlib.import_module("pterotactyl.policies.dataset_specific.MFBA")}
+        for mod in engines.values():
+            mod.tqdm = PassThrough
+        for attempt in range(200):
+            seed = tl.SEED + 100 * attempt
+            out = dict(setup.out, seed=np.int64(seed))
+            StubSampler.records, StubSampler.log = tl.records(seed), []
+            with setup.workdir() as (root, locations):
+                try:
+                    for name in ("mfba", "leba"):
+                        out.update(run(name, engines[name], setup.env_mod, seed, locations, root))
+                except Unfit as e:
+                    print(f"seed {seed}: {e}: re-seeding")
+                    continue
+            if seed != tl.SEED:
+                print(f"set tally_util.SEED = {seed}: the first seed the conditions hold for")
+            save(tl.FIXTURE, **out)
+            return
     raise SystemExit("no seed found")
 
 

@@ -27,7 +27,6 @@ is the first from 0 at which all of this holds."""
 import importlib
 import os
 import sys
-import tempfile
 import types
 
 import numpy as np
@@ -35,12 +34,10 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from make_golden import injected, ref, ref_chamfer_injected, save, state_checksum  # noqa: E402  (installs the import shim)
-from make_golden_env import StubSampler, install_simulator_stubs  # noqa: E402
+from make_golden import save, state_checksum  # noqa: E402  (installs the import shim)
+from make_golden_env import reference_setup  # noqa: E402
 import ddqn_trainer_util as dt  # noqa: E402
-import env_util as eu  # noqa: E402
 import supervised_util as su  # noqa: E402
-import touch_util as tu  # noqa: E402
 
 
 def q_of(policy, obs):
@@ -135,43 +132,18 @@ def run(policy_seed, mods, locations):
 
 
 def main():
-    install_simulator_stubs()
-    env_mod = importlib.import_module("pterotactyl.policies.environment")
-    env_mod.ActiveTouch.get_loaders = lambda self: None
-    mods = (importlib.import_module("pterotactyl.policies.DDQN.train"), env_mod, importlib.import_module("pterotactyl.policies.replay"),
-            importlib.import_module("pterotactyl.policies.DDQN.ddqn"))
-    tm = importlib.import_module("pterotactyl.reconstruction.touch.model")
-    am = importlib.import_module("pterotactyl.reconstruction.autoencoder.model")
-    models = eu.build_models(dt.ENV_CASE, tm, ref.model, am, ref.utils, os.path.join(ref.objects_dir, "vision_charts.obj"))
-    out = {"pytorch3d_restated": np.bool_(True)}
-    enc = models["touch"][1]
-    for k, v in enc.state_dict().items():
-        if tu.is_bn_key(k):
-            out["bn:" + k] = v.numpy().copy()
-    out["sha:touch"] = state_checksum(tu.non_bn_state(enc.state_dict()))
-    out["sha:vision"] = state_checksum(models["vision"][1].state_dict())
-    out["sha:auto"] = state_checksum(models["auto"][1].state_dict())
     tables = su.status_tables()
-    for name, t in tables.items():
-        out["status:" + name] = t
-    StubSampler.records, StubSampler.log = su.records(tables), []
-    faces = models["vision"][1].adj_info["faces"]
-    samples = injected(eu.E, faces.shape[0], 700, eu.CASES[dt.ENV_CASE]["sample_seed"])
-    out.update({"face_idx": torch.stack([s[0] for s in samples]).numpy().astype(np.int16),
-                "u": torch.stack([s[1] for s in samples]).numpy(), "v": torch.stack([s[2] for s in samples]).numpy()})
-    ref.utils.chamfer_distance = lambda verts, f, g, num=1000, repeat=3: ref_chamfer_injected(verts, f, g, samples)
-    cwd = os.getcwd()
-    for policy_seed in range(20):
-        with tempfile.TemporaryDirectory() as root:
-            os.chdir(root)
-            try:
-                log, gap, ok = run(policy_seed, mods, eu.write_models(root, models))
-            finally:
-                os.chdir(cwd)
-        if ok and gap > dt.MIN_CHOICE_GAP:
-            break
+    with reference_setup(dt.ENV_CASE, tables=tables, records=su.records(tables)) as setup:
+        mods = (importlib.import_module("pterotactyl.policies.DDQN.train"), setup.env_mod,
+                importlib.import_module("pterotactyl.policies.replay"), importlib.import_module("pterotactyl.policies.DDQN.ddqn"))
+        for policy_seed in range(20):
+            with setup.workdir() as (_, locations):
+                log, gap, ok = run(policy_seed, mods, locations)
+            if ok and gap > dt.MIN_CHOICE_GAP:
+                break
     assert ok and gap > dt.MIN_CHOICE_GAP, "no policy seed below 20 gives a greedy and a random action after burn-in with every greedy " \
                                            "decision's two highest open Q values 1e-2 apart"
+    out = setup.out
     out.update(log)
     out["policy_seed"] = np.int64(policy_seed)
     for k in sorted(out):

@@ -24,6 +24,7 @@ Stored per case ``<c>``: (weights and images are NOT stored: the tests rebuild t
   bn:<key>                       every BatchNorm tensor of the touch encoder (shared by the cases)
 At every greedy decision the relative gap between the lowest and the second-lowest eligible score of each element must exceed
 1e-2 (one hundred times the tests' score tolerance); asserted, and the smallest gap printed."""
+import contextlib
 import importlib
 import os
 import random
@@ -80,6 +81,56 @@ def install_simulator_stubs():
     sys.modules["pterotactyl.simulator.physics"].grasping = g
 
 
+@contextlib.contextmanager
+def workdir(models):
+    """A temporary working directory with ``env_util.write_models``' checkpoints in it -> (root, locations)."""
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as root:
+        os.chdir(root)
+        try:
+            yield root, eu.write_models(root, models)
+        finally:
+            os.chdir(cwd)
+
+
+@contextlib.contextmanager
+def reference_setup(case, tables=None, records=None):
+    """The opening the generators of the policy fixtures (g19 - g22) share, in the order that fixes the key order of their
+    files: the simulator stubs and ``get_loaders`` a no-op; the reference's seeded models of ``env_util``'s ``case``; ``out`` with
+    the ``bn:`` and ``sha:`` entries, ``status:<batch>`` of ``tables`` and the injected draws ``face_idx|u|v``; ``records`` for
+    the ``StubSampler``; ``utils.chamfer_distance`` on those draws (put back on leaving).  Yields a namespace: ``env_mod``
+    (``policies.environment``), ``models``, ``out``, ``samples`` and ``workdir``, which enters a fresh temporary working
+    directory with the models' checkpoints -> (root, locations); a generator that re-seeds takes one per attempt, so that no
+    attempt finds the files of the one before."""
+    install_simulator_stubs()
+    env_mod = importlib.import_module("pterotactyl.policies.environment")
+    env_mod.ActiveTouch.get_loaders = lambda self: None
+    tm = importlib.import_module("pterotactyl.reconstruction.touch.model")
+    am = importlib.import_module("pterotactyl.reconstruction.autoencoder.model")
+    models = eu.build_models(case, tm, ref.model, am, ref.utils, os.path.join(ref.objects_dir, "vision_charts.obj"))
+    out = {"pytorch3d_restated": np.bool_(True)}
+    enc = models["touch"][1]
+    for k, v in enc.state_dict().items():
+        if tu.is_bn_key(k):
+            out["bn:" + k] = v.numpy().copy()
+    out["sha:touch"] = state_checksum(tu.non_bn_state(enc.state_dict()))
+    out["sha:vision"] = state_checksum(models["vision"][1].state_dict())
+    out["sha:auto"] = state_checksum(models["auto"][1].state_dict())
+    for name, t in (tables or {}).items():
+        out["status:" + name] = t
+    StubSampler.records, StubSampler.log = records, []
+    faces = models["vision"][1].adj_info["faces"]
+    samples = injected(eu.E, faces.shape[0], 700, eu.CASES[case]["sample_seed"])
+    out.update({"face_idx": torch.stack([s[0] for s in samples]).numpy().astype(np.int16),
+                "u": torch.stack([s[1] for s in samples]).numpy(), "v": torch.stack([s[2] for s in samples]).numpy()})
+    chamfer = ref.utils.chamfer_distance
+    ref.utils.chamfer_distance = lambda verts, f, g, num=1000, repeat=3: ref_chamfer_injected(verts, f, g, samples)
+    try:
+        yield types.SimpleNamespace(env_mod=env_mod, models=models, out=out, samples=samples, workdir=lambda: workdir(models))
+    finally:
+        ref.utils.chamfer_distance = chamfer
+
+
 def gap_of(scores, eligible):
     s = np.sort(np.asarray(scores, dtype=np.float64)[eligible])
     return np.inf if len(s) < 2 else (s[1] - s[0]) / s[0]
@@ -98,9 +149,9 @@ def run_case(case, env_mod, out):
     out[f"{case}:sha:vision"] = state_checksum(models["vision"][1].state_dict())
     if "auto" in models:
         out[f"{case}:sha:auto"] = state_checksum(models["auto"][1].state_dict())
-    table = eu.status_table(case)
-    StubSampler.records, StubSampler.log = eu.records(case, table), []
-    gt = eu.clouds(case)
+    table = eu.case_table(case)
+    StubSampler.records, StubSampler.log = eu.case_records(case, table), []
+    gt = eu.clouds(c["cloud_seed"])
     faces = models["vision"][1].adj_info["faces"]
     samples = injected(eu.E, faces.shape[0], 700, c["sample_seed"])
     out.update({f"{case}:status": table, f"{case}:gt": gt.numpy(),

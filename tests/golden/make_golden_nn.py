@@ -26,49 +26,25 @@ import importlib
 import os
 import random
 import sys
-import tempfile
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from make_golden import injected, ref, ref_chamfer_injected, save, state_checksum  # noqa: E402  (installs the import shim)
-from make_golden_env import StubSampler, install_simulator_stubs  # noqa: E402
+from make_golden import save  # noqa: E402  (installs the import shim)
+from make_golden_env import reference_setup  # noqa: E402
 import env_util as eu  # noqa: E402
 import nn_policy_util as nu  # noqa: E402
-import touch_util as tu  # noqa: E402
 
 
 def main():
-    install_simulator_stubs()
-    env_mod = importlib.import_module("pterotactyl.policies.environment")
-    env_mod.ActiveTouch.get_loaders = lambda self: None
-    nn_mod = importlib.import_module("pterotactyl.policies.NearestNeighbor.train")
-    tm = importlib.import_module("pterotactyl.reconstruction.touch.model")
-    am = importlib.import_module("pterotactyl.reconstruction.autoencoder.model")
     c = eu.CASES[nu.CASE]
-    models = eu.build_models(nu.CASE, tm, ref.model, am, ref.utils, os.path.join(ref.objects_dir, "vision_charts.obj"))
-    out = {"pytorch3d_restated": np.bool_(True)}
-    enc = models["touch"][1]
-    for k, v in enc.state_dict().items():
-        if tu.is_bn_key(k):
-            out["bn:" + k] = v.numpy().copy()
-    out["sha:touch"] = state_checksum(tu.non_bn_state(enc.state_dict()))
-    out["sha:vision"] = state_checksum(models["vision"][1].state_dict())
-    out["sha:auto"] = state_checksum(models["auto"][1].state_dict())
-    StubSampler.records, StubSampler.log = nu.records(), []
-    faces = models["vision"][1].adj_info["faces"]
-    samples = injected(eu.E, faces.shape[0], 700, c["sample_seed"])
-    out.update({"face_idx": torch.stack([s[0] for s in samples]).numpy().astype(np.int16),
-                "u": torch.stack([s[1] for s in samples]).numpy(), "v": torch.stack([s[2] for s in samples]).numpy()})
-    ref.utils.chamfer_distance = lambda verts, f, g, num=1000, repeat=3: ref_chamfer_injected(verts, f, g, samples)
     k = 5 * 5
-    cwd = os.getcwd()
-    with tempfile.TemporaryDirectory() as root:
-        os.chdir(root)
-        try:
-            locations = eu.write_models(root, models)
+    with reference_setup(nu.CASE, records=nu.records()) as setup:
+        env_mod, out = setup.env_mod, setup.out
+        nn_mod = importlib.import_module("pterotactyl.policies.NearestNeighbor.train")
+        with setup.workdir() as (root, locations):
             # ---- train ------------------------------------------------------------------------------------------------------
             engine = nn_mod.Engine(nu.engine_args(False, **locations))
             engine.env = env_mod.ActiveTouch(engine.args)
@@ -127,8 +103,6 @@ def main():
             assert len(bank_actions) == nu.BANK_ROWS
             out["bank:latents"], out["bank:actions"] = bank_latents, bank_actions
             log = validate(bank_latents, bank_actions, "bank.npy")
-        finally:
-            os.chdir(cwd)
     smallest, skipped = np.inf, 0
     for n, (b, i, obs, actions) in enumerate(log):
         key = f"valid:{b}:{i}:"

@@ -27,7 +27,6 @@ open values of each element are more than ``MIN_CHOICE_GAP`` = 1e-2 apart (relat
 import importlib
 import os
 import sys
-import tempfile
 import types
 
 import numpy as np
@@ -35,11 +34,10 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from make_golden import injected, ref, ref_chamfer_injected, save, state_checksum  # noqa: E402  (installs the import shim)
-from make_golden_env import StubSampler, install_simulator_stubs  # noqa: E402
+from make_golden import save, state_checksum  # noqa: E402  (installs the import shim)
+from make_golden_env import reference_setup  # noqa: E402
 import env_util as eu  # noqa: E402
 import supervised_util as su  # noqa: E402
-import touch_util as tu  # noqa: E402
 
 
 def run(policy_seed, sup_mod, env_mod, locations, root):
@@ -131,42 +129,17 @@ def run(policy_seed, sup_mod, env_mod, locations, root):
 
 
 def main():
-    install_simulator_stubs()
-    env_mod = importlib.import_module("pterotactyl.policies.environment")
-    env_mod.ActiveTouch.get_loaders = lambda self: None
-    sup_mod = importlib.import_module("pterotactyl.policies.supervised.train")
-    tm = importlib.import_module("pterotactyl.reconstruction.touch.model")
-    am = importlib.import_module("pterotactyl.reconstruction.autoencoder.model")
-    models = eu.build_models(su.ENV_CASE, tm, ref.model, am, ref.utils, os.path.join(ref.objects_dir, "vision_charts.obj"))
-    out = {"pytorch3d_restated": np.bool_(True)}
-    enc = models["touch"][1]
-    for k, v in enc.state_dict().items():
-        if tu.is_bn_key(k):
-            out["bn:" + k] = v.numpy().copy()
-    out["sha:touch"] = state_checksum(tu.non_bn_state(enc.state_dict()))
-    out["sha:vision"] = state_checksum(models["vision"][1].state_dict())
-    out["sha:auto"] = state_checksum(models["auto"][1].state_dict())
     tables = su.status_tables()
-    for name, t in tables.items():
-        out["status:" + name] = t
-    StubSampler.records, StubSampler.log = su.records(tables), []
-    faces = models["vision"][1].adj_info["faces"]
-    samples = injected(eu.E, faces.shape[0], 700, eu.CASES[su.ENV_CASE]["sample_seed"])
-    out.update({"face_idx": torch.stack([s[0] for s in samples]).numpy().astype(np.int16),
-                "u": torch.stack([s[1] for s in samples]).numpy(), "v": torch.stack([s[2] for s in samples]).numpy()})
-    ref.utils.chamfer_distance = lambda verts, f, g, num=1000, repeat=3: ref_chamfer_injected(verts, f, g, samples)
-    cwd = os.getcwd()
-    for policy_seed in range(20):
-        with tempfile.TemporaryDirectory() as root:
-            os.chdir(root)
-            try:
-                log, gap = run(policy_seed, sup_mod, env_mod, eu.write_models(root, models), root)
-            finally:
-                os.chdir(cwd)
-        print(f"policy seed {policy_seed}: smallest relative gap between the two lowest open values of a decision {gap:.3e}")
-        if gap > su.MIN_CHOICE_GAP:
-            break
+    with reference_setup(su.ENV_CASE, tables=tables, records=su.records(tables)) as setup:
+        sup_mod = importlib.import_module("pterotactyl.policies.supervised.train")
+        for policy_seed in range(20):
+            with setup.workdir() as (root, locations):
+                log, gap = run(policy_seed, sup_mod, setup.env_mod, locations, root)
+            print(f"policy seed {policy_seed}: smallest relative gap between the two lowest open values of a decision {gap:.3e}")
+            if gap > su.MIN_CHOICE_GAP:
+                break
     assert gap > su.MIN_CHOICE_GAP, "no policy seed below 20 keeps every decision's two lowest open values 1e-2 apart"
+    out = setup.out
     out.update(log)
     out["policy_seed"] = np.int64(policy_seed)
     for k in sorted(out):

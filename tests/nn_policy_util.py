@@ -4,10 +4,8 @@ restatement of the reference's per-element walk (``policies/NearestNeighbor/trai
 ``g19_nearest_neighbor.npz`` — what the generator (which drives the REFERENCE engine) and the tests (which drive this
 package's) must build alike."""
 import numpy as np
-import torch
 
 import env_util as eu
-import touch_util as tu
 
 FIXTURE = "g19_nearest_neighbor.npz"
 CASE = "b"                 # env_util's case: four fingers, latent, E = 2, 6 actions, budget 3, greedy_checks 3
@@ -86,50 +84,19 @@ def reference_walk(latents, actions, query, seen_actions, k):
 # env_util's case "b" (models, settings, surface draws); every batch has its own two objects, sensor records and clouds, so the
 # batches differ in what the policy observes.
 
-def objects(kind, b):
-    return (f"{kind}{b}_0", f"{kind}{b}_1")
-
-
-def batch_seed(kind, b):
-    return 1900 + (0 if kind == "train" else 50) + 7 * b
-
-
-def status_table(seed):
-    """``env_util.status_table``'s rule for the four-finger case, from ``seed``."""
-    n = eu.CASES[CASE]["num_actions"]
-    g = np.random.default_rng(seed)
-    while True:
-        t = g.integers(0, 3, (eu.E, n, 4)).astype(np.int8)
-        idle = (t.reshape(eu.E, n, -1) == 0).all(axis=2).sum(axis=1)
-        if len(np.unique(t)) == 3 and idle.max() <= 1:
-            return t
+BASE_SEED = 1900
+COUNTS = {"train": TRAIN_BATCHES, "valid": VALID_BATCHES}
 
 
 def records():
-    """Every batch's sensor records in one mapping ``{(object id, action): record}`` (``env_util.records``' construction)."""
-    out = {}
-    for kind, count in (("train", TRAIN_BATCHES), ("valid", VALID_BATCHES)):
-        for b in range(count):
-            table = status_table(batch_seed(kind, b))
-            for e, obj in enumerate(objects(kind, b)):
-                for a in range(eu.CASES[CASE]["num_actions"]):
-                    seed = 10 * batch_seed(kind, b) + 100 * e + a
-                    g = torch.Generator().manual_seed(seed)
-                    rot, pos = tu.frames(4, seed)
-                    out[(obj, a)] = {"touch": torch.rand(4, 121, 121, 3, generator=g) * 255.0, "rot": rot, "pos": pos,
-                                     "status": [eu.STATUS[int(s)] for s in table[e, a]]}
-    return out
+    """Every batch's sensor records in one mapping ``{(object id, action): record}``, tables under the idle rule."""
+    n = eu.CASES[CASE]["num_actions"]
+    return eu.batch_records(BASE_SEED, COUNTS, n, eu.status_tables(BASE_SEED, COUNTS, n))
 
 
 def batches(kind):
-    """The ``kind`` ("train" / "valid") loader as a list of batches: names, (E, 900, 3) clouds on seeded ellipsoids, no image."""
-    out = []
-    for b in range(TRAIN_BATCHES if kind == "train" else VALID_BATCHES):
-        g = torch.Generator().manual_seed(batch_seed(kind, b) + 3)
-        d = torch.randn(eu.E, eu.CLOUD, 3, generator=g)
-        gt = d / d.norm(dim=-1, keepdim=True) * (0.05 + 0.11 * torch.rand(eu.E, 1, 3, generator=g))
-        out.append({"names": [f"/data/object_info/{o}" for o in objects(kind, b)], "gt_points": gt, "img": torch.zeros(eu.E, 1)})
-    return out
+    """The ``kind`` ("train" / "valid") loader as a list of batches."""
+    return eu.batches(BASE_SEED, kind, COUNTS[kind])
 
 
 def engine_args(evaluate, **kw):

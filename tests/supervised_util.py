@@ -199,59 +199,26 @@ MIN_CHOICE_GAP = 1e-2                          # the generator's condition on th
 STORED_WEIGHTS = ("model.2.0.weight", "action_model.0.0.bias", "model.0.0.bias")
 
 
-def objects(kind, b):
-    return (f"{kind}{b}_0", f"{kind}{b}_1")
-
-
-def batch_seed(kind, b):
-    return 2000 + (0 if kind == "train" else 50) + 7 * b
-
-
-def status_table(seed):
-    """(E, NUM_ACTIONS, 4) int8 codes into ``env_util.STATUS``, all three codes present."""
-    import env_util as eu
-    g = np.random.default_rng(seed)
-    while True:
-        t = g.integers(0, 3, (eu.E, NUM_ACTIONS, 4)).astype(np.int8)
-        if len(np.unique(t)) == 3:
-            return t
+BASE_SEED = 2000
+COUNTS = {"train": TRAIN_BATCHES, "valid": VALID_BATCHES}
 
 
 def status_tables():
-    return {f"{kind}{b}": status_table(batch_seed(kind, b)) for kind, count in (("train", TRAIN_BATCHES), ("valid", VALID_BATCHES))
-            for b in range(count)}
+    """Per batch the (E, NUM_ACTIONS, 4) codes into ``env_util.STATUS``, all three codes present (no idle rule)."""
+    import env_util as eu
+    return eu.status_tables(BASE_SEED, COUNTS, NUM_ACTIONS, idle_rule=False)
 
 
 def records(tables):
-    """Every batch's sensor records ``{(object id, action): record}`` (``env_util.records``' construction)."""
-    import torch
+    """Every batch's sensor records ``{(object id, action): record}``."""
     import env_util as eu
-    import touch_util as tu
-    out = {}
-    for kind, count in (("train", TRAIN_BATCHES), ("valid", VALID_BATCHES)):
-        for b in range(count):
-            table = tables[f"{kind}{b}"]
-            for e, obj in enumerate(objects(kind, b)):
-                for a in range(NUM_ACTIONS):
-                    seed = 10 * batch_seed(kind, b) + 100 * e + a
-                    g = torch.Generator().manual_seed(seed)
-                    rot, pos = tu.frames(4, seed)
-                    out[(obj, a)] = {"touch": torch.rand(4, 121, 121, 3, generator=g) * 255.0, "rot": rot, "pos": pos,
-                                     "status": [eu.STATUS[int(s)] for s in table[e, a]]}
-    return out
+    return eu.batch_records(BASE_SEED, COUNTS, NUM_ACTIONS, tables)
 
 
 def batches(kind):
-    """The ``kind`` ("train" / "valid") loader as a list of batches: names, (E, 900, 3) clouds on seeded ellipsoids, no image."""
-    import torch
+    """The ``kind`` ("train" / "valid") loader as a list of batches."""
     import env_util as eu
-    out = []
-    for b in range(TRAIN_BATCHES if kind == "train" else VALID_BATCHES):
-        g = torch.Generator().manual_seed(batch_seed(kind, b) + 3)
-        d = torch.randn(eu.E, eu.CLOUD, 3, generator=g)
-        gt = d / d.norm(dim=-1, keepdim=True) * (0.05 + 0.11 * torch.rand(eu.E, 1, 3, generator=g))
-        out.append({"names": [f"/data/object_info/{o}" for o in objects(kind, b)], "gt_points": gt, "img": torch.zeros(eu.E, 1)})
-    return out
+    return eu.batches(BASE_SEED, kind, COUNTS[kind])
 
 
 def engine_args(**kw):

@@ -159,56 +159,20 @@ SEED = 12400       # the first of 2200, 2300, .. the generator's conditions hold
 MIN_GAP = 1e-2
 
 
-def objects(kind, b):
-    return (f"{kind}{b}_0", f"{kind}{b}_1")
-
-
-def batch_seed(seed, kind, b):
-    return seed + (0 if kind == "train" else 50) + 7 * b
-
-
-def status_table(seed):
-    """``env_util.status_table``'s rule for the four-finger case, from ``seed``."""
-    import env_util as eu
-    n = eu.CASES[CASE]["num_actions"]
-    g = np.random.default_rng(seed)
-    while True:
-        t = g.integers(0, 3, (eu.E, n, 4)).astype(np.int8)
-        idle = (t.reshape(eu.E, n, -1) == 0).all(axis=2).sum(axis=1)
-        if len(np.unique(t)) == 3 and idle.max() <= 1:
-            return t
+COUNTS = {"train": TRAIN_BATCHES, "valid": VALID_BATCHES}
 
 
 def records(seed):
-    """Every batch's sensor records in one mapping ``{(object id, action): record}`` (``env_util.records``' construction)."""
+    """Every batch's sensor records in one mapping ``{(object id, action): record}``, tables under the idle rule."""
     import env_util as eu
-    import torch
-    import touch_util
-    out = {}
-    for kind, count in (("train", TRAIN_BATCHES), ("valid", VALID_BATCHES)):
-        for b in range(count):
-            table = status_table(batch_seed(seed, kind, b))
-            for e, obj in enumerate(objects(kind, b)):
-                for a in range(eu.CASES[CASE]["num_actions"]):
-                    rs = 10 * batch_seed(seed, kind, b) + 100 * e + a
-                    g = torch.Generator().manual_seed(rs)
-                    rot, pos = touch_util.frames(4, rs)
-                    out[(obj, a)] = {"touch": torch.rand(4, 121, 121, 3, generator=g) * 255.0, "rot": rot, "pos": pos,
-                                     "status": [eu.STATUS[int(s)] for s in table[e, a]]}
-    return out
+    n = eu.CASES[CASE]["num_actions"]
+    return eu.batch_records(seed, COUNTS, n, eu.status_tables(seed, COUNTS, n))
 
 
 def batches(seed, kind):
-    """The ``kind`` ("train" / "valid") loader as a list of batches: names, (E, 900, 3) clouds on seeded ellipsoids, no image."""
+    """The ``kind`` ("train" / "valid") loader as a list of batches."""
     import env_util as eu
-    import torch
-    out = []
-    for b in range(TRAIN_BATCHES if kind == "train" else VALID_BATCHES):
-        g = torch.Generator().manual_seed(batch_seed(seed, kind, b) + 3)
-        d = torch.randn(eu.E, eu.CLOUD, 3, generator=g)
-        gt = d / d.norm(dim=-1, keepdim=True) * (0.05 + 0.11 * torch.rand(eu.E, 1, 3, generator=g))
-        out.append({"names": [f"/data/object_info/{o}" for o in objects(kind, b)], "gt_points": gt, "img": torch.zeros(eu.E, 1)})
-    return out
+    return eu.batches(seed, kind, COUNTS[kind])
 
 
 def engine_args(evaluate, **kw):

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import ddqn_trainer_util as dt
+import env_util as eu
 import supervised_util as su
 
 pytestmark = pytest.mark.gpu
@@ -34,29 +35,13 @@ def golden():
 
 @pytest.fixture(autouse=True)
 def restore_process_flags():
-    """``ActiveTouch.seed`` sets torch's convolution flags process-wide, as the reference does; other tests get them back."""
-    b = torch.backends.cudnn
-    kept = (b.deterministic, b.benchmark)
-    yield
-    b.deterministic, b.benchmark = kept
+    yield from eu.kept_process_flags()
 
 
 @pytest.fixture(scope="module")
 def locations(cuda, golden, tmp_path_factory):
     """The checkpoint directories of this package's models built by the fixture's recipe (checksums asserted)."""
-    import env_util as eu
-    import touch_util as tu
-    from golden_util import state_sha256
-    from a3vt_amd.pterotactyl.reconstruction.autoencoder import model as auto_model
-    from a3vt_amd.pterotactyl.reconstruction.touch import model as touch_model
-    from a3vt_amd.pterotactyl.reconstruction.vision import model as vision_model
-    from a3vt_amd.pterotactyl.utility import utils
-    bn = {k[3:]: torch.from_numpy(golden[k]) for k in golden.files if k.startswith("bn:")}
-    models = eu.build_models(dt.ENV_CASE, touch_model, vision_model, auto_model, utils, "vision_charts", bn=bn)
-    for kind, (_, net) in models.items():
-        sd = tu.non_bn_state(net.state_dict()) if kind == "touch" else net.state_dict()
-        assert (state_sha256(sd) == golden[f"sha:{kind}"]).all(), f"the seeded {kind} model is not the fixture's"
-    return eu.write_models(str(tmp_path_factory.mktemp("g21")), models)
+    return eu.package_models(dt.ENV_CASE, golden, tmp_path_factory.mktemp("g21"))
 
 
 @pytest.fixture(scope="module")
@@ -98,7 +83,7 @@ def replay(golden, locations, sensor_records, monkeypatch, tmp_path, **knobs):
     monkeypatch.chdir(tmp_path)                                   # results/ and experiments/checkpoint/ are made in the working directory
     engine = dtr.Engine(dt.engine_args(**knobs, **locations), sampler=recorded.RecordedSampler(sensor_records))
     setup(engine, environment.ActiveTouch(engine.args, sampler=engine.sampler), int(golden["policy_seed"]))
-    engine.env.score_samples = (torch.from_numpy(golden["face_idx"].astype(np.int32)), torch.from_numpy(golden["u"]), torch.from_numpy(golden["v"]))
+    engine.env.score_samples = eu.score_samples(golden)
     sd = {k: v.cpu() for k, v in engine.policy.state_dict().items()}
     assert (state_sha256(sd) == golden["sha:policy"]).all(), "the seeded policy is not the fixture's"
     assert engine.policy.model.fused_q_latent is bool(knobs["fused_q_latent"])

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import env_util as eu
 import nn_policy_util as nu
 
 pytestmark = pytest.mark.gpu
@@ -204,29 +205,13 @@ def golden():
 
 @pytest.fixture(autouse=True)
 def restore_process_flags():
-    """``ActiveTouch.seed`` sets torch's convolution flags process-wide, as the reference does; other tests get them back."""
-    b = torch.backends.cudnn
-    kept = (b.deterministic, b.benchmark)
-    yield
-    b.deterministic, b.benchmark = kept
+    yield from eu.kept_process_flags()
 
 
 @pytest.fixture(scope="module")
 def locations(cuda, golden, tmp_path_factory):
     """The checkpoint directories of this package's models built by the fixture's recipe (checksums asserted)."""
-    import env_util as eu
-    import touch_util as tu
-    from golden_util import state_sha256
-    from a3vt_amd.pterotactyl.reconstruction.autoencoder import model as auto_model
-    from a3vt_amd.pterotactyl.reconstruction.touch import model as touch_model
-    from a3vt_amd.pterotactyl.reconstruction.vision import model as vision_model
-    from a3vt_amd.pterotactyl.utility import utils
-    bn = {k[3:]: torch.from_numpy(golden[k]) for k in golden.files if k.startswith("bn:")}
-    models = eu.build_models(nu.CASE, touch_model, vision_model, auto_model, utils, "vision_charts", bn=bn)
-    for kind, (_, net) in models.items():
-        sd = tu.non_bn_state(net.state_dict()) if kind == "touch" else net.state_dict()
-        assert (state_sha256(sd) == golden[f"sha:{kind}"]).all(), f"the seeded {kind} model is not the fixture's"
-    return eu.write_models(str(tmp_path_factory.mktemp("g19")), models)
+    return eu.package_models(nu.CASE, golden, tmp_path_factory.mktemp("g19"))
 
 
 def make_engine(golden, locations, monkeypatch, tmp_path, evaluate, fused):
@@ -240,8 +225,7 @@ def make_engine(golden, locations, monkeypatch, tmp_path, evaluate, fused):
 
     def with_samples(self, *a, **k):
         inner(self, *a, **k)
-        self.score_samples = (torch.from_numpy(golden["face_idx"].astype(np.int32)), torch.from_numpy(golden["u"]),
-                              torch.from_numpy(golden["v"]))
+        self.score_samples = eu.score_samples(golden)
 
     monkeypatch.setattr(environment.ActiveTouch, "__init__", with_samples)
     return engine, nn

@@ -24,10 +24,10 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--calls", type=int, default=60, help="timed calls per round and path")
-ap.add_argument("--rounds", type=int, default=3)
-ap.add_argument("--warmup", type=int, default=10)
+ab.add_arguments(ap, calls=60, rounds=3, warmup=10, out=False, what="path")
 ap.add_argument("--launches", action="store_true", help="count kernel launches per update with rocprofv3 (child processes)")
 ap.add_argument("--only", choices=("new", "parent"), help="run --updates updates of one path and exit (what --launches profiles)")
 ap.add_argument("--updates", type=int, default=10)
@@ -127,18 +127,6 @@ def paths():
             "parent": (lambda: parent_update(old, old_t, old_opt), lambda: old.get_action(old_obs, 0.0))}
 
 
-def timed(fn, calls):
-    ms = []
-    for _ in range(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
-
-
 if a.only:
     np.random.seed(0)
     update = paths()[a.only][0]
@@ -150,17 +138,11 @@ if a.only:
 np.random.seed(0)
 fns = paths()
 for what, idx in (("update_parameters", 0), ("get_action", 1)):
+    # device events alone, no synchronise between the calls
+    res = ab.alternate({k: fns[k][idx] for k in fns}, a.calls, a.rounds, a.warmup, clocks=("device",))
     for k in fns:
-        for _ in range(a.warmup):
-            fns[k][idx]()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(a.rounds):
-        for k in fns:
-            ms[k] += timed(fns[k][idx], a.calls)
-    pct = {k: np.percentile(v, [10, 50, 90]) for k, v in ms.items()}
-    for k in fns:
-        print(f"{what:17s} {k:6s}: median {pct[k][1]:7.3f} ms  p10 {pct[k][0]:7.3f}  p90 {pct[k][2]:7.3f}   ({len(ms[k])} calls, "
+        s = res[k]["device"]
+        print(f"{what:17s} {k:6s}: median {s['median']:7.3f} ms  p10 {s['p10']:7.3f}  p90 {s['p90']:7.3f}   ({a.calls * a.rounds} calls, "
               f"B = {B}, N = {N}, 4 x 200)")
-    print(f"{what:17s} new / parent = {pct['new'][1] / pct['parent'][1]:.3f} (medians); new p90 {'<' if pct['new'][2] < pct['parent'][0] else '>='} "
-          f"parent p10")
+    print(f"{what:17s} new / parent = {res['new']['device']['median'] / res['parent']['device']['median']:.3f} (medians); "
+          f"new p90 {'<' if ab.wins(res, 'new', 'parent', 'device') else '>='} parent p10")

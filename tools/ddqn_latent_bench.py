@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The DDQN learner over auto-encoder latents (``Latent_Model``) — ``fused_q_latent`` on against off, the two forms ALTERNATING in
-one process (the protocol of ``tools/supervised_bench.py``), at two sizes: the reference's defaults (4 x 200) and the published
+one process (``tools/ab_protocol.py``, both clocks), at two sizes: the reference's defaults (4 x 200) and the published
 ``l_*`` checkpoints' (5 x 300); batch 16, 50 actions, latent 200, a host replay memory of 300 transitions, ``gamma`` 0.9,
 rewards / first_score.
 
@@ -24,25 +24,21 @@ import json
 import os
 import sys
 import tempfile
-import time
 from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--calls", type=int, default=100, help="timed calls per round and form")
-ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=20)
+ab.add_arguments(ap, calls=100, rounds=5, warmup=20)
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--env", type=int, default=3)
 ap.add_argument("--num_actions", type=int, default=50)
 ap.add_argument("--latent", type=int, default=200)
 ap.add_argument("--sizes", type=str, default="4x200,5x300", help="layers x hidden_dim of the Q network, comma-separated")
-ap.add_argument("--out", type=str, default=None)
-a = ap.parse_args()
-if a.out:
-    a.out = os.path.abspath(a.out)
+a = ab.parse(ap)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -51,49 +47,18 @@ from a3vt_amd import ops  # noqa: E402
 from a3vt_amd.pterotactyl.policies import replay  # noqa: E402
 from a3vt_amd.pterotactyl.policies.DDQN import ddqn  # noqa: E402
 
-if not torch.cuda.is_available():
-    raise SystemExit("ddqn_latent_bench: no GPU visible; a timing taken without one says nothing")
+ab.require_gpu("ddqn_latent_bench")
 dev = torch.device("cuda", 0)
 E, A, B = a.env, a.num_actions, a.batch
 
 
-def stats(v):
-    return {"median": float(np.median(v)), "p10": float(np.percentile(v, 10)), "p90": float(np.percentile(v, 90))}
-
-
-def alternate(forms, calls, rounds, warmup):
-    """{name: {"host": stats, "device": stats}} of callables that end with their result on the host."""
-    for fn in forms.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: {"host": [], "device": []} for name in forms}
-    for _ in range(rounds):
-        for name, fn in forms.items():
-            for _ in range(calls):
-                start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                start.record()
-                fn()
-                end.record()
-                t1 = time.perf_counter()
-                end.synchronize()
-                times[name]["host"].append((t1 - t0) * 1e3)
-                times[name]["device"].append(start.elapsed_time(end))
-    return {name: {clock: stats(v) for clock, v in t.items()} for name, t in times.items()}
+def alternate(forms):
+    """Both clocks; the forms end with their result on the host, so the host clock stops before the closing synchronise."""
+    return ab.alternate(forms, a.calls, a.rounds, a.warmup)
 
 
 def report(title, res, lines):
-    lines.append(f"# {title}")
-    for name in ("fused", "modules"):
-        for clock in ("host", "device"):
-            s = res[name][clock]
-            lines.append(f"#   {name:10s} {clock:6s}: median {s['median']:9.4f}  p10 {s['p10']:9.4f}  p90 {s['p90']:9.4f}")
-    wins = res["fused"]["host"]["p90"] < res["modules"]["host"]["p10"]
-    lines.append(f"#   host wall modules / fused = {res['modules']['host']['median'] / res['fused']['host']['median']:.2f} (medians); "
-                 f"fused p90 below modules p10: {wins}")
-    return wins
+    return ab.report(title, res, "fused", "modules", lines, clock="host")
 
 
 root = tempfile.mkdtemp(prefix="ddqn_latent_bench_")
@@ -167,18 +132,14 @@ for size in a.sizes.split(","):
     one["fused_launches_per_update"] = launches
     one["same_actions"] = same
     lines.append(f"# ---- Q network {layers} x {hidden} ----")
-    one["update"] = alternate({"fused": update(fused, fused_target), "modules": update(plain, plain_target)}, a.calls, a.rounds, a.warmup)
+    one["update"] = alternate({"fused": update(fused, fused_target), "modules": update(plain, plain_target)})
     wins = report(f"1. one update_parameters (first losses: fused {first_fused:.6g}, modules {first_plain:.6g}; fused launches per update, "
                   f"Adam included: {launches})", one["update"], lines)
-    one["get_action"] = alternate({"fused": choose(fused), "modules": choose(plain)}, a.calls, a.rounds, a.warmup)
+    one["get_action"] = alternate({"fused": choose(fused), "modules": choose(plain)})
     report(f"2. one greedy get_action at E = {E} (same actions: {same})", one["get_action"], lines)
     verdicts.append(wins)
     result["sizes"][size] = one
 result["fused_q_latent_default"] = bool(all(verdicts))
 lines.append(f"# -> FUSED_Q_LATENT_DEFAULT = {result['fused_q_latent_default']} (the fused update's p90 below the modules' p10 at every size: {verdicts})")
 lines.append(json.dumps(result))
-text = "\n".join(lines) + "\n"
-print(text, end="")
-if a.out:
-    with open(a.out, "w") as f:
-        f.write(text)
+ab.emit(lines, a.out)

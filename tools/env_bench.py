@@ -7,9 +7,10 @@ seeded weights with damped output layers (centimetre deformations, as trained mo
 geometry); the surface draws are fixed (``score_samples``), so both paths score the same points and ``same_actions`` /
 ``score_rel_diff`` compare their decisions.
 
-Protocol: the two paths alternate in one process on the same environment (``args.batched_greedy`` switched per call); every call
-is ``reset`` (not timed) then ``best_step`` (timed: device events around the call, which ends in the step's device-to-host
-copies, and the host clock around the same window); ``--warmup`` calls of each path first, then ``--calls`` each.  Reported per
+Protocol (``tools/ab_protocol.py``): the two paths alternate call by call in one process on the same environment
+(``args.batched_greedy`` switched per call); every call is ``reset`` (not timed) then ``best_step`` (timed: device events around
+the call, which ends in the step's device-to-host copies, and the host clock around the same window, stopped after a device
+synchronise); ``--warmup`` calls of each path first, then ``--calls`` each.  Reported per
 path: median, p10, p90 of the device-event times, the host-clock median, and the allocator's peak during a step.  The verdict
 line applies the project's rule for a knob's default: on only if the batched p90 lies below the loop's p10 at both topologies.
 
@@ -19,7 +20,6 @@ import json
 import os
 import sys
 import tempfile
-import time
 from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,6 +27,8 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
 
 
 def write_checkpoint(directory, config, net):
@@ -50,10 +52,6 @@ def synthetic_records(objects, actions, seed):
                            "pos": 0.12 * d / d.norm(dim=-1, keepdim=True),
                            "status": [status[int(i)] for i in torch.randint(0, 4, (4,), generator=g)]}
     return out
-
-
-def percentiles(ms):
-    return {"median": float(np.percentile(ms, 50)), "p10": float(np.percentile(ms, 10)), "p90": float(np.percentile(ms, 90))}
 
 
 def measure(finger, a, root):
@@ -89,43 +87,33 @@ def measure(finger, a, root):
                          torch.rand(3, a.env, a.points, generator=g), torch.rand(3, a.env, a.points, generator=g))
     batch = {"names": ["/data/object_info/" + o for o in objects], "gt_points": gt_cloud(a.env, a.points, 3), "img": torch.zeros(a.env, 1)}
 
-    def call(batched):
-        args.batched_greedy = batched
+    peaks, chosen = {"batched": [], "loop": []}, {}
+
+    def prepare(name):                                                # not timed
+        args.batched_greedy = name == "batched"
         env.reset(batch)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        e0.record()
-        actions, obs, _, _ = env.best_step()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1), 1e3 * (time.perf_counter() - t0), torch.cuda.max_memory_allocated(), actions, obs
 
-    for _ in range(a.warmup):
-        for batched in (True, False):
-            call(batched)
-    dev = {True: [], False: []}
-    host = {True: [], False: []}
-    peak = {True: 0, False: 0}
-    chosen = {}
-    for _ in range(a.calls):
-        for batched in (True, False):
-            d, h, p, actions, obs = call(batched)
-            dev[batched].append(d)
-            host[batched].append(h)
-            peak[batched] = max(peak[batched], p)
-            chosen[batched] = (actions, obs["score"])
+    def step(name):
+        def run():
+            actions, obs, _, _ = env.best_step()
+            chosen[name] = (actions, obs["score"])
+            peaks[name].append(torch.cuda.max_memory_allocated())     # (a host counter: the step's allocations are all made by now)
+        return run
+
+    # one call per round, so the paths alternate call by call; both clocks, the host's stopped after the closing synchronise
+    res = ab.alternate({name: step(name) for name in peaks}, 1, a.calls, a.warmup, host_stops="after", before=prepare)
     rec = {"topology": tag, "n_vert": 1824 + 125 * (1 if finger else 4),
            "env": a.env, "candidates": a.candidates, "points": a.points, "layers": a.layers, "candidate_chunk": a.chunk,
            "calls": a.calls, "warmup": a.warmup,
-           "same_actions": bool(np.array_equal(chosen[True][0], chosen[False][0])),
-           "score_rel_diff": float(((chosen[True][1] - chosen[False][1]).abs() / chosen[False][1].abs()).max())}
-    for batched, name in ((True, "batched"), (False, "loop")):
-        rec[name] = dict(percentiles(dev[batched]), host_median=float(np.percentile(host[batched], 50)),
-                         peak_allocated_MiB=peak[batched] / 2 ** 20)
+           "same_actions": bool(np.array_equal(chosen["batched"][0], chosen["loop"][0])),
+           "score_rel_diff": float(((chosen["batched"][1] - chosen["loop"][1]).abs() / chosen["loop"][1].abs()).max())}
+    for name in peaks:
+        rec[name] = dict(res[name]["device"], host_median=res[name]["host"]["median"],
+                         peak_allocated_MiB=max(peaks[name][-a.calls:]) / 2 ** 20)
     rec["speedup_median"] = rec["loop"]["median"] / rec["batched"]["median"]
-    rec["batched_p90_below_loop_p10"] = rec["batched"]["p90"] < rec["loop"]["p10"]
+    rec["batched_p90_below_loop_p10"] = ab.wins(res, "batched", "loop", "device")
     return rec
 
 
@@ -135,12 +123,10 @@ def main():
     p.add_argument("--candidates", type=int, default=50)
     p.add_argument("--points", type=int, default=30000)
     p.add_argument("--layers", type=int, default=20)
-    p.add_argument("--calls", type=int, default=30)
-    p.add_argument("--warmup", type=int, default=3)
+    ab.add_arguments(p, calls=30, rounds=None, warmup=3, out=False, what="path")
     p.add_argument("--chunk", type=int, default=None, help="args.candidate_chunk of the batched path")
     a = p.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("env_bench: no GPU visible; nothing is measured without one")
+    ab.require_gpu("env_bench")
     print(f"# one ActiveTouch.best_step, batched vs the candidate loop; device-event ms per call; {torch.cuda.get_device_name(0)}")
     verdict = True
     with tempfile.TemporaryDirectory() as root:

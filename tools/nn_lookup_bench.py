@@ -18,31 +18,28 @@ import argparse
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--calls", type=int, default=100, help="timed calls per round and form")
-ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=20)
+ab.add_arguments(ap, calls=100, rounds=5, warmup=20)
 ap.add_argument("--bank_rows", type=int, default=15400)
 ap.add_argument("--dim", type=int, default=200)
 ap.add_argument("--env", type=int, default=3)
 ap.add_argument("--num_actions", type=int, default=50)
 ap.add_argument("--num_grasps", type=int, default=5)
 ap.add_argument("--taken", type=int, default=4, help="actions already performed per element (the mask of step 4)")
-ap.add_argument("--out", type=str, default=None)
-a = ap.parse_args()
+a = ab.parse(ap)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from a3vt_amd.pterotactyl.policies.NearestNeighbor import train as nn  # noqa: E402
 
-if not torch.cuda.is_available():
-    raise SystemExit("nn_lookup_bench: no GPU visible; a timing taken without one says nothing")
+ab.require_gpu("nn_lookup_bench")
 dev = torch.device("cuda", 0)
 k = a.num_grasps * 5
 g = np.random.default_rng(0)
@@ -72,26 +69,8 @@ def loop():
 forms = {"fused": fused, "loop": loop}
 chosen = {name: fn() for name, fn in forms.items()}
 same = chosen["fused"] == chosen["loop"]
-for fn in forms.values():
-    for _ in range(a.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {name: {"host": [], "device": []} for name in forms}
-for _ in range(a.rounds):
-    for name, fn in forms.items():
-        for _ in range(a.calls):
-            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            start.record()
-            fn()
-            end.record()
-            t1 = time.perf_counter()                       # (fn() ended with host integers: everything it launched has finished)
-            end.synchronize()
-            times[name]["host"].append((t1 - t0) * 1e3)
-            times[name]["device"].append(start.elapsed_time(end))
-
-stats = lambda v: {"median": float(np.median(v)), "p10": float(np.percentile(v, 10)), "p90": float(np.percentile(v, 90))}   # noqa: E731
+# both clocks; fn() ends with host integers, everything it launched has finished: the host clock stops before the synchronise
+res = ab.alternate(forms, a.calls, a.rounds, a.warmup)
 result = {"bank_rows": a.bank_rows, "dim": a.dim, "env": a.env, "k": k, "num_actions": a.num_actions, "taken": a.taken,
           "calls": a.calls * a.rounds, "warmup": a.warmup, "same_actions": same, "actions": chosen["fused"],
           "device": torch.cuda.get_device_name(0)}
@@ -99,19 +78,15 @@ lines = [f"# one nearest-neighbour lookup, library call vs the reference's loop 
          f"# bank {a.bank_rows} x {a.dim}, E = {a.env}, k = {k}, {a.taken} of {a.num_actions} actions taken per element; "
          f"{a.calls * a.rounds} calls per form in {a.rounds} alternating rounds after {a.warmup} warm-up calls"]
 for name in forms:
-    result[name] = {clock: stats(v) for clock, v in times[name].items()}
+    result[name] = res[name]
     for clock in ("host", "device"):
         s = result[name][clock]
         lines.append(f"# {name:5s} {clock:6s}: median {s['median']:8.4f}  p10 {s['p10']:8.4f}  p90 {s['p90']:8.4f}")
 result["speedup_host_median"] = result["loop"]["host"]["median"] / result["fused"]["host"]["median"]
-result["fused_p90_below_loop_p10"] = result["fused"]["host"]["p90"] < result["loop"]["host"]["p10"]
+result["fused_p90_below_loop_p10"] = ab.wins(res, "fused", "loop", "host")
 lines.append(json.dumps(result))
 lines.append(f"# same actions: {same}; host wall loop / fused = {result['speedup_host_median']:.2f} (medians); fused p90 below loop p10: "
              f"{result['fused_p90_below_loop_p10']} -> FUSED_LOOKUP_DEFAULT = {result['fused_p90_below_loop_p10'] and same}")
-text = "\n".join(lines) + "\n"
-print(text, end="")
-if a.out:
-    with open(a.out, "w") as f:
-        f.write(text)
+ab.emit(lines, a.out)
 if not same:
     raise SystemExit(f"nn_lookup_bench: the two forms chose different actions: {chosen}")

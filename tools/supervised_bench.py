@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The supervised latent policy at the reference's ``t_p`` defaults — E = 3 elements, 50 actions, latent size 200, a value network
-of 4 x 200 — three A/B measurements, the two forms of each ALTERNATING in one process (the protocol of ``tools/ddqn_bench.py``):
+of 4 x 200 — three A/B measurements, the two forms of each ALTERNATING in one process (``tools/ab_protocol.py``, both clocks):
 
 1. evaluation   one ``Latent_Model`` evaluation with the action choice at step 4 (four actions performed per element), from host
                 observations to host integers:
@@ -28,16 +28,15 @@ import json
 import os
 import sys
 import tempfile
-import time
 from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--calls", type=int, default=100, help="timed calls per round and form (measurements 1 and 2)")
-ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=20)
+ab.add_arguments(ap, calls=100, rounds=5, warmup=20, what="form (measurements 1 and 2)")
 ap.add_argument("--iterations", type=int, default=8, help="timed train iterations per round and form (measurement 3)")
 ap.add_argument("--iteration_warmup", type=int, default=3)
 ap.add_argument("--env", type=int, default=3)
@@ -49,10 +48,7 @@ ap.add_argument("--taken", type=int, default=4, help="actions already performed 
 ap.add_argument("--points", type=int, default=30000, help="surface points and cloud size of measurement 3")
 ap.add_argument("--gcn_layers", type=int, default=20)
 ap.add_argument("--skip_iteration", action="store_true", help="measurements 1 and 2 only")
-ap.add_argument("--out", type=str, default=None)
-a = ap.parse_args()
-if a.out:
-    a.out = os.path.abspath(a.out)
+a = ab.parse(ap)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -61,53 +57,12 @@ from a3vt_amd import optim as a3vt_optim  # noqa: E402
 from a3vt_amd.pterotactyl.policies.supervised import model as sm  # noqa: E402
 from a3vt_amd.pterotactyl.policies.supervised import train as st  # noqa: E402
 
-if not torch.cuda.is_available():
-    raise SystemExit("supervised_bench: no GPU visible; a timing taken without one says nothing")
+ab.require_gpu("supervised_bench")
 dev = torch.device("cuda", 0)
 E, A = a.env, a.num_actions
-
-
-def stats(v):
-    return {"median": float(np.median(v)), "p10": float(np.percentile(v, 10)), "p90": float(np.percentile(v, 90))}
-
-
-def alternate(forms, calls, rounds, warmup, before=None):
-    """{name: {"host": stats, "device": stats}} of callables that end with their result on the host."""
-    for fn in forms.values():
-        for _ in range(warmup):
-            if before:
-                before()
-            fn()
-    torch.cuda.synchronize()
-    times = {name: {"host": [], "device": []} for name in forms}
-    for _ in range(rounds):
-        for name, fn in forms.items():
-            for _ in range(calls):
-                if before:
-                    before()
-                start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                start.record()
-                fn()
-                end.record()
-                t1 = time.perf_counter()
-                end.synchronize()
-                times[name]["host"].append((t1 - t0) * 1e3)
-                times[name]["device"].append(start.elapsed_time(end))
-    return {name: {clock: stats(v) for clock, v in t.items()} for name, t in times.items()}
-
-
-def report(title, res, new, old, lines):
-    lines.append(f"# {title}")
-    for name in (new, old):
-        for clock in ("host", "device"):
-            s = res[name][clock]
-            lines.append(f"#   {name:10s} {clock:6s}: median {s['median']:9.4f}  p10 {s['p10']:9.4f}  p90 {s['p90']:9.4f}")
-    wins = res[new]["host"]["p90"] < res[old]["host"]["p10"]
-    lines.append(f"#   host wall {old} / {new} = {res[old]['host']['median'] / res[new]['host']['median']:.2f} (medians); "
-                 f"{new} p90 below {old} p10: {wins}")
-    return wins
+# ab.alternate at its defaults: both clocks; every form ends with its result on the host, so the host clock stops before the
+# closing synchronise.  The verdicts read the host clock (ab.report's default).
+alternate, report = ab.alternate, ab.report
 
 
 root = tempfile.mkdtemp(prefix="supervised_bench_")
@@ -266,10 +221,6 @@ if not a.skip_iteration:
     lines.append(f"#   -> BATCHED_TARGETS_DEFAULT = {result['batched_targets_default']}")
 
 lines.append(json.dumps(result))
-text = "\n".join(lines) + "\n"
-print(text, end="")
-if a.out:
-    with open(a.out, "w") as f:
-        f.write(text)
+ab.emit(lines, a.out)
 if not result["same_actions"]:
     raise SystemExit(f"supervised_bench: the two forms chose different actions: {chosen}")

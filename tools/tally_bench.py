@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """One swept batch of the dataset-specific policies LEBA and MFBA after the candidates have been scored — ``fused_tally`` on against
-off, the two forms ALTERNATING in one process (the protocol of ``tools/ddqn_latent_bench.py``), at two sizes: the reference's
+off, the two forms ALTERNATING in one process (``tools/ab_protocol.py``, host wall only), at two sizes: the reference's
 defaults (K = 50 candidates, E = 3 elements, A = 50 actions) and a large batch (K = 50, E = 64, A = 50).
 
 The environment is synthetic: ``score_candidates`` answers with a (K, E) table that one small device op has just written (as the
@@ -27,21 +27,17 @@ import argparse
 import json
 import os
 import sys
-import time
 from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--calls", type=int, default=100, help="timed calls per round and form")
-ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=20)
+ab.add_arguments(ap, calls=100, rounds=5, warmup=20)
 ap.add_argument("--sizes", type=str, default="50x3x50,50x64x50", help="K x E x A, comma-separated (K = A: a full search)")
-ap.add_argument("--out", type=str, default=None)
-a = ap.parse_args()
-if a.out:
-    a.out = os.path.abspath(a.out)
+a = ab.parse(ap)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -50,31 +46,13 @@ from a3vt_amd import ops  # noqa: E402
 from a3vt_amd.pterotactyl.policies import environment  # noqa: E402
 from a3vt_amd.pterotactyl.policies.dataset_specific import LEBA, MFBA  # noqa: E402
 
-if not torch.cuda.is_available():
-    raise SystemExit("tally_bench: no GPU visible; a timing taken without one says nothing")
+ab.require_gpu("tally_bench")
 dev = torch.device("cuda", 0)
 
 
-def stats(v):
-    return {"median": float(np.median(v)), "p10": float(np.percentile(v, 10)), "p90": float(np.percentile(v, 90))}
-
-
-def alternate(forms, calls, rounds, warmup):
-    """{name: stats of the host wall in ms} of callables, each timed call ending with a device synchronise."""
-    for fn in forms.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in forms}
-    for _ in range(rounds):
-        for name, fn in forms.items():
-            for _ in range(calls):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                fn()
-                torch.cuda.synchronize()
-                times[name].append((time.perf_counter() - t0) * 1e3)
-    return {name: stats(v) for name, v in times.items()}
+def alternate(forms):
+    """The host wall alone, stopped after the closing synchronise: the forms do not end on the host."""
+    return ab.alternate(forms, a.calls, a.rounds, a.warmup, clocks=("host",), host_stops="after")
 
 
 class SyntheticEnv:
@@ -106,15 +84,13 @@ def engine_of(module, K, E, A, fused):
     return engine
 
 
+def host_only(res):
+    """The result as the JSON line has always held it: {form: stats of the host wall}."""
+    return {form: r["host"] for form, r in res.items()}
+
+
 def report(title, res, lines):
-    lines.append(f"# {title}")
-    for name in ("fused", "loop"):
-        s = res[name]
-        lines.append(f"#   {name:6s} host: median {s['median']:9.4f}  p10 {s['p10']:9.4f}  p90 {s['p90']:9.4f}")
-    wins = res["fused"]["p90"] < res["loop"]["p10"]
-    lines.append(f"#   host wall loop / fused = {res['loop']['median'] / res['fused']['median']:.2f} (medians); "
-                 f"fused p90 below loop p10: {wins}")
-    return wins
+    return ab.report(title, res, "fused", "loop", lines, clock="host", width=6)
 
 
 lines = ["# profiles/candidate_tally_ab.txt: `python tools/tally_bench.py --out profiles/candidate_tally_ab.txt`, one MI355X (the device "
@@ -134,8 +110,8 @@ for size in a.sizes.split(","):
         for attr in module.Engine.state_names:                   # the two forms must agree bit for bit before they are timed
             if not np.array_equal(getattr(on, attr), getattr(off, attr)):
                 raise SystemExit(f"tally_bench: {name} {attr} differs between the forms at {size}")
-        res = alternate({"fused": on.tally_fused, "loop": off.tally_loop}, a.calls, a.rounds, a.warmup)
-        entry[name] = res
+        res = alternate({"fused": on.tally_fused, "loop": off.tally_loop})
+        entry[name] = host_only(res)
         verdict[name] &= report(f"{name} swept batch, K = {K}, E = {E}, A = {A}", res, lines)
     # the tally alone, from a table on the device
     env = SyntheticEnv(SimpleNamespace(num_actions=A, env_batch_size=E))
@@ -159,16 +135,11 @@ for size in a.sizes.split(","):
                     sums[action] += score
                 checks[action] += 1.0
 
-    res = alternate({"fused": launch, "loop": copy_and_loop}, a.calls, a.rounds, a.warmup)
-    entry["tally_alone"] = res
+    res = alternate({"fused": launch, "loop": copy_and_loop})
+    entry["tally_alone"] = host_only(res)
     report(f"the tally alone (fused: ops.candidate_tally; loop: the table's copy and LEBA's loop), K = {K}, E = {E}, A = {A}", res, lines)
 result["fused_tally_default"] = verdict
 lines.append(json.dumps(result))
 lines.append("# fused p90 below loop p10 at every size -> " +
              ", ".join(f"{name}.FUSED_TALLY_DEFAULT = {wins}" for name, wins in verdict.items()))
-text = "\n".join(lines) + "\n"
-print(text, end="")
-if a.out:
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
+ab.emit(lines, a.out)

@@ -17,14 +17,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--calls", type=int, default=40, help="timed calls per round and path")
-ap.add_argument("--rounds", type=int, default=3)
-ap.add_argument("--warmup", type=int, default=10)
+ab.add_arguments(ap, calls=40, rounds=3, warmup=10, out=False, what="path")
 ap.add_argument("--batches", type=int, nargs="+", default=[12, 600])
 a = ap.parse_args()
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from a3vt_amd import synthetic  # noqa: E402
@@ -45,18 +44,6 @@ def stem_macs(net):
     return total
 
 
-def timed(fn, calls):
-    ms = []
-    for _ in range(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
-
-
 torch.manual_seed(0)
 nets = {"fused": model.Encoder(fused_stem=True).to(dev).eval(), "torch": model.Encoder(fused_stem=False).to(dev).eval()}
 nets["torch"].load_state_dict(nets["fused"].state_dict())
@@ -74,23 +61,18 @@ for B in a.batches:
         print(f"B = {B}: max |fused - torch| of the forward = {diff:.3e}")
         for what in ("forward", "stem"):
             fns = {k: ((lambda n=n: n(x, ref, verts)) if what == "forward" else (lambda n=n: n.stem(x))) for k, n in nets.items()}
+            # device events alone, no synchronise between the calls
+            res = ab.alternate(fns, a.calls, a.rounds, a.warmup, clocks=("device",))
             for k in fns:
-                for _ in range(a.warmup):
-                    fns[k]()
-            torch.cuda.synchronize()
-            ms = {k: [] for k in fns}
-            for _ in range(a.rounds):
-                for k in fns:
-                    ms[k] += timed(fns[k], a.calls)
-            pct = {k: np.percentile(v, [10, 50, 90]) for k, v in ms.items()}
-            for k in fns:
-                line = f"B = {B:4d} {what:8s} {k:6s}: p10 {pct[k][0]:8.3f} ms  median {pct[k][1]:8.3f}  p90 {pct[k][2]:8.3f}   ({len(ms[k])} calls)"
+                s = res[k]["device"]
+                line = f"B = {B:4d} {what:8s} {k:6s}: p10 {s['p10']:8.3f} ms  median {s['median']:8.3f}  p90 {s['p90']:8.3f}   ({a.calls * a.rounds} calls)"
                 if what == "stem":
-                    rate = 2.0 * macs * B / (pct[k][1] * 1e-3)
+                    rate = 2.0 * macs * B / (s["median"] * 1e-3)
                     line += f"   {rate / 1e12:6.2f} TFLOP/s = {rate / PEAK:.3f} of the fp32 matrix peak"
                 print(line)
-            below = pct["fused"][2] < pct["torch"][0]
-            print(f"B = {B:4d} {what:8s} fused / torch = {pct['fused'][1] / pct['torch'][1]:.3f} (medians); fused p90 {'<' if below else '>='} torch p10")
+            below = ab.wins(res, "fused", "torch", "device")
+            print(f"B = {B:4d} {what:8s} fused / torch = {res['fused']['device']['median'] / res['torch']['device']['median']:.3f} (medians); "
+                  f"fused p90 {'<' if below else '>='} torch p10")
             if what == "forward":
                 verdict.append(below)
 print(f"rule for the default: fused p90 < torch p10 at every size: {all(verdict)} -> FUSED_STEM_DEFAULT = {all(verdict)}")

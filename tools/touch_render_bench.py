@@ -5,7 +5,7 @@ Workload: an icosphere-5 (20 480 faces) of radius 0.16 at the origin; finger fra
 0.012 above the surface and looking at the centre, so every view touches.  Batch sizes: I = 12 (one ``RenderedSampler.sample`` at
 E = 3) and I = 600 (one ``sample_many`` at K = 50).
 
-Per batch size, device events around each call after the warm-up, median / p10 / p90 in ms of
+Per batch size, device events around each call after the warm-up, median / p10 / p90 (``ab_protocol.stats``) in ms of
     render   the whole call (both launches, all outputs),
     finish   ``ops.touch_finish`` on the depth maps of that call (the second launch alone),
     depth    the first launch: render - finish of the same round (a difference of two measurements, not an event pair of its own),
@@ -23,16 +23,15 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402  (tools/ is this script's directory)
 from a3vt_amd import mesh, ops  # noqa: E402
 
 p = argparse.ArgumentParser()
 p.add_argument("--sizes", default="12,600")
-p.add_argument("--warmup", type=int, default=20)
-p.add_argument("--calls", type=int, default=100)
+ab.add_arguments(p, calls=100, rounds=None, warmup=20, what="batch size")
 p.add_argument("--level", type=int, default=5)
 p.add_argument("--stat-views", type=int, default=3, help="views whose cull is restated on the host")
-p.add_argument("--out", default=None)
-a = p.parse_args()
+a = ab.parse(p)
 if a.warmup < 20 or a.calls < 100:
     raise SystemExit("touch_render_bench: at least 20 warm-up and 100 timed calls")
 RADIUS, LIFT, RES, TILE = 0.16, 0.012, 121, 16
@@ -73,18 +72,11 @@ def survivors(verts, faces, pos, rot, yfov, znear, zfar):
     return total
 
 
-def stats(ms):
-    ms = np.sort(np.asarray(ms))
-    return {"median": float(np.median(ms)), "p10": float(ms[int(0.1 * (len(ms) - 1))]), "p90": float(ms[int(round(0.9 * (len(ms) - 1)))])}
+stats, source = ab.stats, ab.CudaSource()            # p10 / p90 by np.percentile, as every tool's; device events per call
 
 
 def timed(fn):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    out = fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end), out
+    return ab.time_call(fn, source)["device"]
 
 
 v, f = mesh.icosphere(a.level, RADIUS)
@@ -110,8 +102,8 @@ for size in (int(s) for s in a.sizes.split(",")):
     torch.cuda.synchronize()
     t_render, t_finish = [], []
     for _ in range(a.calls):
-        t_render.append(timed(render)[0])
-        t_finish.append(timed(finish)[0])
+        t_render.append(timed(render))
+        t_finish.append(timed(finish))
     n_stat = min(a.stat_views, size)
     kept = np.mean([survivors(v, f, pos[i], rot[i], cam["yfov"], cam["znear"], cam["zfar"]) for i in range(n_stat)])
     entry = {"render": stats(t_render), "finish": stats(t_finish), "depth": stats(np.array(t_render) - np.array(t_finish)),
@@ -126,8 +118,4 @@ for size in (int(s) for s in a.sizes.split(",")):
                  f"{entry['tests_per_view']:.3e} ray-triangle tests per view, {entry['ray_triangle_tests_per_s']:.3e} per second of the "
                  f"depth launch")
 lines.append(json.dumps(result))
-text = "\n".join(lines) + "\n"
-print(text, end="")
-if a.out:
-    with open(a.out, "w") as fh:
-        fh.write(text)
+ab.emit(lines, a.out)
