@@ -58,3 +58,17 @@ def random_cloud(batch, n, seed, kind="ellipsoid"):
     d /= np.linalg.norm(d, axis=-1, keepdims=True)
     ax = g.uniform(0.05, 0.16, (batch, 1, 3))
     return torch.from_numpy((d * ax).astype(np.float32))
+
+
+def _fuzz_shapes(count, seed):
+    """Seeded random (m, k, n): k a multiple of 4 up to 452 (the image model's first layer), n up to 304, m from a few
+    rows to past the 2048-tile main/remainder split (32,768 rows)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(count):
+        k = 4 * int(rng.integers(1, 114))
+        n = int(rng.integers(1, 305))
+        m = int(rng.choice([rng.integers(1, 64), rng.integers(64, 3000), rng.integers(3000, 20000),
+                            rng.integers(32700, 36000)]))
+        out.append((m, k, n))
+    return out

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_grad_close, make_args, oracle_adj, random_cloud, rel_err, template
+from helpers import _fuzz_shapes, assert_grad_close, make_args, oracle_adj, random_cloud, rel_err, template
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +24,6 @@ def test_rowgemm_matches_fp64(cuda, m, k, n):
     ref = (a.double() @ w.double())
     # fp32 fma chain over K <= 300: ~1e-6 relative to the row scale
     assert rel_err(c, ref) < 2e-6
-
-
-def _fuzz_shapes(count, seed):
-    """Seeded random (m, k, n): k a multiple of 4 up to 452 (the image model's first layer), n up to 304, m from a few
-    rows to past the 2048-tile main/remainder split (32,768 rows)."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for i in range(count):
-        k = 4 * int(rng.integers(1, 114))
-        n = int(rng.integers(1, 305))
-        m = int(rng.choice([rng.integers(1, 64), rng.integers(64, 3000), rng.integers(3000, 20000),
-                            rng.integers(32700, 36000)]))
-        out.append((m, k, n))
-    return out
 
 
 @pytest.mark.parametrize("bf16", [False, True])
