@@ -33,6 +33,7 @@ def install_as_pterotactyl():
         "pterotactyl.utility.utils": ".pterotactyl.utility.utils",
         # consumers of the same kernels
         "pterotactyl.utility.data_loaders": ".pterotactyl.utility.data_loaders",
+        "pterotactyl.utility.data_making": ".pterotactyl.utility.data_making",
         "pterotactyl.reconstruction.autoencoder.model": ".pterotactyl.reconstruction.autoencoder.model",
         "pterotactyl.reconstruction.autoencoder.train": ".pterotactyl.reconstruction.autoencoder.train",
         "pterotactyl.policies.DDQN.model": ".pterotactyl.policies.DDQN.model",

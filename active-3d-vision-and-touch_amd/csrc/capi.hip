@@ -1464,6 +1464,114 @@ int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, co
   return launch_touch_finish(depth, cam_pos, cam_rot, I, max_depth, yfov, touch, points, count, status, s);
 }
 
+// ---- the ground-truth point cloud of a batch of meshes (voxel.hip) -----------------------------------------------------------------
+namespace {
+std::atomic<long long> g_voxel_launches[3];
+
+struct VoxelPtr {
+  const char *name;
+  const void *p;
+  bool required;
+  unsigned align;
+  const char *why;
+};
+int voxel_ptr_check(const char *who, const VoxelPtr *ptrs, int n) {
+  for (int i = 0; i < n; ++i) {
+    const VoxelPtr &a = ptrs[i];
+    if (a.required && !a.p) {
+      set_error("%s: %s=NULL: %s", who, a.name, a.why);
+      return -1;
+    }
+    if (!aligned_to(a.p, a.align)) {
+      set_error("%s: %s=%p is not %u-byte aligned", who, a.name, a.p, a.align);
+      return -1;
+    }
+  }
+  return 0;
+}
+int voxel_size_check(const char *who, int M, int dim) {
+  if (dim < kVoxelMinDim || dim > kVoxelMaxDim) {
+    set_error("%s: dim=%d outside %d..%d", who, dim, kVoxelMinDim, kVoxelMaxDim);
+    return -1;
+  }
+  if (M < 1 || M > kVoxelMaxMeshes) {
+    set_error("%s: M=%d outside 1..%d", who, M, kVoxelMaxMeshes);
+    return -1;
+  }
+  if ((long long)M * dim * dim * dim > kVoxelMaxCells) {
+    set_error("%s: M=%d meshes at dim=%d are more than %lld voxels", who, M, dim, kVoxelMaxCells);
+    return -1;
+  }
+  return 0;
+}
+}  // namespace
+
+int a3vt_voxel_surface(const float *verts, int V, const int32_t *faces, int F, const int32_t *vert_offset, const int32_t *face_offset, int M,
+                       int dim, uint8_t *occupancy, int32_t *depth_maps, int32_t *counts, void *stream) {
+  if (voxel_size_check("voxel_surface", M, dim)) return -1;
+  if (V < 0 || V > kVoxelMaxIndex) {
+    set_error("voxel_surface: V=%d outside 0..%d", V, kVoxelMaxIndex);
+    return -1;
+  }
+  if (F < 0 || F > kVoxelMaxIndex) {
+    set_error("voxel_surface: F=%d outside 0..%d", F, kVoxelMaxIndex);
+    return -1;
+  }
+  const VoxelPtr ptrs[] = {{"verts", verts, V > 0, 4, "required when V > 0"},
+                           {"faces", faces, F > 0, 4, "required when F > 0"},
+                           {"vert_offset", vert_offset, true, 4, "required"},
+                           {"face_offset", face_offset, true, 4, "required"},
+                           {"occupancy", occupancy, false, 1, ""},
+                           {"depth_maps", depth_maps, false, 4, ""},
+                           {"counts", counts, true, 4, "required"}};
+  if (voxel_ptr_check("voxel_surface", ptrs, (int)(sizeof(ptrs) / sizeof(ptrs[0])))) return -1;
+  const int rc = launch_voxel_surface(verts, V, faces, F, vert_offset, face_offset, M, dim, occupancy, depth_maps, counts,
+                                      static_cast<hipStream_t>(stream));
+  if (rc < 0) return rc;
+  g_voxel_launches[0].fetch_add(rc, std::memory_order_relaxed);
+  return 0;
+}
+
+int a3vt_voxel_depth_maps(const uint8_t *voxels, int M, int dim, int32_t *depth_maps, void *stream) {
+  if (voxel_size_check("voxel_depth_maps", M, dim)) return -1;
+  const VoxelPtr ptrs[] = {{"voxels", voxels, true, 1, "required"}, {"depth_maps", depth_maps, true, 4, "required"}};
+  if (voxel_ptr_check("voxel_depth_maps", ptrs, 2)) return -1;
+  const int rc = launch_voxel_depth_maps(voxels, M, dim, depth_maps, static_cast<hipStream_t>(stream));
+  if (rc < 0) return rc;
+  g_voxel_launches[1].fetch_add(rc, std::memory_order_relaxed);
+  return 0;
+}
+
+int a3vt_voxel_points(int M, int dim, long long total, int32_t *surface, float *aligned, const long long *index, int num_points, float *cloud,
+                      void *stream) {
+  if (voxel_size_check("voxel_points", M, dim)) return -1;
+  if (total < 0 || total > kVoxelMaxCells) {
+    set_error("voxel_points: total=%lld outside 0..%lld", total, kVoxelMaxCells);
+    return -1;
+  }
+  if (cloud && (num_points <= 0 || num_points > kVoxelMaxIndex)) {
+    set_error("voxel_points: num_points=%d outside 1..%d", num_points, kVoxelMaxIndex);
+    return -1;
+  }
+  const VoxelPtr ptrs[] = {{"surface", surface, total > 0, 4, "required when total > 0"},
+                           {"aligned", aligned, false, 4, ""},
+                           {"index", index, cloud != nullptr, 8, "index and cloud go together"},
+                           {"cloud", cloud, index != nullptr, 4, "index and cloud go together"}};
+  if (voxel_ptr_check("voxel_points", ptrs, 4)) return -1;
+  const int rc = launch_voxel_points(M, dim, total, surface, aligned, index, num_points, cloud, static_cast<hipStream_t>(stream));
+  if (rc < 0) return rc;
+  g_voxel_launches[2].fetch_add(rc, std::memory_order_relaxed);
+  return 0;
+}
+
+int a3vt_voxel_launches(long long *counts, int reset) {
+  for (int i = 0; i < 3; ++i) {
+    if (counts) counts[i] = g_voxel_launches[i].load(std::memory_order_relaxed);
+    if (reset) g_voxel_launches[i].store(0, std::memory_order_relaxed);
+  }
+  return 3;
+}
+
 // ---- the supervised latent policy's value network (latent_policy.hip) ------------------------------------------------------------
 namespace {
 static_assert(sizeof(a3vt_mlp) == sizeof(PolicyNet) && sizeof(a3vt_mlp_layer) == sizeof(PolicyLayer) &&

@@ -402,6 +402,18 @@ int launch_touch_depth(const float *verts, int V, const int32_t *faces, int F, c
 int launch_touch_finish(const float *depth, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float *touch,
                         float *points, int32_t *count, int32_t *status, hipStream_t s);
 
+// voxel.hip: the ground-truth point cloud of a batch of meshes (utility/data_making.py::extract_points): voxelise by adaptive
+// subdivision, column ranges (the six depth maps), carve + surface, realign + gather.  The launch_* return the number of operations
+// they enqueued (kernels, the clear, the optional copies), or a negative error code with the message set.
+constexpr int kVoxelMinDim = 4, kVoxelMaxDim = 256, kVoxelMaxMeshes = 4096, kVoxelMaxIndex = 1 << 28;
+constexpr long long kVoxelMaxCells = 1ll << 30;   // M * dim^3
+constexpr int kVoxelMaxDepth = 12;                // a sub-triangle of this depth is never split (ceil(log2(sqrt(3) * 256)) + 1 = 10)
+int launch_voxel_surface(const float *verts, int V, const int32_t *faces, int F, const int32_t *vert_offset, const int32_t *face_offset, int M,
+                         int dim, uint8_t *occupancy, int32_t *odm_out, int32_t *counts, hipStream_t s);
+int launch_voxel_depth_maps(const uint8_t *grids, int M, int dim, int32_t *odm, hipStream_t s);
+int launch_voxel_points(int M, int dim, long long total, int32_t *surface, float *aligned, const long long *index, int num_points,
+                        float *cloud, hipStream_t s);
+
 // latent_policy.hip: the supervised policy's value network (policies/supervised/model.py), its loss and its backward.  The layer
 // table travels by value in the kernel arguments (a3vt_mlp of include/a3vt.h, field for field).
 constexpr int kPolicyMaxLayers = 16;     // layers of a table

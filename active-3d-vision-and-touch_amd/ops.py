@@ -1372,6 +1372,234 @@ def touch_finish(depth, cam_pos, cam_rot, max_depth=TOUCH_DEFAULTS["max_depth"],
     return _touch_result(depth, touch, points, count, status)
 
 
+# csrc/kernels.h's kVoxelMinDim / kVoxelMaxDim / kVoxelMaxMeshes / kVoxelMaxCells / kVoxelMaxDepth
+VOXEL_LIMITS = dict(min_dim=4, max_dim=256, meshes=4096, cells=1 << 30, depth=12)
+
+
+def voxel_launches(reset=False):
+    """Operations ``a3vt_voxel_surface`` / ``a3vt_voxel_depth_maps`` / ``a3vt_voxel_points`` enqueued since the last reset (a test
+    hook, as ``policy_launches``)."""
+    buf = (ctypes.c_longlong * 3)()
+    _lib.load().a3vt_voxel_launches(buf, 1 if reset else 0)
+    return dict(zip(("surface", "depth_maps", "points"), (int(x) for x in buf)))
+
+
+def _voxel_check(verts, faces, vert_offset, face_offset, dim):
+    for t, name, dtype in ((verts, "verts", torch.float32), (faces, "faces", torch.int32), (vert_offset, "vert_offset", torch.int32),
+                           (face_offset, "face_offset", torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise RuntimeError(f"a3vt: voxel_surface `{name}` must be a {dtype} tensor")
+        if t.device != verts.device:
+            raise RuntimeError(f"a3vt: voxel_surface `{name}` is on {t.device}, verts on {verts.device}")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"a3vt: voxel_surface wants verts (V, 3) and faces (F, 3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    if vert_offset.dim() != 1 or vert_offset.numel() < 2 or face_offset.shape != vert_offset.shape:
+        raise ValueError(f"a3vt: voxel_surface wants vert_offset and face_offset (M + 1,), M >= 1, got {tuple(vert_offset.shape)} and "
+                         f"{tuple(face_offset.shape)}")
+    M, dim, lim = vert_offset.numel() - 1, int(dim), VOXEL_LIMITS
+    if not (lim["min_dim"] <= dim <= lim["max_dim"] and M <= lim["meshes"] and M * dim ** 3 <= lim["cells"]):
+        raise ValueError(f"a3vt: voxel_surface M={M} dim={dim} outside {lim}")
+    return M, dim
+
+
+def _voxel_mark_host(verts, faces, dim):
+    """One mesh's occupancy on NumPy, level by level: the contract of ``a3vt_voxel_surface``'s marking in ``include/a3vt.h``."""
+    f32 = np.float32
+    grid = np.zeros((dim, dim, dim), dtype=np.uint8)
+    finite = verts[np.isfinite(verts)]
+    faces = faces[((faces >= 0) & (faces < verts.shape[0])).all(axis=1)]
+    if finite.size == 0 or faces.shape[0] == 0:
+        return grid
+    lo, hi = finite.min(), finite.max()
+    with np.errstate(all="ignore"):
+        norm = (verts - lo) / (hi - lo) - f32(0.5)
+    a, b, c = norm[faces[:, 0]], norm[faces[:, 1]], norm[faces[:, 2]]
+    ok = np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1) & np.isfinite(c).all(axis=1)
+    a, b, c = a[ok], b[ok], c[ok]
+    thr = f32((1.0 / dim) ** 2)
+
+    def mark(p):
+        f = (p + f32(0.5)) * f32(dim - 1)
+        inside = ((f >= 0) & (f < f32(dim))).all(axis=1)
+        i = f[inside].astype(np.int64)
+        grid[i[:, 0], i[:, 1], i[:, 2]] = 1
+
+    def side(p, q):
+        d = p - q
+        d = d * d
+        return (d[:, 0] + d[:, 1]) + d[:, 2]
+
+    mark(np.concatenate((a, b, c)))
+    for _ in range(VOXEL_LIMITS["depth"]):
+        split = np.maximum(np.maximum(side(a, b), side(b, c)), side(c, a)) > thr
+        if not split.any():
+            break
+        a, b, c = a[split], b[split], c[split]
+        ac, ab, bc = (a + c) * f32(0.5), (a + b) * f32(0.5), (b + c) * f32(0.5)
+        mark(np.concatenate((ac, ab, bc)))
+        a, b, c = np.concatenate((a, ab, ab, ac)), np.concatenate((ac, b, ac, c)), np.concatenate((ab, bc, bc, bc))
+    return grid
+
+
+def _voxel_depth_maps_host(grid):
+    """``extract_ODMs``' values of one (dim, dim, dim) grid, int32 (6, dim, dim)."""
+    dim, occ = grid.shape[0], grid != 0
+    odm = np.empty((6, dim, dim), dtype=np.int32)
+    for axis in range(3):                                  # columns along k, j, i: the maps over (i, j), (i, k), (j, k)
+        along = np.moveaxis(occ, 2 - axis, 2)
+        some = along.any(axis=2)
+        odm[2 * axis] = np.where(some, np.argmax(along[:, :, ::-1], axis=2), dim)      # dim - 1 - last
+        odm[2 * axis + 1] = np.where(some, np.argmax(along, axis=2), dim)              # first
+    return odm
+
+
+def _voxel_carve_host(odm):
+    """Kept = inside all three column intervals (``apply_ODMs`` with its fill), uint8 (dim, dim, dim)."""
+    dim = odm.shape[1]
+    x = np.arange(dim)
+    i, j, k = x[:, None, None], x[None, :, None], x[None, None, :]
+    kept = (k >= odm[1][:, :, None]) & (k <= dim - 1 - odm[0][:, :, None])
+    kept &= (j >= odm[3][:, None, :]) & (j <= dim - 1 - odm[2][:, None, :])
+    kept &= (i >= odm[5][None, :, :]) & (i <= dim - 1 - odm[4][None, :, :])
+    return kept.astype(np.uint8)
+
+
+def _voxel_surface_host(kept):
+    """Surface voxels of a kept grid in lexicographic order, int32 (n, 3)."""
+    box = np.pad(kept.astype(np.int32), 1)
+    for axis in range(3):                                  # the 3 x 3 x 3 box sum, one axis at a time
+        lo = [slice(None)] * 3
+        mid, hi = list(lo), list(lo)
+        lo[axis], mid[axis], hi[axis] = slice(0, -2), slice(1, -1), slice(2, None)
+        box = box[tuple(lo)] + box[tuple(mid)] + box[tuple(hi)]
+    return np.argwhere((kept != 0) & (box < 27)).astype(np.int32)
+
+
+def _voxel_realign_host(surface, verts):
+    """``realign_points`` of one mesh's surface rows, fp32 (n, 3), in the reference's order of operations."""
+    f32 = np.float32
+    out = np.zeros(surface.shape, dtype=f32)
+    if surface.shape[0] == 0:
+        return out
+    for axis in range(3):
+        col, x = verts[:, axis], surface[:, axis].astype(f32)
+        col = col[np.isfinite(col)]
+        hi, lo = x.max(), x.min()
+        mid = (hi + lo) * f32(0.5)
+        c = x - mid
+        p_range = ((hi - mid) + f32(1)) - (lo - mid)
+        with np.errstate(all="ignore"):
+            v_range = col.max() - col.min() if col.size else f32(np.nan)
+            out[:, axis] = (c * v_range) / p_range
+    return out
+
+
+class VoxelSurface:
+    """What ``voxel_surface`` returns and ``voxel_points`` consumes: ``counts`` (M,) int32 on the inputs' device, ``occupancy`` /
+    ``depth_maps`` when asked for.  On the GPU the tables of the call live in the library's workspace until the next
+    ``voxel_surface`` call on that device; on the CPU they are kept here."""
+
+    def __init__(self, M, dim, device, counts, occupancy, depth_maps, host=None):
+        self.M, self.dim, self.device, self.counts, self.occupancy, self.depth_maps, self._host = M, dim, device, counts, occupancy, \
+            depth_maps, host
+
+
+def voxel_surface(verts, faces, vert_offset, face_offset, dim, want_occupancy=False, want_depth_maps=False):
+    """Voxelise, depth maps, carve and surface count of M meshes (``a3vt_voxel_surface``, csrc/voxel.hip; the whole contract is in
+    ``include/a3vt.h``).  ``verts`` (V, 3) float32 and ``faces`` (F, 3) int32 with indices local to each mesh, both concatenated
+    over the meshes; ``vert_offset`` / ``face_offset`` (M + 1,) int32.  Returns a ``VoxelSurface``.  GPU tensors run the kernels
+    (a fixed number of launches, no host synchronisation); CPU tensors take the same contract on NumPy, with identical results."""
+    M, dim = _voxel_check(verts, faces, vert_offset, face_offset, dim)
+    dev = verts.device
+    if not verts.is_cuda:
+        v, f, vo, fo = verts.numpy(), faces.numpy(), vert_offset.numpy(), face_offset.numpy()
+        V, F = v.shape[0], f.shape[0]
+        host = []
+        for m in range(M):
+            v0 = min(max(int(vo[m]), 0), V)
+            f0 = min(max(int(fo[m]), 0), F)
+            vm, fm = v[v0:min(max(int(vo[m + 1]), v0), V)], f[f0:min(max(int(fo[m + 1]), f0), F)]
+            occ = _voxel_mark_host(vm, fm, dim)
+            odm = _voxel_depth_maps_host(occ)
+            host.append((vm, occ, odm, _voxel_surface_host(_voxel_carve_host(odm))))
+        counts = torch.tensor([h[3].shape[0] for h in host], dtype=torch.int32)
+        occupancy = torch.from_numpy(np.stack([h[1] for h in host])) if want_occupancy else None
+        depth_maps = torch.from_numpy(np.stack([h[2] for h in host])) if want_depth_maps else None
+        return VoxelSurface(M, dim, dev, counts, occupancy, depth_maps, host)
+    verts, faces, vert_offset, face_offset = verts.contiguous(), faces.contiguous(), vert_offset.contiguous(), face_offset.contiguous()
+    counts = torch.empty(M, dtype=torch.int32, device=dev)
+    occupancy = torch.empty((M, dim, dim, dim), dtype=torch.uint8, device=dev) if want_occupancy else None
+    depth_maps = torch.empty((M, 6, dim, dim), dtype=torch.int32, device=dev) if want_depth_maps else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().a3vt_voxel_surface(_lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], _lib.ptr(vert_offset),
+                                                  _lib.ptr(face_offset), M, dim, _lib.ptr(occupancy), _lib.ptr(depth_maps),
+                                                  _lib.ptr(counts), _stream()), "voxel_surface")
+    return VoxelSurface(M, dim, dev, counts, occupancy, depth_maps)
+
+
+def voxel_points(state, counts=None, index=None, want_aligned=False):
+    """The clouds of the ``voxel_surface`` call that returned ``state`` (``a3vt_voxel_points``; no other ``voxel_surface`` call on that
+    device may lie between the two).  ``counts``: ``state.counts`` as the caller read it to the host (a list of M ints; read here
+    when None — the pipeline's one host read).  ``index`` (M, num_points) int64, or None: row p of mesh m's cloud is its realigned
+    surface row ``index[m, p] % n_m``.  Returns a dict: ``surface`` (total, 3) int32, the meshes' surface voxels one after the other,
+    each in lexicographic order; ``offset`` (a list of M + 1 ints into it); with ``want_aligned`` ``aligned`` (total, 3) float32;
+    with ``index`` ``cloud`` (M, num_points, 3) float32, zeros for a mesh without a surface."""
+    M, dim, dev = state.M, state.dim, state.device
+    counts = [int(c) for c in (state.counts.tolist() if counts is None else counts)]
+    offset = [0]
+    for c in counts:
+        offset.append(offset[-1] + c)
+    total = offset[-1]
+    if index is not None:
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != M or \
+                index.shape[1] < 1 or index.device != dev:
+            raise ValueError(f"a3vt: voxel_points wants index ({M}, num_points >= 1) int64 on {dev}")
+        index = index.contiguous()
+    out = {"offset": offset}
+    if state._host is not None:
+        surface = np.concatenate([h[3] for h in state._host]) if M else np.zeros((0, 3), np.int32)
+        aligned = [_voxel_realign_host(h[3], h[0]) for h in state._host]
+        out["surface"] = torch.from_numpy(surface)
+        if want_aligned:
+            out["aligned"] = torch.from_numpy(np.concatenate(aligned))
+        if index is not None:
+            idx = index.numpy()
+            cloud = np.zeros((M, idx.shape[1], 3), dtype=np.float32)
+            for m in range(M):
+                if counts[m]:
+                    cloud[m] = aligned[m][idx[m] % counts[m]]
+            out["cloud"] = torch.from_numpy(cloud)
+        return out
+    surface = torch.empty((total, 3), dtype=torch.int32, device=dev)
+    aligned = torch.empty((total, 3), dtype=torch.float32, device=dev) if want_aligned else None
+    cloud = torch.empty((M, index.shape[1], 3), dtype=torch.float32, device=dev) if index is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().a3vt_voxel_points(M, dim, total, _lib.ptr(surface), _lib.ptr(aligned), _lib.ptr(index),
+                                                 index.shape[1] if index is not None else 0, _lib.ptr(cloud), _stream()), "voxel_points")
+    out["surface"] = surface
+    if want_aligned:
+        out["aligned"] = aligned
+    if index is not None:
+        out["cloud"] = cloud
+    return out
+
+
+def voxel_depth_maps(voxels):
+    """``extract_ODMs``' six orthographic depth maps of grids (M, dim, dim, dim) uint8, non-zero = occupied -> (M, 6, dim, dim) int32
+    (``a3vt_voxel_depth_maps``: one launch; CPU tensors on NumPy).  The layout is in ``include/a3vt.h``."""
+    if not isinstance(voxels, torch.Tensor) or voxels.dtype != torch.uint8 or voxels.dim() != 4 or voxels.shape[1] != voxels.shape[2] or \
+            voxels.shape[2] != voxels.shape[3] or voxels.shape[0] < 1:
+        raise ValueError("a3vt: voxel_depth_maps wants grids (M, dim, dim, dim) uint8, M >= 1")
+    M, dim = voxels.shape[0], voxels.shape[1]
+    if not voxels.is_cuda:
+        return torch.from_numpy(np.stack([_voxel_depth_maps_host(g) for g in voxels.numpy()]))
+    voxels = voxels.contiguous()
+    odm = torch.empty((M, 6, dim, dim), dtype=torch.int32, device=voxels.device)
+    with torch.cuda.device(voxels.device):
+        _lib.check(_lib.load().a3vt_voxel_depth_maps(_lib.ptr(voxels), M, dim, _lib.ptr(odm), _stream()), "voxel_depth_maps")
+    return odm
+
+
 # csrc/kernels.h's kPolicyMaxRows / kPolicyMaxWidth / kPolicyMaxLayers (a3vt_latent_policy_limit returns the library's own): rows
 # of a call (and steps of the loss), every layer's in and out, layers of a table.
 LATENT_POLICY_MAX = dict(rows=4096, width=1024, layers=16)

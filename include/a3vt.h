@@ -656,6 +656,75 @@ int a3vt_touch_finish(const float *depth, const float *cam_pos, const float *cam
                       float *points, int32_t *count, int32_t *status, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The ground-truth point cloud of a mesh: utility/data_making.py::extract_points (mesh_to_voxel, extract_ODMs, apply_ODMs,
+ * voxel_to_pointcloud, realign_points of utility/utils.py) for a batch of M meshes.
+ *
+ *   verts        [V][3] fp32, the meshes' vertices concatenated
+ *   faces        [F][3] int32, the meshes' faces concatenated, each with indices LOCAL to its mesh (as the mesh's file stores them)
+ *   vert_offset  [M + 1] int32: mesh m owns vertices vert_offset[m] .. vert_offset[m + 1] - 1
+ *   face_offset  [M + 1] int32: the same for faces
+ *   dim          the grid's resolution; a grid is [dim][dim][dim] bytes, (i, j, k) = (x, y, z), k fastest
+ *
+ * a3vt_voxel_surface: everything up to the size of each mesh's surface.
+ * - Normalisation.  n(v) = (v - lo) / (hi - lo) - 0.5 in fp32, each step rounded, lo / hi the smallest / largest FINITE coordinate
+ *   of the mesh's vertices, used or not, over all three axes.
+ * - Subdivision.  A triangle (a, b, c) is split while its largest squared side exceeds (float)((1.0 / dim)^2): strictly, the squared
+ *   side being ((dx dx + dy dy) + dz dz) with every step rounded.  Its children are (a, ac, ab), (ab, b, bc), (ab, ac, bc),
+ *   (ac, c, bc) with ab = (a + b) / 2 and so on.  The test is per triangle, so siblings stop at different depths.  A triangle of
+ *   depth 12 is never split (no finite input reaches it: the depth is at most ceil(log2(sqrt(3) dim)) + 1 <= 10).
+ * - Marking.  Every face's three vertices and every midpoint formed mark voxel trunc((p + 0.5) * (dim - 1)) per axis, fp32, each step
+ *   rounded.  A face with an index outside its mesh, or with a non-finite normalised coordinate, marks nothing.
+ * - occupancy [M][dim][dim][dim] uint8 out, or NULL: the marked grid (mesh_to_voxel's).
+ * - depth_maps [M][6][dim][dim] int32 out, or NULL: extract_ODMs' values — see a3vt_voxel_depth_maps.
+ * - Carving.  A voxel is kept iff along each of the three axes it lies inside [first, last] occupied voxel of its column.  This equals
+ *   apply_ODMs INCLUDING its binary_fill_holes: a carved voxel lies outside its column's interval along some axis, and so does
+ *   every voxel beyond it in that column out to the border, so no carved region is enclosed.
+ * - Surface.  A kept voxel with fewer than 27 kept voxels in its 3 x 3 x 3 neighbourhood, voxels outside the grid counting as empty
+ *   (voxel_to_pointcloud).  counts [M] int32 out: the number of surface voxels of each mesh.
+ * The tables the next call needs (kept grids, row offsets, the surface's and the vertices' per-axis bounds) stay in the library's
+ * workspace: one per device, grown with hipMalloc when a call needs more than any before it (the only allocation; it may
+ * synchronise the device), and cleared by every call — nothing of an earlier call's grids is visible to a later one.  Calls that share
+ * a device must therefore be made in order, from one thread at a time, on one stream.
+ *
+ * a3vt_voxel_points: the clouds, from the workspace of the a3vt_voxel_surface call right before it (same M and dim, else an error).
+ * - total: the sum of that call's counts, which the caller read from the device (the one host read the pipeline needs: the size of
+ *   `surface` depends on it).
+ * - surface [total][3] int32 out: the surface voxels (i, j, k), mesh after mesh, each mesh's in lexicographic order (torch.where's).
+ * - aligned [total][3] fp32 out, or NULL: realign_points of every row.  Per axis, in fp32 with every step rounded, lo / hi the
+ *   surface's smallest / largest index on that axis of that mesh: mid = (hi + lo) / 2; c = x - mid; range = ((hi - mid) + 1) - (lo - mid);
+ *   result = (c * (vhi - vlo)) / range, vlo / vhi the smallest / largest finite vertex coordinate of the mesh on that axis.
+ * - cloud [M][num_points][3] fp32 out with index [M][num_points] int64, both or neither: row p of mesh m is the realigned surface
+ *   row index[m][p] mod n_m of that mesh — "mod" because the reference doubles a cloud of n_m rows until it has num_points, and row r
+ *   of a doubled cloud is row r mod n_m.  A mesh with n_m = 0 gets zeros.
+ *
+ * a3vt_voxel_depth_maps: extract_ODMs on grids the caller supplies.  voxels [M][dim][dim][dim] uint8, non-zero = occupied.
+ * depth_maps [m][0][i][j] = dim - 1 - (last occupied k of column (i, j)), [1][i][j] = its first occupied k; [2], [3] the same along j
+ * for column (i, k); [4], [5] along i for column (j, k); dim for an empty column.
+ *
+ * Launches per call do not depend on M, the number of faces or the subdivision depth: a3vt_voxel_surface enqueues the clear and seven
+ * kernels (six without faces; one copy more for each optional output), a3vt_voxel_points two kernels, a3vt_voxel_depth_maps one.
+ * Nothing synchronises the host.  Marking is a plain store of 1, the surface's bounds are integer atomics, every float step is
+ * rounded on its own (the file is compiled without contraction): the same bits on every call, whatever else is in the batch.
+ * a3vt_voxel_launches: operations enqueued since the last reset by [0] a3vt_voxel_surface, [1] a3vt_voxel_depth_maps,
+ * [2] a3vt_voxel_points; returns 3.
+ *
+ * What the host cannot check is made safe in the kernel: offsets are clamped into [0, V] / [0, F], and an end below its start
+ * counts as the start (an empty mesh); writes to `surface` stop at `total`.
+ *
+ * Limits.
+ * - 4 <= dim <= 256, 1 <= M <= 4096, M * dim^3 <= 2^30, 0 <= V, F <= 268435456, 0 <= total <= 2^30, 1 <= num_points <= 268435456.
+ * - verts may be NULL when V == 0, faces when F == 0, surface when total == 0.
+ * - Pointers are 4-byte aligned, index 8-byte aligned; the byte grids need no alignment.
+ * - Anything else, or a missing required pointer, returns non-zero with a message in a3vt_last_error that names the argument and
+ *   its value.  Nothing is launched. */
+int a3vt_voxel_surface(const float *verts, int V, const int32_t *faces, int F, const int32_t *vert_offset, const int32_t *face_offset, int M,
+                       int dim, uint8_t *occupancy, int32_t *depth_maps, int32_t *counts, void *stream);
+int a3vt_voxel_depth_maps(const uint8_t *voxels, int M, int dim, int32_t *depth_maps, void *stream);
+int a3vt_voxel_points(int M, int dim, long long total, int32_t *surface, float *aligned, const long long *index, int num_points, float *cloud,
+                      void *stream);
+int a3vt_voxel_launches(long long *counts /*[3]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The supervised latent policy's value network (policies/supervised/model.py, train.py:119-158), fp32 throughout.
  *
  * The network is a table of at most 16 layers, read on the host and passed to the kernels by value.  Layer l computes
