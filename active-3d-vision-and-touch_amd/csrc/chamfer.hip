@@ -487,13 +487,20 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_kernel(const float *__restri
   const float g = gcd[t % batch] * inv_draws;
   const float ct = g * (2.0f / (float)nt), cs = g * (2.0f / (float)ns);
 
-  // bound on |T_i - S_j| per coordinate: max|T| + max|S| over the clouds involved (the same value in every tile)
+  // bound on |T_i - S_j| per coordinate: max|T| + max|S| over the clouds involved (the same value in every tile).
+  // fmaxf returns its other operand for a NaN, so a NaN coordinate enters the maximum as Inf: the comparison is false for it.
   float mx = 0.f;
-  for (int i = tid; i < nt * 3; i += 1024) mx = fmaxf(mx, fabsf(T[i]));
+  for (int i = tid; i < nt * 3; i += 1024) {
+    const float a = fabsf(T[i]);
+    mx = fmaxf(mx, a < INFINITY ? a : INFINITY);
+  }
   float ms = 0.f;
   for (int s = 0; s < nsrc; ++s) {
     const float *S = src + (s * src_stride_s + (t % src_mod)) * ns * 3;
-    for (int j = tid; j < ns * 3; j += 1024) ms = fmaxf(ms, fabsf(S[j]));
+    for (int j = tid; j < ns * 3; j += 1024) {
+      const float a = fabsf(S[j]);
+      ms = fmaxf(ms, a < INFINITY ? a : INFINITY);
+    }
   }
   mx = wave_max(mx);
   ms = wave_max(ms);

@@ -441,7 +441,9 @@ int a3vt_chamfer_fwd_shared(const float *x, const float *y, int draws, int batch
                             float *dist_xy, int32_t *idx_xy, float *dist_yx, int32_t *idx_yx, float *cd,
                             void *workspace, size_t workspace_bytes, int algo, void *stream);
 /* grad_cd [batch].  grad_x [draws][batch][p][3] overwritten; grad_y [batch][q][3] overwritten, may be
- * NULL (the trainer's ground truth needs no gradient, vision/train.py:141-143). */
+ * NULL (the trainer's ground truth needs no gradient, vision/train.py:141-143).  Every index must be in range.
+ * A NaN or Inf coordinate makes the gradient of every cloud it enters NaN throughout: x[r][b] poisons grad_x[r][b] and
+ * grad_y[b], y[b] poisons grad_x[.][b] and grad_y[b]; the other clouds are unaffected. */
 int a3vt_chamfer_bwd(const float *x, const float *y, int draws, int batch, int p, int q,
                      const int32_t *idx_xy, const int32_t *idx_yx, const float *grad_cd,
                      float *grad_x, float *grad_y, void *stream);

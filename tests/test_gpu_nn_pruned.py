@@ -182,6 +182,8 @@ def test_pruned_nonfinite_coordinates_stay_in_bounds(cuda):
     ops.ChamferFn.apply(xg, y.to(cuda)).sum().backward()
     torch.cuda.synchronize()
     assert torch.isfinite(xg.grad[0, 0]).all()
+    # ... and says so where a cloud is poisoned: x[0, 1] itself, and x[0, 2] through its ground truth y[2] — NaN throughout
+    assert torch.isnan(xg.grad[0, 1]).all() and torch.isnan(xg.grad[0, 2]).all()
 
 
 def test_training_is_bit_identical_whichever_search_runs(cuda):
