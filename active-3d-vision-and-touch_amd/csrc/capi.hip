@@ -7,6 +7,7 @@
 
 #include "../../include/a3vt.h"
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
 
@@ -23,6 +24,64 @@ void set_error(const char *fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
 }
+
+// ---- the argument-check vocabulary of the entry points: each returns 0, or -1 with the message set.
+// A table of pointer arguments, checked in table order, per entry null first, then alignment.
+struct PtrArg {
+  const char *name;
+  const void *p;
+  bool required;
+  unsigned align;
+  const char *why;
+};
+static int check_ptrs(const char *who, std::initializer_list<PtrArg> ptrs) {
+  for (const PtrArg &a : ptrs) {
+    if (a.required && !a.p) {
+      set_error("%s: %s=NULL: %s", who, a.name, a.why);
+      return -1;
+    }
+    if (!aligned_to(a.p, a.align)) {
+      set_error("%s: %s=%p is not %u-byte aligned", who, a.name, a.p, a.align);
+      return -1;
+    }
+  }
+  return 0;
+}
+// One value against its closed range.
+static int check_range(const char *who, const char *name, long long v, long long lo, long long hi) {
+  if (v >= lo && v <= hi) return 0;
+  set_error("%s: %s=%lld outside %lld..%lld", who, name, v, lo, hi);
+  return -1;
+}
+// One count (rows, steps, a batch, actions) against the largest the kernels take.
+static int check_count(const char *who, const char *name, int v, int max) {
+  if (v >= 1 && v <= max) return 0;
+  set_error("%s: %s=%d (1..%d) unsupported", who, name, v, max);
+  return -1;
+}
+// The gradient table of a layer table of n_layers layers.
+static int check_grads(const char *who, const PolicyGrads &g, int n_layers) {
+  for (int l = 0; l < n_layers; ++l) {
+    if (!g.dw[l] || !g.db[l] || !aligned_to(g.dw[l], 4) || !aligned_to(g.db[l], 4)) {
+      set_error("%s: layer %d dweight / dbias null or misaligned", who, l);
+      return -1;
+    }
+  }
+  return 0;
+}
+// Launch counters of a feature's entry points (the a3vt_*_launches test hooks): one relaxed add per accepted call.
+template <int N>
+struct LaunchCounts {
+  std::atomic<long long> n[N];
+  void add(int i, long long k) { n[i].fetch_add(k, std::memory_order_relaxed); }
+  int read(long long *counts, int reset) {
+    for (int i = 0; i < N; ++i) {
+      if (counts) counts[i] = n[i].load(std::memory_order_relaxed);
+      if (reset) n[i].store(0, std::memory_order_relaxed);
+    }
+    return N;
+  }
+};
 
 // 256 bytes of zeros in the code object: source for out-of-range LDS-DMA lanes.
 __device__ float g_zero_page[64];
@@ -1346,50 +1405,26 @@ int a3vt_candidate_tally(const float *scores, const int32_t *candidates, const f
               kTallyMaxActions);
     return -1;
   }
-  const struct {
-    const char *name;
-    const void *p;
-    bool required;
-    unsigned align;
-    const char *why;
-  } ptrs[] = {{"scores", scores, true, 4, "required"},
-              {"candidates", candidates, true, 4, "required"},
-              {"first_score", first_score, sums != nullptr, 4, "required with sums"},
-              {"taken", taken, false, 4, ""},
-              {"sums", sums, checks != nullptr, 8, "sums and checks go together"},
-              {"checks", checks, sums != nullptr, 8, "sums and checks go together"},
-              {"votes", votes, false, 8, ""},
-              {"best", best, votes != nullptr, 4, "required with votes"},
-              {"best_score", best_score, false, 4, ""}};
-  for (const auto &a : ptrs) {
-    if (a.required && !a.p) {
-      set_error("candidate_tally: %s=NULL: %s", a.name, a.why);
-      return -1;
-    }
-    if (!aligned_to(a.p, a.align)) {
-      set_error("candidate_tally: %s=%p is not %u-byte aligned", a.name, a.p, a.align);
-      return -1;
-    }
-  }
+  if (check_ptrs("candidate_tally", {{"scores", scores, true, 4, "required"},
+                                     {"candidates", candidates, true, 4, "required"},
+                                     {"first_score", first_score, sums != nullptr, 4, "required with sums"},
+                                     {"taken", taken, false, 4, ""},
+                                     {"sums", sums, checks != nullptr, 8, "sums and checks go together"},
+                                     {"checks", checks, sums != nullptr, 8, "sums and checks go together"},
+                                     {"votes", votes, false, 8, ""},
+                                     {"best", best, votes != nullptr, 4, "required with votes"},
+                                     {"best_score", best_score, false, 4, ""}}))
+    return -1;
   return launch_candidate_tally(scores, candidates, first_score, taken, K, E, A, unvisited, sums, checks, votes, best, best_score,
                                 static_cast<hipStream_t>(stream));
 }
 
 // ---- the rendered touch sampler (touch_render.hip) ---------------------------------------------------------------------------------
 namespace {
-struct TouchPtr {
-  const char *name;
-  const void *p;
-  bool required;
-  const char *why;
-};
 // The finish launch's own arguments (shared by both entries): 0, or -1 with the message set.
 int touch_finish_check(const char *who, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, const float *depth,
                        const float *touch, const float *points, const int32_t *count, const int32_t *status) {
-  if (I < 1 || I > kTouchMaxImages) {
-    set_error("%s: I=%d outside 1..%d", who, I, kTouchMaxImages);
-    return -1;
-  }
+  if (check_range(who, "I", I, 1, kTouchMaxImages)) return -1;
   if (!(max_depth > 0.f)) {
     set_error("%s: max_depth=%g must be > 0", who, (double)max_depth);
     return -1;
@@ -1398,24 +1433,13 @@ int touch_finish_check(const char *who, const float *cam_pos, const float *cam_r
     set_error("%s: yfov=%g outside (0, pi)", who, (double)yfov);
     return -1;
   }
-  const TouchPtr ptrs[] = {{"cam_pos", cam_pos, true, "required"},
-                           {"cam_rot", cam_rot, true, "required"},
-                           {"depth", depth, true, "required"},
-                           {"touch", touch, false, ""},
-                           {"points", points, count != nullptr, "points and count go together"},
-                           {"count", count, points != nullptr, "points and count go together"},
-                           {"status", status, true, "required"}};
-  for (const auto &a : ptrs) {
-    if (a.required && !a.p) {
-      set_error("%s: %s=NULL: %s", who, a.name, a.why);
-      return -1;
-    }
-    if (!aligned_to(a.p, 4)) {
-      set_error("%s: %s=%p is not 4-byte aligned", who, a.name, a.p);
-      return -1;
-    }
-  }
-  return 0;
+  return check_ptrs(who, {{"cam_pos", cam_pos, true, 4, "required"},
+                          {"cam_rot", cam_rot, true, 4, "required"},
+                          {"depth", depth, true, 4, "required"},
+                          {"touch", touch, false, 4, ""},
+                          {"points", points, count != nullptr, 4, "points and count go together"},
+                          {"count", count, points != nullptr, 4, "points and count go together"},
+                          {"status", status, true, 4, "required"}});
 }
 }  // namespace
 
@@ -1428,10 +1452,7 @@ int a3vt_touch_finish(const float *depth, const float *cam_pos, const float *cam
 int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, const int32_t *face_offset, int M, const int32_t *image_mesh,
                       const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float znear, float zfar, float *depth,
                       float *touch, float *points, int32_t *count, int32_t *status, void *stream) {
-  if (M < 1 || M > kTouchMaxMeshes) {
-    set_error("touch_render: M=%d outside 1..%d", M, kTouchMaxMeshes);
-    return -1;
-  }
+  if (check_range("touch_render", "M", M, 1, kTouchMaxMeshes)) return -1;
   if (V < 0 || V > kTouchMaxIndex || F < 0 || F > kTouchMaxIndex) {
     set_error("touch_render: V=%d F=%d outside 0..%d", V, F, kTouchMaxIndex);
     return -1;
@@ -1444,20 +1465,11 @@ int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, co
     set_error("touch_render: zfar=%g must be above znear=%g", (double)zfar, (double)znear);
     return -1;
   }
-  const TouchPtr ptrs[] = {{"verts", verts, V > 0, "required when V > 0"},
-                           {"faces", faces, F > 0, "required when F > 0"},
-                           {"face_offset", face_offset, true, "required"},
-                           {"image_mesh", image_mesh, true, "required"}};
-  for (const auto &a : ptrs) {
-    if (a.required && !a.p) {
-      set_error("touch_render: %s=NULL: %s", a.name, a.why);
-      return -1;
-    }
-    if (!aligned_to(a.p, 4)) {
-      set_error("touch_render: %s=%p is not 4-byte aligned", a.name, a.p);
-      return -1;
-    }
-  }
+  if (check_ptrs("touch_render", {{"verts", verts, V > 0, 4, "required when V > 0"},
+                                  {"faces", faces, F > 0, 4, "required when F > 0"},
+                                  {"face_offset", face_offset, true, 4, "required"},
+                                  {"image_mesh", image_mesh, true, 4, "required"}}))
+    return -1;
   if (touch_finish_check("touch_render", cam_pos, cam_rot, I, max_depth, yfov, depth, touch, points, count, status)) return -1;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int rc = launch_touch_depth(verts, V, faces, F, face_offset, M, image_mesh, cam_pos, cam_rot, I, yfov, znear, zfar, depth, s)) return rc;
@@ -1466,38 +1478,10 @@ int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, co
 
 // ---- the ground-truth point cloud of a batch of meshes (voxel.hip) -----------------------------------------------------------------
 namespace {
-std::atomic<long long> g_voxel_launches[3];
+LaunchCounts<3> g_voxel_launches;
 
-struct VoxelPtr {
-  const char *name;
-  const void *p;
-  bool required;
-  unsigned align;
-  const char *why;
-};
-int voxel_ptr_check(const char *who, const VoxelPtr *ptrs, int n) {
-  for (int i = 0; i < n; ++i) {
-    const VoxelPtr &a = ptrs[i];
-    if (a.required && !a.p) {
-      set_error("%s: %s=NULL: %s", who, a.name, a.why);
-      return -1;
-    }
-    if (!aligned_to(a.p, a.align)) {
-      set_error("%s: %s=%p is not %u-byte aligned", who, a.name, a.p, a.align);
-      return -1;
-    }
-  }
-  return 0;
-}
 int voxel_size_check(const char *who, int M, int dim) {
-  if (dim < kVoxelMinDim || dim > kVoxelMaxDim) {
-    set_error("%s: dim=%d outside %d..%d", who, dim, kVoxelMinDim, kVoxelMaxDim);
-    return -1;
-  }
-  if (M < 1 || M > kVoxelMaxMeshes) {
-    set_error("%s: M=%d outside 1..%d", who, M, kVoxelMaxMeshes);
-    return -1;
-  }
+  if (check_range(who, "dim", dim, kVoxelMinDim, kVoxelMaxDim) || check_range(who, "M", M, 1, kVoxelMaxMeshes)) return -1;
   if ((long long)M * dim * dim * dim > kVoxelMaxCells) {
     set_error("%s: M=%d meshes at dim=%d are more than %lld voxels", who, M, dim, kVoxelMaxCells);
     return -1;
@@ -1509,68 +1493,48 @@ int voxel_size_check(const char *who, int M, int dim) {
 int a3vt_voxel_surface(const float *verts, int V, const int32_t *faces, int F, const int32_t *vert_offset, const int32_t *face_offset, int M,
                        int dim, uint8_t *occupancy, int32_t *depth_maps, int32_t *counts, void *stream) {
   if (voxel_size_check("voxel_surface", M, dim)) return -1;
-  if (V < 0 || V > kVoxelMaxIndex) {
-    set_error("voxel_surface: V=%d outside 0..%d", V, kVoxelMaxIndex);
+  if (check_range("voxel_surface", "V", V, 0, kVoxelMaxIndex) || check_range("voxel_surface", "F", F, 0, kVoxelMaxIndex)) return -1;
+  if (check_ptrs("voxel_surface", {{"verts", verts, V > 0, 4, "required when V > 0"},
+                                   {"faces", faces, F > 0, 4, "required when F > 0"},
+                                   {"vert_offset", vert_offset, true, 4, "required"},
+                                   {"face_offset", face_offset, true, 4, "required"},
+                                   {"occupancy", occupancy, false, 1, ""},
+                                   {"depth_maps", depth_maps, false, 4, ""},
+                                   {"counts", counts, true, 4, "required"}}))
     return -1;
-  }
-  if (F < 0 || F > kVoxelMaxIndex) {
-    set_error("voxel_surface: F=%d outside 0..%d", F, kVoxelMaxIndex);
-    return -1;
-  }
-  const VoxelPtr ptrs[] = {{"verts", verts, V > 0, 4, "required when V > 0"},
-                           {"faces", faces, F > 0, 4, "required when F > 0"},
-                           {"vert_offset", vert_offset, true, 4, "required"},
-                           {"face_offset", face_offset, true, 4, "required"},
-                           {"occupancy", occupancy, false, 1, ""},
-                           {"depth_maps", depth_maps, false, 4, ""},
-                           {"counts", counts, true, 4, "required"}};
-  if (voxel_ptr_check("voxel_surface", ptrs, (int)(sizeof(ptrs) / sizeof(ptrs[0])))) return -1;
   const int rc = launch_voxel_surface(verts, V, faces, F, vert_offset, face_offset, M, dim, occupancy, depth_maps, counts,
                                       static_cast<hipStream_t>(stream));
   if (rc < 0) return rc;
-  g_voxel_launches[0].fetch_add(rc, std::memory_order_relaxed);
+  g_voxel_launches.add(0, rc);
   return 0;
 }
 
 int a3vt_voxel_depth_maps(const uint8_t *voxels, int M, int dim, int32_t *depth_maps, void *stream) {
   if (voxel_size_check("voxel_depth_maps", M, dim)) return -1;
-  const VoxelPtr ptrs[] = {{"voxels", voxels, true, 1, "required"}, {"depth_maps", depth_maps, true, 4, "required"}};
-  if (voxel_ptr_check("voxel_depth_maps", ptrs, 2)) return -1;
+  if (check_ptrs("voxel_depth_maps", {{"voxels", voxels, true, 1, "required"}, {"depth_maps", depth_maps, true, 4, "required"}})) return -1;
   const int rc = launch_voxel_depth_maps(voxels, M, dim, depth_maps, static_cast<hipStream_t>(stream));
   if (rc < 0) return rc;
-  g_voxel_launches[1].fetch_add(rc, std::memory_order_relaxed);
+  g_voxel_launches.add(1, rc);
   return 0;
 }
 
 int a3vt_voxel_points(int M, int dim, long long total, int32_t *surface, float *aligned, const long long *index, int num_points, float *cloud,
                       void *stream) {
   if (voxel_size_check("voxel_points", M, dim)) return -1;
-  if (total < 0 || total > kVoxelMaxCells) {
-    set_error("voxel_points: total=%lld outside 0..%lld", total, kVoxelMaxCells);
+  if (check_range("voxel_points", "total", total, 0, kVoxelMaxCells)) return -1;
+  if (cloud && check_range("voxel_points", "num_points", num_points, 1, kVoxelMaxIndex)) return -1;
+  if (check_ptrs("voxel_points", {{"surface", surface, total > 0, 4, "required when total > 0"},
+                                  {"aligned", aligned, false, 4, ""},
+                                  {"index", index, cloud != nullptr, 8, "index and cloud go together"},
+                                  {"cloud", cloud, index != nullptr, 4, "index and cloud go together"}}))
     return -1;
-  }
-  if (cloud && (num_points <= 0 || num_points > kVoxelMaxIndex)) {
-    set_error("voxel_points: num_points=%d outside 1..%d", num_points, kVoxelMaxIndex);
-    return -1;
-  }
-  const VoxelPtr ptrs[] = {{"surface", surface, total > 0, 4, "required when total > 0"},
-                           {"aligned", aligned, false, 4, ""},
-                           {"index", index, cloud != nullptr, 8, "index and cloud go together"},
-                           {"cloud", cloud, index != nullptr, 4, "index and cloud go together"}};
-  if (voxel_ptr_check("voxel_points", ptrs, 4)) return -1;
   const int rc = launch_voxel_points(M, dim, total, surface, aligned, index, num_points, cloud, static_cast<hipStream_t>(stream));
   if (rc < 0) return rc;
-  g_voxel_launches[2].fetch_add(rc, std::memory_order_relaxed);
+  g_voxel_launches.add(2, rc);
   return 0;
 }
 
-int a3vt_voxel_launches(long long *counts, int reset) {
-  for (int i = 0; i < 3; ++i) {
-    if (counts) counts[i] = g_voxel_launches[i].load(std::memory_order_relaxed);
-    if (reset) g_voxel_launches[i].store(0, std::memory_order_relaxed);
-  }
-  return 3;
-}
+int a3vt_voxel_launches(long long *counts, int reset) { return g_voxel_launches.read(counts, reset); }
 
 // ---- the supervised latent policy's value network (latent_policy.hip) ------------------------------------------------------------
 namespace {
@@ -1578,7 +1542,7 @@ static_assert(sizeof(a3vt_mlp) == sizeof(PolicyNet) && sizeof(a3vt_mlp_layer) ==
                   sizeof(a3vt_mlp_grads) == sizeof(PolicyGrads) && offsetof(a3vt_mlp, n_layers) == offsetof(PolicyNet, n_layers) &&
                   offsetof(a3vt_mlp, scale) == offsetof(PolicyNet, scale) && offsetof(a3vt_mlp_layer, in) == offsetof(PolicyLayer, in),
               "a3vt_mlp is PolicyNet field for field");
-std::atomic<long long> g_policy_launches[3];
+LaunchCounts<3> g_policy_launches;
 
 // The table's own rules -> floats of a stash row (the sum of the layers' out), or -1 with the message set.
 int policy_net_check(const char *who, const a3vt_mlp *net) {
@@ -1612,11 +1576,6 @@ int policy_net_check(const char *who, const a3vt_mlp *net) {
   }
   return total;
 }
-bool policy_rows_ok(const char *who, const char *name, int v) {
-  if (v >= 1 && v <= kPolicyMaxRows) return true;
-  set_error("%s: %s=%d (1..%d) unsupported", who, name, v, kPolicyMaxRows);
-  return false;
-}
 PolicyNet policy_net_of(const a3vt_mlp *net) {
   PolicyNet n;
   memcpy(&n, net, sizeof(n));
@@ -1636,26 +1595,24 @@ int a3vt_latent_policy_stash_floats(const a3vt_mlp *net) {
 int a3vt_latent_policy_fwd(const a3vt_mlp *net, const float *mask, const float *latent, const float *first_latent, const float *taken,
                            int rows, float *values, int32_t *action, float *stash, void *stream) {
   const int ld = policy_net_check("latent_policy_fwd", net);
-  if (ld < 0 || !policy_rows_ok("latent_policy_fwd", "rows", rows)) return -1;
+  if (ld < 0 || check_count("latent_policy_fwd", "rows", rows, kPolicyMaxRows)) return -1;
   A3VT_CHECK_ARG(mask && latent && first_latent && values);
   A3VT_CHECK_ARG((taken && action) || (!taken && !action));
   A3VT_CHECK_ARG(aligned_to(mask, 4) && aligned_to(latent, 4) && aligned_to(first_latent, 4) && aligned_to(taken, 4) &&
                  aligned_to(values, 4) && aligned_to(action, 4) && aligned_to(stash, 4));
-  g_policy_launches[0].fetch_add(1, std::memory_order_relaxed);
+  g_policy_launches.add(0, 1);
   return launch_policy_fwd(policy_net_of(net), mask, latent, first_latent, taken, rows, values, action, stash, ld,
                            static_cast<hipStream_t>(stream));
 }
 
 int a3vt_action_value_loss(const float *values, const int32_t *actions, const float *targets, int steps, int rows, int num_actions,
                            float *loss, float *dvalues, void *stream) {
-  if (!policy_rows_ok("action_value_loss", "steps", steps) || !policy_rows_ok("action_value_loss", "rows", rows)) return -1;
-  if (num_actions < 1 || num_actions > kPolicyMaxWidth) {
-    set_error("action_value_loss: num_actions=%d (1..%d) unsupported", num_actions, kPolicyMaxWidth);
+  if (check_count("action_value_loss", "steps", steps, kPolicyMaxRows) || check_count("action_value_loss", "rows", rows, kPolicyMaxRows) ||
+      check_count("action_value_loss", "num_actions", num_actions, kPolicyMaxWidth))
     return -1;
-  }
   A3VT_CHECK_ARG(values && actions && targets && loss && dvalues);
   A3VT_CHECK_ARG(aligned_to(values, 4) && aligned_to(actions, 4) && aligned_to(targets, 4) && aligned_to(loss, 4) && aligned_to(dvalues, 4));
-  g_policy_launches[1].fetch_add(1, std::memory_order_relaxed);
+  g_policy_launches.add(1, 1);
   return launch_action_value_loss(values, actions, targets, steps, rows, num_actions, loss, dvalues, static_cast<hipStream_t>(stream));
 }
 
@@ -1663,34 +1620,23 @@ int a3vt_latent_policy_bwd(const a3vt_mlp *net, const a3vt_mlp_grads *grads, con
                            const float *first_latent, const float *dvalues, const float *stash, float *delta, int rows, int accumulate,
                            void *stream) {
   const int ld = policy_net_check("latent_policy_bwd", net);
-  if (ld < 0 || !policy_rows_ok("latent_policy_bwd", "rows", rows)) return -1;
+  if (ld < 0 || check_count("latent_policy_bwd", "rows", rows, kPolicyMaxRows)) return -1;
   A3VT_CHECK_ARG(grads && mask && latent && first_latent && dvalues && stash && delta);
   A3VT_CHECK_ARG(aligned_to(mask, 4) && aligned_to(latent, 4) && aligned_to(first_latent, 4) && aligned_to(dvalues, 4) &&
                  aligned_to(stash, 4) && aligned_to(delta, 4));
   PolicyGrads g;
   memcpy(&g, grads, sizeof(g));
-  for (int l = 0; l < net->n_layers; ++l) {
-    if (!g.dw[l] || !g.db[l] || !aligned_to(g.dw[l], 4) || !aligned_to(g.db[l], 4)) {
-      set_error("latent_policy_bwd: layer %d dweight / dbias null or misaligned", l);
-      return -1;
-    }
-  }
-  g_policy_launches[2].fetch_add(2, std::memory_order_relaxed);
+  if (check_grads("latent_policy_bwd", g, net->n_layers)) return -1;
+  g_policy_launches.add(2, 2);
   return launch_policy_bwd(policy_net_of(net), g, mask, latent, first_latent, dvalues, stash, delta, rows, ld, accumulate ? 1 : 0,
                            static_cast<hipStream_t>(stream));
 }
 
-int a3vt_latent_policy_launches(long long *counts, int reset) {
-  for (int i = 0; i < 3; ++i) {
-    if (counts) counts[i] = g_policy_launches[i].load(std::memory_order_relaxed);
-    if (reset) g_policy_launches[i].store(0, std::memory_order_relaxed);
-  }
-  return 3;
-}
+int a3vt_latent_policy_launches(long long *counts, int reset) { return g_policy_launches.read(counts, reset); }
 
 // ---- DDQN's Latent_Model on the same layer table (ddqn_latent.hip) ---------------------------------------------------------------
 namespace {
-std::atomic<long long> g_ddqn_latent_launches[2];
+LaunchCounts<2> g_ddqn_latent_launches;
 
 // The table's rules plus the learner's: transform 0, at most kTdMaxActions outputs -> floats of a stash row, or -1 (message set).
 int ddqn_latent_net_check(const char *who, const a3vt_mlp *net) {
@@ -1704,27 +1650,22 @@ int ddqn_latent_net_check(const char *who, const a3vt_mlp *net) {
   }
   return ld;
 }
-bool ddqn_latent_batch_ok(const char *who, const char *name, int v) {
-  if (v >= 1 && v <= kTdMaxBatch) return true;
-  set_error("%s: %s=%d (1..%d) unsupported", who, name, v, kTdMaxBatch);
-  return false;
-}
 }  // namespace
 
 size_t a3vt_ddqn_latent_scratch_bytes(const a3vt_mlp *online, int batch) {
   const int ld = ddqn_latent_net_check("ddqn_latent_scratch_bytes", online);
-  if (ld < 0 || !ddqn_latent_batch_ok("ddqn_latent_scratch_bytes", "batch", batch)) return 0;
+  if (ld < 0 || check_count("ddqn_latent_scratch_bytes", "batch", batch, kTdMaxBatch)) return 0;
   return (size_t)batch * (2 * (size_t)online->layer[online->n_layers - 1].out + 2 * (size_t)ld) * sizeof(float);
 }
 
 int a3vt_ddqn_latent_q(const a3vt_mlp *net, const float *mask, const float *latent, const float *first_latent, const float *mask_penalty,
                        int rows, float *q, int32_t *action, void *stream) {
-  if (ddqn_latent_net_check("ddqn_latent_q", net) < 0 || !ddqn_latent_batch_ok("ddqn_latent_q", "rows", rows)) return -1;
+  if (ddqn_latent_net_check("ddqn_latent_q", net) < 0 || check_count("ddqn_latent_q", "rows", rows, kTdMaxBatch)) return -1;
   A3VT_CHECK_ARG(mask && latent && first_latent && q);
   A3VT_CHECK_ARG((mask_penalty && action) || (!mask_penalty && !action));
   A3VT_CHECK_ARG(aligned_to(mask, 4) && aligned_to(latent, 4) && aligned_to(first_latent, 4) && aligned_to(mask_penalty, 4) &&
                  aligned_to(q, 4) && aligned_to(action, 4));
-  g_ddqn_latent_launches[0].fetch_add(1, std::memory_order_relaxed);
+  g_ddqn_latent_launches.add(0, 1);
   return launch_ddqn_latent_q(policy_net_of(net), mask, latent, first_latent, mask_penalty, rows, q, action, static_cast<hipStream_t>(stream));
 }
 
@@ -1734,7 +1675,7 @@ int a3vt_ddqn_latent_update(const a3vt_mlp *online, const a3vt_mlp *target_net, 
                             float *q_cur, int32_t *best_next, float *target, float *diff, float *loss, void *scratch, void *stream) {
   const int ld = ddqn_latent_net_check("ddqn_latent_update (online)", online);
   if (ld < 0 || ddqn_latent_net_check("ddqn_latent_update (target)", target_net) < 0 ||
-      !ddqn_latent_batch_ok("ddqn_latent_update", "batch", batch))
+      check_count("ddqn_latent_update", "batch", batch, kTdMaxBatch))
     return -1;
   if (online->n_layers != target_net->n_layers || online->concat_at != target_net->concat_at ||
       online->latent_size != target_net->latent_size) {
@@ -1763,29 +1704,18 @@ int a3vt_ddqn_latent_update(const a3vt_mlp *online, const a3vt_mlp *target_net, 
                  aligned_to(scratch, 4));
   PolicyGrads g;
   memcpy(&g, grads, sizeof(g));
-  for (int l = 0; l < online->n_layers; ++l) {
-    if (!g.dw[l] || !g.db[l] || !aligned_to(g.dw[l], 4) || !aligned_to(g.db[l], 4)) {
-      set_error("ddqn_latent_update: layer %d dweight / dbias null or misaligned", l);
-      return -1;
-    }
-  }
+  if (check_grads("ddqn_latent_update", g, online->n_layers)) return -1;
   DdqnLatentArgs a{};
   a.mask = mask, a.mask_n = mask_n, a.latent = latent, a.latent_n = latent_n, a.first_latent = first_latent;
   a.actions = actions, a.rewards = rewards, a.denom = denom;
   a.batch = batch, a.budget = budget, a.ld = ld, a.gamma = gamma;
   a.q_cur = q_cur, a.diff = diff, a.target = target, a.loss = loss, a.best_next = best_next;
   a.scratch = static_cast<float *>(scratch);
-  g_ddqn_latent_launches[1].fetch_add(3, std::memory_order_relaxed);
+  g_ddqn_latent_launches.add(1, 3);
   return launch_ddqn_latent_update(policy_net_of(online), policy_net_of(target_net), g, a, static_cast<hipStream_t>(stream));
 }
 
-int a3vt_ddqn_latent_launches(long long *counts, int reset) {
-  for (int i = 0; i < 2; ++i) {
-    if (counts) counts[i] = g_ddqn_latent_launches[i].load(std::memory_order_relaxed);
-    if (reset) g_ddqn_latent_launches[i].store(0, std::memory_order_relaxed);
-  }
-  return 2;
-}
+int a3vt_ddqn_latent_launches(long long *counts, int reset) { return g_ddqn_latent_launches.read(counts, reset); }
 
 namespace {
 struct QnetLayout {

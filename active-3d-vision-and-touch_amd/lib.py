@@ -4,7 +4,9 @@ There is deliberately NO fallback: if the shared library is missing or a call fa
 ``RuntimeError`` is raised.  ``build()`` compiles the HIP sources in-tree with hipcc for gfx950.
 """
 import ctypes
+import glob
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,118 +52,50 @@ class MlpGrads(ctypes.Structure):
     _fields_ = [("dweight", _vp * 16), ("dbias", _vp * 16)]
 
 
-# name -> (restype, argtypes); mirrors include/a3vt.h one to one.
-SIGNATURES = {
-    "a3vt_version": (_i, []),
-    "a3vt_last_error": (ctypes.c_char_p, []),
-    "a3vt_csr_validate": (_i, [_vp, _vp, _i, _i]),
-    "a3vt_gcn_stack_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
-    "a3vt_gcn_stack_mask_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "a3vt_gcn_stack_scratch_bytes_mode": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "a3vt_gcn_stack_stash_bytes": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "a3vt_gcn_stack_fwd": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_gcn_stack_bwd": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
-                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_gcn_stack_bwd_acc": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
-                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "a3vt_adj_split_validate": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "a3vt_gcn_stack_fwd_adj": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_gcn_stack_bwd_adj": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i,
-                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "a3vt_gcn_layer_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "a3vt_gcn_layer_fwd": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "a3vt_gcn_layer_bwd": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i,
-                                _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_wt_rows": (_i, [_i]),
-    "a3vt_wt_ld": (_i, [_i]),
-    "a3vt_transpose_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "a3vt_rowgemm": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
-    "a3vt_posenc_param_count": (_sz, [_i]),
-    "a3vt_posenc_scratch_bytes": (_sz, [_i, _i]),
-    "a3vt_posenc_mask_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
-    "a3vt_posenc_mask_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "a3vt_posenc_wide_supported": (_i, [_i]),
-    "a3vt_posenc_wide_acts_bytes": (_sz, [_i, _i]),
-    "a3vt_posenc_wide_scratch_bytes": (_sz, [_i, _i, _i]),
-    "a3vt_posenc_wide_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
-    "a3vt_posenc_wide_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
-    "a3vt_image_pool_fwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "a3vt_image_pool_fwd_add": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "a3vt_image_pool_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
-    "a3vt_bias_grad_scratch_bytes": (_sz, [ctypes.c_longlong, _i]),
-    "a3vt_bias_grad_nhwc": (_i, [_vp, _i, ctypes.c_longlong, _i, _vp, _vp, _sz, _vp]),
-    "a3vt_cast_weights_bf16": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_conv5_supported": (_i, [_i, _i, _i]),
-    "a3vt_conv5_image_bytes": (_sz, [_i, _i, _i]),
-    "a3vt_conv5_weight_image": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "a3vt_conv5_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "a3vt_conv5_input_grad_3x16s2": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "a3vt_conv5_wrw_scratch_bytes": (_sz, [_i, _i]),
-    "a3vt_conv5_weight_grad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "a3vt_conv5f_supported": (_i, [_i, _i, _i]),
-    "a3vt_conv5f_image_bytes": (_sz, [_i, _i]),
-    "a3vt_conv5f_weight_image": (_i, [_vp, _i, _i, _vp, _vp]),
-    "a3vt_conv5f_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
-    "a3vt_adam_chunk_elems": (_i, []),
-    "a3vt_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                       ctypes.c_longlong, _vp]),
-    "a3vt_adam_step_clamp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                             ctypes.c_double, ctypes.c_longlong, ctypes.c_double, _vp]),
-    "a3vt_bnrelu_scratch_bytes": (_sz, [_i]),
-    "a3vt_bnrelu_fwd": (_i, [_vp, ctypes.c_longlong, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "a3vt_bnrelu_bwd": (_i, [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "a3vt_vertex_update": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "a3vt_face_cdf": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "a3vt_sample_points_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _u64, _u64,
-                                    _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_sample_points_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_chamfer_scratch_bytes": (_sz, [_i, _i, _i, _i]),
-    "a3vt_chamfer_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_chamfer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "a3vt_chamfer_fwd_ws": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
-    "a3vt_chamfer_fwd_shared": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
-    "a3vt_chamfer_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_fold_workspace_bytes": (_sz, [_i, _i, _i]),
-    "a3vt_fold_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "a3vt_fold_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "a3vt_ddqn_td": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_ddqn_td_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "a3vt_latent_nearest_scratch_bytes": (_sz, [_i, _i, _i]),
-    "a3vt_latent_nearest": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_latent_nn_tile": (_i, []),
-    "a3vt_latent_nn_query_floats": (_i, []),
-    "a3vt_latent_nn_cached_rows": (_i, []),
-    "a3vt_candidate_tally": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_touch_render": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_touch_finish": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_voxel_surface": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "a3vt_voxel_depth_maps": (_i, [_vp, _i, _i, _vp, _vp]),
-    "a3vt_voxel_points": (_i, [_i, _i, ctypes.c_longlong, _vp, _vp, _vp, _i, _vp, _vp]),
-    "a3vt_voxel_launches": (_i, [_vp, _i]),
-    "a3vt_latent_policy_limit": (_i, [_i]),
-    "a3vt_latent_policy_stash_floats": (_i, [_vp]),
-    "a3vt_latent_policy_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "a3vt_action_value_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "a3vt_latent_policy_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "a3vt_latent_policy_launches": (_i, [_vp, _i]),
-    "a3vt_ddqn_latent_scratch_bytes": (_sz, [_vp, _i]),
-    "a3vt_ddqn_latent_q": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
-    "a3vt_ddqn_latent_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_float,
-                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_ddqn_latent_launches": (_i, [_vp, _i]),
-    "a3vt_qnet_input_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "a3vt_qnet_input_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "a3vt_qnet_input_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i,
-                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "a3vt_dbg_csr_algo": (_i, [_i]),
-    "a3vt_dbg_path_counts": (_i, [_vp, _i, _i]),
-    "a3vt_dbg_nn_work": (_i, [_i, _vp]),
-    "a3vt_split3_bf16": (_i, [_vp, _sz, _vp, _vp, _vp, _vp]),
-    "a3vt_check_finite": (_i, [_vp, _sz, _vp, _vp]),
-    "a3vt_profile_enable": (_i, [_i]),
-    "a3vt_profile_read": (_i, [_vp, _vp]),
-    "a3vt_profile_read_classes": (_i, [_vp, _vp, _i]),
-}
+_SCALARS = {"int": _i, "size_t": _sz, "float": _f, "double": ctypes.c_double, "long long": ctypes.c_longlong, "uint64_t": _u64}
+
+
+def parse_header(text):
+    """``name -> (restype, [argtypes])`` of every prototype ``RET a3vt_name(ARGS);`` in the text of a C header.
+
+    Anything with ``*`` is a ``c_void_p`` (the struct pointers too), a ``const char *`` return a ``c_char_p``; scalars go through
+    ``_SCALARS``.  A declaration outside that raises ``ValueError`` and names it: a binding is never guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)                        # comments
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)                               # preprocessor lines
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{[^{}]*\}\s*\w+\s*;", " ", text)         # the struct definitions
+    text = re.sub(r'extern\s+"C"\s*\{|\}', " ", text)                                  # the extern "C" block's braces
+    sigs = {}
+    for decl in (" ".join(d.split()) for d in text.split(";")):
+        if not decl:
+            continue
+        m = re.fullmatch(r"(.*?)\b(a3vt_\w+) ?\((.*)\)", decl)
+        if m is None:
+            raise ValueError(f"a3vt.h: not a prototype: {decl!r}")
+        ret, name, params = m.groups()
+
+        def ctype(words, what):
+            if words not in _SCALARS:
+                raise ValueError(f"a3vt.h: {name}: no ctypes mapping for {what} in {decl!r}")
+            return _SCALARS[words]
+        if "(" in params or ")" in params or "[" in params:
+            raise ValueError(f"a3vt.h: {name}: cannot split the parameter list of {decl!r}")
+        if "*" in ret:
+            if ret.split() != ["const", "char", "*"]:
+                raise ValueError(f"a3vt.h: {name}: no ctypes mapping for the return type {ret.strip()!r} in {decl!r}")
+            res = ctypes.c_char_p
+        else:
+            res = ctype(ret.strip(), f"the return type {ret.strip()!r}")
+        args = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            words = [w for w in param.split() if w != "const"]          # "TYPE name": every parameter is named
+            args.append(_vp if "*" in param else ctype(" ".join(words[:-1]), f"parameter {param.strip()!r}"))
+        sigs[name] = (res, args)
+    return sigs
+
+
+HEADER = os.path.join(_HERE, "..", "include", "a3vt.h")
+with open(HEADER) as _h:
+    SIGNATURES = parse_header(_h.read())    # at import: tests read the table before load()
 
 _LIB = None
 
@@ -173,8 +107,7 @@ def build(force=False, verbose=False):
 
 def _build(force, verbose, lib_path, objdir):
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "prims.h", "policy_dev.h", "gemm_tile.h")] + \
-        [os.path.join(_HERE, "..", "include", "a3vt.h")]
+    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
     force = force or os.environ.get("A3VT_FORCE_BUILD", "0") not in ("", "0")   # prove on any box that it compiles
     if not force and os.path.exists(lib_path) and all(
             os.path.getmtime(lib_path) >= os.path.getmtime(d) for d in deps if os.path.exists(d)):

@@ -103,6 +103,13 @@ def path_counts(reset=False):
     return dict(zip(PATH_NAMES, (int(x) for x in buf)))
 
 
+def _launch_counts(symbol, names, reset):
+    """One ``a3vt_*_launches(counts, reset)`` hook read into ``{name: count}``."""
+    buf = (ctypes.c_longlong * len(names))()
+    getattr(_lib.load(), symbol)(buf, 1 if reset else 0)
+    return dict(zip(names, (int(x) for x in buf)))
+
+
 def nn_work(enable):
     """Work counters of the pruned nearest-neighbour search (``a3vt_dbg_nn_work``; a test hook, synchronises the device):
     returns what was counted since they were switched on, then switches them on (True: cleared first) or off (False)."""
@@ -1379,9 +1386,7 @@ VOXEL_LIMITS = dict(min_dim=4, max_dim=256, meshes=4096, cells=1 << 30, depth=12
 def voxel_launches(reset=False):
     """Operations ``a3vt_voxel_surface`` / ``a3vt_voxel_depth_maps`` / ``a3vt_voxel_points`` enqueued since the last reset (a test
     hook, as ``policy_launches``)."""
-    buf = (ctypes.c_longlong * 3)()
-    _lib.load().a3vt_voxel_launches(buf, 1 if reset else 0)
-    return dict(zip(("surface", "depth_maps", "points"), (int(x) for x in buf)))
+    return _launch_counts("a3vt_voxel_launches", ("surface", "depth_maps", "points"), reset)
 
 
 def _voxel_check(verts, faces, vert_offset, face_offset, dim):
@@ -1608,9 +1613,7 @@ LATENT_POLICY_MAX = dict(rows=4096, width=1024, layers=16)
 def policy_launches(reset=False):
     """Kernel launches of ``a3vt_latent_policy_fwd`` / ``a3vt_action_value_loss`` / ``a3vt_latent_policy_bwd`` since the last
     reset (a test hook, as ``path_counts``)."""
-    buf = (ctypes.c_longlong * 3)()
-    _lib.load().a3vt_latent_policy_launches(buf, 1 if reset else 0)
-    return dict(zip(("fwd", "loss", "bwd"), (int(x) for x in buf)))
+    return _launch_counts("a3vt_latent_policy_launches", ("fwd", "loss", "bwd"), reset)
 
 
 class PolicyTable:
@@ -1870,9 +1873,7 @@ def action_value_loss(values, actions, targets):
 
 def ddqn_latent_launches(reset=False):
     """Kernel launches of ``a3vt_ddqn_latent_q`` / ``a3vt_ddqn_latent_update`` since the last reset (a test hook)."""
-    buf = (ctypes.c_longlong * 2)()
-    _lib.load().a3vt_ddqn_latent_launches(buf, 1 if reset else 0)
-    return dict(zip(("q", "update"), (int(x) for x in buf)))
+    return _launch_counts("a3vt_ddqn_latent_launches", ("q", "update"), reset)
 
 
 def ddqn_latent_supported(table, mask):

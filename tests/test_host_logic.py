@@ -104,12 +104,20 @@ def test_header_symbols_all_bound_and_exported():
     hdr = open(os.path.join(ROOT, "include", "a3vt.h")).read()
     declared = set(re.findall(r"\b(a3vt_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(lib.SIGNATURES), declared ^ set(lib.SIGNATURES)
+    # one argument type per parameter: counted here by the commas of each prototype, not by the parser under test
+    protos = re.findall(r"\b(a3vt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+    assert {name for name, _ in protos} == declared and len(protos) == len(declared)
+    for name, params in protos:
+        assert len(lib.SIGNATURES[name][1]) == (0 if params.strip() == "void" else params.count(",") + 1), name
     if not os.path.exists(lib.LIB_PATH):
         pytest.skip("library not built (run __graft_entry__.build())")
     dll = ctypes.CDLL(lib.LIB_PATH)
     for name in declared:
         assert hasattr(dll, name), name
     L = lib.load()
+    for name, (res, args) in lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is res and list(fn.argtypes) == args and len(args) == len(fn.argtypes), name
     assert L.a3vt_version() == 163
     assert L.a3vt_posenc_param_count(50) == 12 * 63 + 12 + 25 * 12 + 25 + 50 * 25 + 50 + 200
     assert L.a3vt_wt_rows(300) >= 304 and L.a3vt_wt_ld(300) == 304
@@ -120,6 +128,47 @@ def test_header_symbols_all_bound_and_exported():
     col[2] = 7
     assert L.a3vt_csr_validate(rp.ctypes.data, col.ctypes.data, 2, 3) != 0
     assert b"out of range" in L.a3vt_last_error()
+
+
+def test_signatures_are_derived_from_the_header_type_by_type():
+    """lib.SIGNATURES is parsed from include/a3vt.h: every type spelling of the header maps to the ctypes type stated here."""
+    vp, i, sz, f, d, ll, u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double, ctypes.c_longlong,
+                                ctypes.c_uint64)
+    want = {
+        "a3vt_last_error": (ctypes.c_char_p, []),                                             # const char * return, (void)
+        "a3vt_gcn_stack_stash_bytes": (i, [i] * 6 + [vp, vp]),                                # size_t * is a pointer
+        "a3vt_adam_step": (i, [vp] * 7 + [i] + [d] * 5 + [ll, vp]),                           # void *const *, const long long *, double
+        "a3vt_voxel_points": (i, [i, i, ll, vp, vp, vp, i, vp, vp]),                          # long long by value
+        "a3vt_candidate_tally": (i, [vp] * 4 + [i, i, i, d] + [vp] * 6),
+        "a3vt_touch_render": (i, [vp, i, vp, i, vp, i, vp, vp, vp, i, f, f, f, f] + [vp] * 6),  # float by value
+        "a3vt_bias_grad_scratch_bytes": (sz, [ll, i]),                                        # size_t return
+        "a3vt_check_finite": (i, [vp, sz, vp, vp]),                                           # size_t by value
+        "a3vt_ddqn_latent_scratch_bytes": (sz, [vp, i]),                                      # a struct pointer
+    }
+    for name, (res, args) in want.items():
+        got = lib.SIGNATURES[name]
+        assert got[0] is res and len(got[1]) == len(args) and all(a is b for a, b in zip(got[1], args)), name
+    assert lib.SIGNATURES["a3vt_sample_points_fwd"][1][11:13] == [u64, u64]
+    assert lib.parse_header("/* int a3vt_no(short x); */ int a3vt_yes(const float *x, uint64_t seed /*[2]*/); // int a3vt_no2(void);\n") == \
+        {"a3vt_yes": (i, [vp, u64])}
+
+
+@pytest.mark.parametrize("decl,word", [
+    ("int a3vt_bad(short x);", "short"),                              # a scalar outside the map, as parameter ..
+    ("int a3vt_bad(const float *x, unsigned n);", "unsigned"),
+    ("unsigned a3vt_bad(void);", "unsigned"),                          # .. and as return type
+    ("float *a3vt_bad(void);", "float *"),                             # a pointer return that is no const char *
+    ("int a3vt_bad(int);", "'int'"),                                   # an unnamed parameter: "int" could be its name
+    ("int a3vt_bad(void (*callback)(int, int), int n);", "split"),     # a parameter list that commas do not split
+    ("int a3vt_bad(const float rows[3], int n);", "split"),
+])
+def test_header_parser_refuses_what_it_does_not_understand(decl, word):
+    """A prototype with a type outside the map raises at import and names the function; it never gets a guessed binding."""
+    good = "int a3vt_good(int n);\n"
+    assert lib.parse_header(good) == {"a3vt_good": (ctypes.c_int, [ctypes.c_int])}
+    with pytest.raises(ValueError) as err:
+        lib.parse_header(good + decl + "\n" + good.replace("good", "good2"))
+    assert "a3vt_bad" in str(err.value) and word in str(err.value)
 
 
 def test_no_cpu_fallback():
