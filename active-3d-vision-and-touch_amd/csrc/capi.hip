@@ -1476,6 +1476,103 @@ int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, co
   return launch_touch_finish(depth, cam_pos, cam_rot, I, max_depth, yfov, touch, points, count, status, s);
 }
 
+// ---- mesh and point-cloud rendering (scene_render.hip) -----------------------------------------------------------------------------
+namespace {
+LaunchCounts<2> g_scene_launches;
+
+// One HOST offset table of M + 1 entries against its primitive table of `count` rows.
+int scene_offsets_check(const char *name, const int32_t *offset, int M, int count, const char *table) {
+  if (offset[0] < 0) {
+    set_error("scene_render: %s[0]=%d is below 0", name, (int)offset[0]);
+    return -1;
+  }
+  for (int m = 0; m < M; ++m) {
+    if (offset[m + 1] < offset[m]) {
+      set_error("scene_render: %s[%d]=%d is below %s[%d]=%d: offsets must not decrease", name, m + 1, (int)offset[m + 1], name, m,
+                (int)offset[m]);
+      return -1;
+    }
+  }
+  if (offset[M] > count) {
+    set_error("scene_render: %s[%d]=%d runs past %s=%d", name, M, (int)offset[M], table, count);
+    return -1;
+  }
+  return 0;
+}
+}  // namespace
+
+int a3vt_scene_render(const float *verts, int V, const int32_t *faces, const uint8_t *face_rgb, int F, const float *centres,
+                      const float *radii, const uint8_t *sphere_rgb, int S, const int32_t *face_offset, const int32_t *sphere_offset,
+                      int M, const int32_t *image_scene, const float *cam_pos, const float *cam_rot, int I, float yfov, float znear,
+                      float zfar, int W, int H, const float *lights, int L, float ambient, const uint8_t *background, uint8_t *rgb,
+                      float *depth, int32_t *prim, void *stream) {
+  const char *who = "scene_render";
+  if (check_range(who, "I", I, 1, kSceneMaxImages) || check_range(who, "M", M, 1, kSceneMaxScenes) ||
+      check_range(who, "W", W, 1, kSceneMaxSide) || check_range(who, "H", H, 1, kSceneMaxSide) ||
+      check_range(who, "L", L, 0, kSceneMaxLights) || check_range(who, "V", V, 0, kSceneMaxIndex) ||
+      check_range(who, "F", F, 0, kSceneMaxIndex) || check_range(who, "S", S, 0, kSceneMaxIndex))
+    return -1;
+  if (!(yfov > 0.f && (double)yfov < 3.14159265358979323846)) {
+    set_error("%s: yfov=%g outside (0, pi)", who, (double)yfov);
+    return -1;
+  }
+  if (!(znear > 0.f)) {
+    set_error("%s: znear=%g must be > 0", who, (double)znear);
+    return -1;
+  }
+  if (!(znear < zfar && zfar <= 3.402823466e38f)) {
+    set_error("%s: zfar=%g must be finite and above znear=%g", who, (double)zfar, (double)znear);
+    return -1;
+  }
+  if (!(ambient >= -3.402823466e38f && ambient <= 3.402823466e38f)) {
+    set_error("%s: ambient=%g must be finite", who, (double)ambient);
+    return -1;
+  }
+  if (check_ptrs(who, {{"verts", verts, V > 0, 4, "required when V > 0"},
+                       {"faces", faces, F > 0, 4, "required when F > 0"},
+                       {"face_rgb", face_rgb, F > 0, 1, "required when F > 0"},
+                       {"centres", centres, S > 0, 4, "required when S > 0"},
+                       {"radii", radii, S > 0, 4, "required when S > 0"},
+                       {"sphere_rgb", sphere_rgb, S > 0, 1, "required when S > 0"},
+                       {"face_offset", face_offset, true, 4, "required (a host table)"},
+                       {"sphere_offset", sphere_offset, true, 4, "required (a host table)"},
+                       {"image_scene", image_scene, true, 4, "required (a host table)"},
+                       {"cam_pos", cam_pos, true, 4, "required"},
+                       {"cam_rot", cam_rot, true, 4, "required"},
+                       {"lights", lights, L > 0, 4, "required when L > 0 (a host table)"},
+                       {"background", background, true, 1, "required (a host table)"},
+                       {"rgb", rgb, true, 1, "required"},
+                       {"depth", depth, true, 4, "required"},
+                       {"prim", prim, false, 4, ""}}))
+    return -1;
+  // the host tables' contents
+  if (scene_offsets_check("face_offset", face_offset, M, F, "F") || scene_offsets_check("sphere_offset", sphere_offset, M, S, "S")) return -1;
+  for (int i = 0; i < I; ++i) {
+    if (image_scene[i] < 0 || image_scene[i] >= M) {
+      set_error("%s: image_scene[%d]=%d outside 0..%d", who, i, (int)image_scene[i], M - 1);
+      return -1;
+    }
+  }
+  SceneRange *ranges = static_cast<SceneRange *>(malloc(sizeof(SceneRange) * (size_t)I));
+  if (!ranges) {
+    set_error("%s: no host memory for the ranges of I=%d images", who, I);
+    return -1;
+  }
+  for (int i = 0; i < I; ++i) {
+    const int m = image_scene[i];
+    ranges[i] = {face_offset[m], face_offset[m + 1], sphere_offset[m], sphere_offset[m + 1]};
+  }
+  const int rc = launch_scene_render(verts, V, faces, face_rgb, F, centres, radii, sphere_rgb, ranges, cam_pos, cam_rot, I, yfov, znear,
+                                     zfar, W, H, lights, L, ambient, background, rgb, depth, prim, static_cast<hipStream_t>(stream));
+  free(ranges);
+  if (rc < 0) return rc;
+  g_scene_launches.add(0, 1);
+  g_scene_launches.add(1, rc);
+  return 0;
+}
+
+int a3vt_scene_launches(long long *counts, int reset) { return g_scene_launches.read(counts, reset); }
+
 // ---- the ground-truth point cloud of a batch of meshes (voxel.hip) -----------------------------------------------------------------
 namespace {
 LaunchCounts<3> g_voxel_launches;

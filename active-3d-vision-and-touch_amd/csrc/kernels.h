@@ -402,6 +402,29 @@ int launch_touch_depth(const float *verts, int V, const int32_t *faces, int F, c
 int launch_touch_finish(const float *depth, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float *touch,
                         float *points, int32_t *count, int32_t *status, hipStream_t s);
 
+// scene_render.hip: colour, depth and primitive-index images of triangle + sphere scenes (utility/pretty_render.py's job): a ray
+// cast per pixel with Lambert shading, one launch per kSceneImagesPerLaunch images.  The small tables travel by value in the kernel
+// arguments: the host has checked them, and nothing on the device has to be trusted or clamped.
+constexpr int kSceneChunk = 256;              // primitives culled, and survivors held in LDS, at a time
+constexpr int kSceneMaxSide = 2048, kSceneMaxLights = 8;
+constexpr int kSceneMaxImages = 1 << 16, kSceneMaxScenes = 1 << 20, kSceneMaxIndex = 1 << 28;   // I, M, and V, F and S
+constexpr int kSceneImagesPerLaunch = 128;    // (16 bytes each of the kernel-argument block)
+struct SceneRange {                           // one image's primitives: faces f0 .. f1 - 1, spheres s0 .. s1 - 1
+  int32_t f0, f1, s0, s1;
+};
+struct SceneTables {
+  SceneRange range[kSceneImagesPerLaunch];
+  float light[kSceneMaxLights][4];            // position, intensity
+  int32_t n_lights;
+  float ambient;
+  uint8_t background[4];
+};
+// ranges: I entries on the HOST (resolved from the offsets and image_scene, already checked); lights [L][4] and background [3] too
+int launch_scene_render(const float *verts, int V, const int32_t *faces, const uint8_t *face_rgb, int F, const float *centres,
+                        const float *radii, const uint8_t *sphere_rgb, const SceneRange *ranges, const float *cam_pos,
+                        const float *cam_rot, int I, float yfov, float znear, float zfar, int W, int H, const float *lights, int L,
+                        float ambient, const uint8_t *background, uint8_t *rgb, float *depth, int32_t *prim, hipStream_t s);
+
 // voxel.hip: the ground-truth point cloud of a batch of meshes (utility/data_making.py::extract_points): voxelise by adaptive
 // subdivision, column ranges (the six depth maps), carve + surface, realign + gather.  The launch_* return the number of operations
 // they enqueued (kernels, the clear, the optional copies), or a negative error code with the message set.

@@ -1379,6 +1379,88 @@ def touch_finish(depth, cam_pos, cam_rot, max_depth=TOUCH_DEFAULTS["max_depth"],
     return _touch_result(depth, touch, points, count, status)
 
 
+# The reference's camera, lights and colours (utility/pretty_render.py:35-76, :129): what CameraRenderer starts from.
+RENDER_DEFAULTS = dict(yfov=60.0 / 180.0 * np.pi, znear=0.01, zfar=10.0, width=512, height=512,
+                       cam_pos=(0.0, 0.6, 0.6), cam_euler_xyz_deg=(45.0, 0.0, 180.0),
+                       lights=((0.0, -0.8, 0.3, 1.8), (0.0, 0.8, 0.3, 1.8), (-1.0, 0.0, 1.0, 1.8), (1.0, 0.0, 1.0, 1.8)),
+                       ambient=0.3, colour=(228, 217, 111), background=(255, 255, 255))
+SCENE_LIMITS = dict(side=2048, lights=8)            # csrc/kernels.h's kSceneMaxSide / kSceneMaxLights
+
+
+def scene_launches(reset=False):
+    """``a3vt_scene_render`` calls accepted and kernels launched since the last reset (a test hook, as ``voxel_launches``)."""
+    return _launch_counts("a3vt_scene_launches", ("calls", "kernels"), reset)
+
+
+def _host_table(t, name, dtype, shape):
+    """A small HOST table of ``a3vt_scene_render`` (a sequence, an array or a CPU tensor) as a contiguous NumPy array."""
+    if isinstance(t, torch.Tensor):
+        if t.is_cuda:
+            raise RuntimeError(f"a3vt: scene_render reads `{name}` on the host (it is checked there and travels in the launch's "
+                               "arguments): pass a sequence, an array or a CPU tensor")
+        t = t.numpy()
+    a = np.ascontiguousarray(np.asarray(t), dtype=dtype)
+    if a.ndim != len(shape) or any(want is not None and want != got for want, got in zip(shape, a.shape)):
+        raise ValueError(f"a3vt: scene_render wants {name} of shape {shape}, got {a.shape}")
+    return a
+
+
+def scene_render(verts, faces, face_rgb, centres, radii, sphere_rgb, face_offset, sphere_offset, image_scene, cam_pos, cam_rot,
+                 yfov=RENDER_DEFAULTS["yfov"], znear=RENDER_DEFAULTS["znear"], zfar=RENDER_DEFAULTS["zfar"],
+                 width=RENDER_DEFAULTS["width"], height=RENDER_DEFAULTS["height"], lights=RENDER_DEFAULTS["lights"],
+                 ambient=RENDER_DEFAULTS["ambient"], background=RENDER_DEFAULTS["background"], want_prim=True):
+    """Colour, depth and primitive-index images of I views over M scenes of triangles and spheres (``a3vt_scene_render``,
+    csrc/scene_render.hip: one launch per 128 images on the current stream, no host synchronisation).  Ray casting with Lambert
+    shading under the given lights: NOT pyrender's shader, and never compared with it.
+
+    Device tensors: ``verts`` (V, 3) float32, ``faces`` (F, 3) int32 with global indices, ``face_rgb`` (F, 3) uint8, ``centres``
+    (S, 3) and ``radii`` (S,) float32, ``sphere_rgb`` (S, 3) uint8, ``cam_pos`` (I, 3) and ``cam_rot`` (I, 3, 3) float32 (the pose
+    matrix ``pretty_render.py`` builds; the camera looks down its -z).  Host tables (sequences, arrays or CPU tensors):
+    ``face_offset`` and ``sphere_offset`` (M + 1,), ``image_scene`` (I,), ``lights`` (L, 4) position and intensity, L <= 8,
+    ``background`` (3,).  Returns ``{"rgb": (I, H, W, 3) uint8, "depth": (I, H, W) float32, 0 without a hit}`` and, with
+    ``want_prim``, ``"prim"`` (I, H, W) int32: the face's index, F + the sphere's index, or -1.  The whole contract is in
+    ``include/a3vt.h``."""
+    verts, faces, face_rgb = _req(verts, "verts"), _req(faces, "faces", torch.int32), _req(face_rgb, "face_rgb", torch.uint8)
+    centres, radii, sphere_rgb = _req(centres, "centres"), _req(radii, "radii"), _req(sphere_rgb, "sphere_rgb", torch.uint8)
+    cam_pos, cam_rot = _req(cam_pos, "cam_pos"), _req(cam_rot, "cam_rot")
+    I, F, S = cam_pos.shape[0], faces.shape[0], centres.shape[0]
+    if cam_pos.shape != (I, 3) or cam_rot.shape != (I, 3, 3) or I < 1:
+        raise ValueError(f"a3vt: scene_render wants cam_pos (I, 3) and cam_rot (I, 3, 3), I >= 1, got {tuple(cam_pos.shape)} and "
+                         f"{tuple(cam_rot.shape)}")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.shape != (F, 3) or face_rgb.shape != (F, 3):
+        raise ValueError(f"a3vt: scene_render wants verts (V, 3), faces (F, 3) and face_rgb (F, 3), got {tuple(verts.shape)}, "
+                         f"{tuple(faces.shape)} and {tuple(face_rgb.shape)}")
+    if centres.shape != (S, 3) or radii.shape != (S,) or sphere_rgb.shape != (S, 3):
+        raise ValueError(f"a3vt: scene_render wants centres (S, 3), radii (S,) and sphere_rgb (S, 3), got {tuple(centres.shape)}, "
+                         f"{tuple(radii.shape)} and {tuple(sphere_rgb.shape)}")
+    face_offset = _host_table(face_offset, "face_offset", np.int32, (None,))
+    M = len(face_offset) - 1
+    if M < 1:
+        raise ValueError("a3vt: scene_render wants face_offset (M + 1,), M >= 1")
+    sphere_offset = _host_table(sphere_offset, "sphere_offset", np.int32, (M + 1,))
+    image_scene = _host_table(image_scene, "image_scene", np.int32, (I,))
+    lights = _host_table(np.zeros((0, 4)) if len(lights) == 0 else lights, "lights", np.float32, (None, 4))
+    background = _host_table(background, "background", np.uint8, (3,))
+    W, H = int(width), int(height)
+    if not (1 <= W <= SCENE_LIMITS["side"] and 1 <= H <= SCENE_LIMITS["side"]):      # (before the outputs are sized by them)
+        raise RuntimeError(f"a3vt: scene_render: W={W} H={H} outside 1..{SCENE_LIMITS['side']}")
+    dev = cam_pos.device
+    rgb = torch.empty((I, H, W, 3), dtype=torch.uint8, device=dev)
+    depth = torch.empty((I, H, W), dtype=torch.float32, device=dev)
+    prim = torch.empty((I, H, W), dtype=torch.int32, device=dev) if want_prim else None
+    host = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    _lib.check(_lib.load().a3vt_scene_render(
+        _lib.ptr(verts) if verts.shape[0] else None, verts.shape[0], _lib.ptr(faces) if F else None, _lib.ptr(face_rgb) if F else None, F,
+        _lib.ptr(centres) if S else None, _lib.ptr(radii) if S else None, _lib.ptr(sphere_rgb) if S else None, S, host(face_offset),
+        host(sphere_offset), M, host(image_scene), _lib.ptr(cam_pos), _lib.ptr(cam_rot), I, float(yfov), float(znear), float(zfar), W, H,
+        host(lights), len(lights), float(ambient), host(background), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(prim), _stream()),
+        "scene_render")
+    out = {"rgb": rgb, "depth": depth}
+    if prim is not None:
+        out["prim"] = prim
+    return out
+
+
 # csrc/kernels.h's kVoxelMinDim / kVoxelMaxDim / kVoxelMaxMeshes / kVoxelMaxCells / kVoxelMaxDepth
 VOXEL_LIMITS = dict(min_dim=4, max_dim=256, meshes=4096, cells=1 << 30, depth=12)
 

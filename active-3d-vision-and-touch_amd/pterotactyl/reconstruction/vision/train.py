@@ -17,7 +17,9 @@ overlaps with the rest of the backward), BatchNorm running statistics follow ran
 validation loss and example counts are summed over ranks whatever the loader (``a3vt_amd.distributed``).  Datasets: ``get_loaders`` reads the reference's on-disk
 layout through ``utility/data_loaders.py`` (``args.data_root`` / ``PTEROTACTYL_DATA``; worker count ``args.num_workers``,
 default 16 as the reference); or pass ``loaders=(train_loader, valid_loader)`` (e.g. ``a3vt_amd.synthetic.SyntheticLoader``).
-Batches are uploaded one step ahead on a copy stream (``data_loaders.DevicePrefetcher``).
+Batches are uploaded one step ahead on a copy stream (``data_loaders.DevicePrefetcher``).  With ``args.visualize`` and
+``args.eval``, ``validate`` renders the predictions of its first six batches into ``results_dir`` after the sixth (reference
+:193-198; ``utils.visualize_prediction``, this library's own ray caster, not pyrender), on rank 0; the score keeps its bits.
 """
 import os
 
@@ -173,6 +175,9 @@ class Engine:
         self.encoder.eval()
         num_examples = 0
         dev = self.initial_mesh.device
+        # args.visualize with args.eval: the predictions of the first six batches are rendered (reference :193-198), on rank 0
+        visualize = bool(getattr(self.args, "visualize", False) and self.args.eval and self.rank == 0)
+        observations, names = [], []
         for v, batch in enumerate(data_loaders.DevicePrefetcher(valid_loader, dev)):
             img = batch["img"].to(dev, non_blocking=True)
             gt_points = batch["gt_points"].to(dev, non_blocking=True)
@@ -181,6 +186,12 @@ class Engine:
             loss = utils.chamfer_distance(verts, self.mesh_info["faces_i32"], gt_points, num=self.args.number_points)
             total_loss += self.args.loss_coeff * loss.sum()
             num_examples += float(img.shape[0])
+            if visualize and v <= 5:
+                observations.append(verts.detach())
+                names += [n if isinstance(n, str) else n[0] for n in batch["names"]]
+                if v == 5:
+                    utils.visualize_prediction(self.results_dir, torch.cat(observations, dim=0)[:, :, :3], self.mesh_info["faces"], names)
+                    observations, names = [], []
         if self.world > 1:
             # Always: with a sharded loader the ranks hold disjoint parts of the set; with an injected loader (no
             # ``sampler.plan``) they hold copies of it scored with different surface samples (per-rank seeds) — either way

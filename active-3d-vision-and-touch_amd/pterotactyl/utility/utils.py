@@ -5,7 +5,9 @@ Reference symbols mirrored (file:line under the reference tree):
 ``adj_fuse_touch`` :75-130, ``calc_adj`` :134-148, ``batch_sample`` :152-187, ``load_mesh_touch`` :194-200,
 ``chamfer_distance`` :204-217, ``save_config`` :535-544, ``load_model_config`` :547-553; and, for ``utility/data_making.py``,
 ``save_points`` :220, ``extract_surface`` :228, ``write_obj`` :241, ``scale_points`` :348, ``get_obj_data`` :374, ``mesh_to_voxel``
-:382, ``voxel_to_pointcloud`` :453, ``extract_ODMs`` :471, ``apply_ODMs`` :502, ``realign_points`` :523.
+:382, ``voxel_to_pointcloud`` :453, ``extract_ODMs`` :471, ``apply_ODMs`` :502, ``realign_points`` :523; and, for looking at
+results, ``get_circle`` :257, ``euler2matrix`` :330, ``add_faces`` :338, ``visualize_actions`` :563, ``visualize_prediction`` :657
+(rendered by ``utility/pretty_render.py`` with this library's own ray caster: NOT pyrender's shader, see there).
 
 Differences that callers can see:
 * ``adj_info`` is an :class:`AdjInfo` dict.  It still answers ``['origional']``, ``['adj']`` (dense float tensors,
@@ -19,6 +21,7 @@ This package's own: ``pretrained_root(args)`` (where the reference's pretrained 
 ``SummaryWriter`` (tensorboard's, or a no-op stub where tensorboard is missing).
 """
 import json
+import math
 import os
 import random
 from collections import namedtuple
@@ -300,3 +303,147 @@ def get_obj_data(obj_location, scale=1.0):
     """(verts float32 scaled by ``scale_points``, faces int64) of an OBJ file, read by this package's own reader (``mesh.load_obj``)."""
     verts, faces = _mesh.load_obj(obj_location)
     return scale_points(verts, scale), faces
+
+
+# ---- looking at results (reference :257-285, :330-345, :563-668; the renderer itself is utility/pretty_render.py) ----
+class get_circle(object):
+    """The sphere of actions (reference :257-285): ``points`` (num_points, 3) float32 unit vectors in rings of equal area,
+    ``sphere_points`` their [theta, phi].  Where the rings do not add up to ``num_points`` the reference prints and calls ``exit()``;
+    this raises ``ValueError`` with the same figures."""
+
+    def __init__(self, num_points, rank=0):
+        action_position = []
+        a = 4 * np.pi / float(num_points)
+        d = math.sqrt(a)
+        M_t = round(np.pi / d)
+        d_t = np.pi / M_t
+        d_phi = a / d_t
+        sphere_positions = []
+        for i in range(0, M_t):
+            theta = np.pi * (i + 0.5) / M_t
+            M_phi = round(2 * np.pi * math.sin(theta) / d_phi)
+            for j in range(0, M_phi):
+                phi = 2 * np.pi * j / M_phi
+                sphere_positions.append([theta, phi])
+                action_position.append(self.get_point(theta, phi))
+        if num_points != len(action_position):
+            raise ValueError(f"a3vt: get_circle: we have {len(action_position)} points but want {num_points}")
+        self.points = torch.stack(action_position)
+        self.sphere_points = sphere_positions
+
+    def get_point(self, a, b):
+        return torch.FloatTensor([math.sin(a) * math.cos(b), math.sin(a) * math.sin(b), math.cos(a)])
+
+
+def euler_matrix(angles, xyz="xyz", degrees=False):
+    """SciPy's ``Rotation.from_euler(xyz, angles, degrees).as_matrix()`` for lower-case axis strings, which is all the reference
+    passes: extrinsic rotations, applied in the order written about the fixed axes."""
+    if len(xyz) != len(angles) or set(xyz) - set("xyz"):
+        raise ValueError(f"a3vt: euler_matrix: axes {xyz!r} for {len(angles)} angles (lower-case x, y, z: extrinsic rotations)")
+    out = np.eye(3)
+    for axis, angle in zip(xyz, np.radians(angles) if degrees else angles):
+        c, s = math.cos(angle), math.sin(angle)
+        r = {"x": [[1, 0, 0], [0, c, -s], [0, s, c]], "y": [[c, 0, s], [0, 1, 0], [-s, 0, c]], "z": [[c, -s, 0], [s, c, 0], [0, 0, 1]]}[axis]
+        out = np.array(r, np.float64) @ out
+    return out
+
+
+def euler2matrix(angles=[0, 0, 0], translation=[0, 0, 0], xyz="xyz", degrees=False):
+    """A 4 x 4 pose from Euler angles and a translation (reference :330-335)."""
+    pose = np.eye(4)
+    pose[:3, 3] = translation
+    pose[:3, :3] = euler_matrix(angles, xyz, degrees)
+    return pose
+
+
+def add_faces(faces):
+    """The faces, then (a, c, b) and (c, b, a) of each (reference :338-345): every triangle three times, once per winding and once
+    more, which is how the reference makes its meshes two-sided for pyrender."""
+    faces = np.asarray(faces)
+    f1, f2, f3 = (np.array(faces[:, k]).reshape(-1, 1) for k in range(3))
+    return np.concatenate((faces, np.concatenate((f1, f3, f2), axis=-1), np.concatenate((f3, f2, f1), axis=-1)), axis=0)
+
+
+def _sphere_cell(point, num_actions):
+    """The (row, column) of a unit vector on ``visualize_actions``' (2 num_actions, 4 num_actions) map (reference :573-579)."""
+    x, y, z = (float(v) for v in point)
+    x = math.atan2(-x, y)
+    x = (x + np.pi / 2.0) / (np.pi * 2.0) + np.pi * (28.670 / 360.0)
+    y = math.acos(z) / np.pi
+    return int(y * num_actions * 12 / (2 * np.pi)), int(x * num_actions * 24 / (2 * np.pi))
+
+
+def _seen_points(args):
+    """The points vision sees, for ``visualize_actions`` with ``use_img``: ``args.visible_points``, an ``.obj`` or ``.npy``.  (The
+    reference reads ``objects/visible.obj`` of its own package, which this one does not carry.)"""
+    path = getattr(args, "visible_points", None)
+    if not path or not os.path.exists(path):
+        raise FileNotFoundError(f"a3vt: visualize_actions with use_img needs args.visible_points, the path of an .obj or .npy holding the "
+                                f"points vision sees (the reference's pterotactyl/objects/visible.obj); got {path!r}")
+    points = np.load(path) if path.endswith(".npy") else _mesh.load_obj(path)[0]
+    return np.asarray(points, np.float64).reshape(-1, 3)
+
+
+def sphere_projection(actions, args):
+    """``visualize_actions``' map (reference :571-648) as a (2 num_actions, 4 num_actions, 3) uint8 array: every action's cell, its
+    count on top, scaled to 255; with ``args.use_img`` the region vision sees in orange where nothing was marked, and the share of
+    the policy's actions inside it printed; the rest teal."""
+    n = args.num_actions
+    actions = (actions.detach().reshape(-1).long().cpu().numpy() if isinstance(actions, torch.Tensor)
+               else np.asarray(actions).reshape(-1).astype(np.int64))
+    points = get_circle(n).points.numpy()
+    cells = [_sphere_cell(p, n) for p in points]
+    array = np.zeros([n * 2, n * 4, 3])
+    for x_co, y_co in cells + [cells[a] for a in actions]:
+        for i in range(3):
+            for j in range(3):
+                array[x_co - 1 + i, y_co - 1 + j] += 1.0
+    array = array * 255.0 / array.max()
+    if args.use_img:
+        seen = _seen_points(args)
+        seen = seen / np.sqrt((seen ** 2).sum(axis=1)).reshape(-1, 1)
+        seen_cells = [_sphere_cell(p, n) for p in seen]
+        for x_co, y_co in seen_cells:
+            for i in range(5):
+                for j in range(5):
+                    if array[x_co - 2 + i, y_co - 2 + j].sum() == 0:
+                        array[x_co - 2 + i, y_co - 2 + j] = (255, 127, 80)
+        array[np.all(array == (0, 0, 0), axis=-1)] = (0, 204, 204)
+        check_array = np.zeros([n * 2, n * 4])
+        for x_co, y_co in seen_cells:
+            for i in range(3):
+                for j in range(3):
+                    check_array[x_co - 1 + i, y_co - 1 + j] = 100
+        on = sum(1.0 for a in actions if check_array[cells[a]] > 0)
+        print(f"percentage in vision is {on * 100 / len(actions):.2f} % for policy")
+    else:
+        array[np.all(array == (0, 0, 0), axis=-1)] = (0, 204, 204)
+    return array.astype(np.uint8)
+
+
+def visualize_actions(location, actions, args):
+    """``<location>/histogram.png`` (matplotlib) and ``<location>/sphere_projection.png`` of the actions a policy took (reference
+    :563-649), on the host."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    from PIL import Image
+    flat = actions.detach().reshape(-1).long().cpu().numpy() if isinstance(actions, torch.Tensor) else np.asarray(actions).reshape(-1)
+    plt.hist(flat, bins=np.arange(0, args.num_actions + 1))
+    plt.title("actions histogram")
+    plt.savefig(location + "/histogram.png")
+    plt.close()
+    Image.fromarray(sphere_projection(actions, args)).save(location + "/sphere_projection.png")
+
+
+def visualize_prediction(location, meshes, faces, names):
+    """``mesh.png``, ``points.png`` and ``ground_truth.png`` of every predicted mesh under ``<location>/<name's last part>/``
+    (reference :657-668), all of them rendered by one library call (``pretty_render.render_representations``)."""
+    from . import pretty_render
+    meshes = meshes.detach().cpu().numpy() if isinstance(meshes, torch.Tensor) else np.asarray(meshes)
+    faces = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    locations = []
+    for n in names:
+        locations.append(location + "/" + n.split("/")[-1] + "/")
+        os.makedirs(locations[-1], exist_ok=True)
+    pretty_render.render_representations(locations, names, meshes, faces)

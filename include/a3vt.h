@@ -727,6 +727,70 @@ int a3vt_voxel_points(int M, int dim, long long total, int32_t *surface, float *
 int a3vt_voxel_launches(long long *counts /*[3]*/, int reset);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mesh and point-cloud rendering: what utility/pretty_render.py asks of pyrender, as a ray caster of this library's own.
+ *
+ * THIS IS NOT PYRENDER'S SHADER.  It is ray casting at pixel centres with Lambert shading under the reference's lights and camera.
+ * It is not the metallic-roughness model, and no image of it has been compared with one of pyrender's.
+ *
+ * One call renders I images.  Every image has its own pinhole camera and looks at one of M scenes cut from shared tables.
+ *   verts         [V][3] fp32 and faces [F][3] int32 (indices into verts, already global), face_rgb [F][3] uint8: the triangles
+ *   centres       [S][3] fp32, radii [S] fp32, sphere_rgb [S][3] uint8: the spheres
+ *   face_offset   [M + 1] int32, HOST: scene m owns faces face_offset[m] .. face_offset[m + 1] - 1
+ *   sphere_offset [M + 1] int32, HOST: the same for spheres.  A scene may be empty.
+ *   image_scene   [I] int32, HOST: the scene image i looks at
+ *   cam_pos       [I][3], cam_rot [I][3][3] fp32: the camera's pose matrix as pretty_render.py builds it.  The camera looks down its
+ *                 own -z; no R_y(-90 deg) is applied (unlike a3vt_touch_render's finger frame).
+ *   yfov (radians), znear, zfar, W, H: the aspect ratio is W / H
+ *   lights        [L][4] fp32, HOST: position (world) and intensity; ambient; background [3] uint8, HOST
+ *   rgb           [I][H][W][3] uint8 out
+ *   depth         [I][H][W] fp32 out: 0 without a hit
+ *   prim          [I][H][W] int32 out, or NULL: the face's index, F + the sphere's index, -1 without a hit (indices into the tables)
+ * The HOST tables are small; they are read and checked during the call and travel in the kernel arguments, which is what lets the
+ * call refuse a bad table before anything is launched and without reading the device.  Everything else is device memory.
+ *
+ * Visibility.
+ * - Pixel (r, c), row 0 at the top, has the centre x = (c + 0.5) / W * 2 - 1, y = 1 - (r + 0.5) / H * 2 and the ray
+ *   (x tan(yfov / 2) W / H, y tan(yfov / 2), -1) in the eye frame, as in the touch contract.
+ * - depth is the ray parameter (= -z in the eye frame) of the nearest hit with znear <= depth <= zfar.
+ * - Triangles are two-sided and inclusive on edges.  Across an edge that two faces share BY VERTEX INDEX the test is watertight
+ *   (a3vt_touch_render's rule, restated in csrc/scene_render.hip).
+ * - A sphere of centre c and radius r is hit, with oc = c - o and the unit ray u, at b - sqrt(disc), b = oc . u,
+ *   disc = r^2 - |oc - b u|^2 >= 0; a ray that starts inside a sphere does not hit it (its only hit lies behind it or is the far one).
+ * - Among hits of exactly equal depth the lowest prim wins, so the output does not depend on chunking or order of evaluation.
+ *   A face's depth is computed from its vertices in the order of their indices: copies of a face under another winding or
+ *   rotation (add_faces' (a, c, b) and (c, b, a)) have exactly the depth of the original, and the first of them is seen.
+ * - A face with a non-finite coordinate, a sphere with a non-finite centre or radius or with radius <= 0, is never hit and changes
+ *   nothing else.  A face with an index outside [0, V) is skipped: this is checked on the device, as a3vt_touch_render does.
+ *
+ * Shading, in fp32, of the hit point p.
+ * - n is the unit face normal turned towards the eye, or (p - c) / r on a sphere.
+ * - out = clip(base * (ambient + (1 / pi) sum_k I_k max(0, n . l_k / |l_k|) / |l_k|^2), 0, 255) per channel, l_k = L_k - p, the sum
+ *   in table order, rounded half up.  No shadows, no specular term, no vertex normals, no blending.  A pixel without a hit gets
+ *   the background.
+ *
+ * One launch per 128 images (a reference-sized job, 16 objects of 3 images, is one), on `stream`; a workgroup takes a 16 x 16 tile.
+ * No allocation, no host synchronisation, no atomics, every float sum in a fixed order: the same bits on every call, and an
+ * image does not depend on what else is in the batch.
+ * a3vt_scene_launches: since the last reset, [0] the a3vt_scene_render calls that were accepted, [1] the kernels they launched;
+ * returns 2.
+ *
+ * Limits.
+ * - 1 <= I <= 65536, 1 <= M <= 1048576, 1 <= W, H <= 2048, 0 <= L <= 8, 0 <= V, F, S <= 268435456.
+ * - verts and centres / radii may be NULL when V == 0 or S == 0, faces and face_rgb when F == 0, sphere_rgb when S == 0, lights when
+ *   L == 0.
+ * - 0 < znear < zfar < infinity; 0 < yfov < pi; ambient finite.
+ * - face_offset and sphere_offset start at >= 0, do not decrease and end at <= F and <= S; image_scene[i] lies in [0, M).
+ * - Pointers to fp32 and int32 are 4-byte aligned; the byte tables need no alignment.
+ * - Anything else, or a missing required pointer, returns non-zero with a message in a3vt_last_error that names the argument and
+ *   its value.  Nothing is launched. */
+int a3vt_scene_render(const float *verts, int V, const int32_t *faces, const uint8_t *face_rgb, int F, const float *centres,
+                      const float *radii, const uint8_t *sphere_rgb, int S, const int32_t *face_offset, const int32_t *sphere_offset,
+                      int M, const int32_t *image_scene, const float *cam_pos, const float *cam_rot, int I, float yfov, float znear,
+                      float zfar, int W, int H, const float *lights, int L, float ambient, const uint8_t *background, uint8_t *rgb,
+                      float *depth, int32_t *prim, void *stream);
+int a3vt_scene_launches(long long *counts /*[2]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The supervised latent policy's value network (policies/supervised/model.py, train.py:119-158), fp32 throughout.
  *
  * The network is a table of at most 16 layers, read on the host and passed to the kernels by value.  Layer l computes
