@@ -73,6 +73,7 @@ enum PathCount {
   PATH_QNET_BWD,         // a3vt_qnet_input_bwd calls
   PATH_FOLD_FWD,         // a3vt_fold_fwd calls (fold.hip: one FoldingNet fold, forward)
   PATH_FOLD_BWD,         // a3vt_fold_bwd calls
+  PATH_CSR3_SPLIT,       // csr3s_kernel launches (the 3-channel output aggregation through the P + bipartite split, either direction)
   PATH_COUNT
 };
 void path_count(int which);

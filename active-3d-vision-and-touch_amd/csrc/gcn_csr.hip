@@ -563,6 +563,7 @@ int launch_csr3(const float *z, const float *bias, const int32_t *rowptr, const 
   if (sp && (size_t)n_vert * 16 <= 60 * 1024) {
     int parts = 512 / batch;   // ~two workgroups per CU
     parts = parts < 1 ? 1 : parts > 8 ? 8 : parts;
+    path_count(PATH_CSR3_SPLIT);
     if (transposed)
       A3VT_LAUNCH(csr3s_kernel<true>, dim3(batch * parts), dim3(256), (size_t)n_vert * 16, s, z, bias, sp->rowptr, sp->col,
                   sp->scale, sp->cls, n_vert, parts, out, ldo);

@@ -91,7 +91,7 @@ GEMM_MODES = {"fp32": 0, "bf16": 1, "bf16s": 2, "fp32x3": 3}
 
 
 PATH_NAMES = ("stack_quad", "stack_rows", "rowgemm_adirect", "rowgemm3", "dw3", "dw_hybrid", "rowgemm16", "stack16_quad", "rowgemm_w", "dw_w", "stack_split", "csr16_tiles",
-              "qnet_input_fwd", "qnet_input_bwd", "fold_fwd", "fold_bwd")
+              "qnet_input_fwd", "qnet_input_bwd", "fold_fwd", "fold_bwd", "csr3_split")
 
 
 def path_counts(reset=False):

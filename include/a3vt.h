@@ -465,6 +465,7 @@ int a3vt_dbg_csr_algo(int algo);
  *   [10] stack forward calls that aggregated through the P + bipartite split (struct a3vt_adj_split)
  *   [11] csr16t forward launches (bf16 storage: aggregation from LDS tiles)
  *   [12] a3vt_qnet_input_fwd calls  [13] a3vt_qnet_input_bwd calls  [14] a3vt_fold_fwd calls  [15] a3vt_fold_bwd calls
+ *   [16] csr3s_kernel launches (the 3-channel output-layer aggregation through the split, forward or transposed)
  * Returns the number of counters the library keeps (entries beyond it are written as 0); reset != 0 clears them. */
 int a3vt_dbg_path_counts(long long *counts, int n, int reset);
 

@@ -90,7 +90,9 @@ def test_k2_lattice_with_a_gradient_is_refused():
 
 def test_path_counters_are_appended(L):
     from a3vt_amd import ops
-    assert ops.PATH_NAMES[-2:] == ("fold_fwd", "fold_bwd") and ops.PATH_NAMES[:2] == ("stack_quad", "stack_rows")
+    # every counter keeps its index: the fold counters at 14 and 15, later ones (csr3_split) behind them
+    assert ops.PATH_NAMES[14:16] == ("fold_fwd", "fold_bwd") and ops.PATH_NAMES[:2] == ("stack_quad", "stack_rows")
+    assert ops.PATH_NAMES[16:] == ("csr3_split",)
     buf = (ctypes.c_longlong * len(ops.PATH_NAMES))()
     assert L.a3vt_dbg_path_counts(buf, len(ops.PATH_NAMES), 0) == len(ops.PATH_NAMES)
     assert L.a3vt_version() == 163

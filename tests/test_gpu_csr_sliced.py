@@ -2,7 +2,12 @@
 adjacency products of reconstruction/vision/model.py:356,360 for the hidden layers of a stack) against (i) the
 half-wave-per-vertex kernels it replaces — bit for bit, the summation order per element is the same — and (ii) the fp64
 oracle, on shapes that take the new path (>= 12 288 rows, hidden 300): plain icospheres, the reference atlas, and the
-fused vision + touch graph whose hub rows (~1150 neighbours) go through ``csrq_heavy_kernel``."""
+fused vision + touch graph whose hub rows (~1150 neighbours) go through ``csrq_heavy_kernel``.
+
+``test_split_aggregation_against_oracle_and_row_kernels`` is the gate of the P + bipartite split kernels (csrc/gcn_csrqs.hip,
+``csr3s_kernel``) for the REAL values 1 / row length, which are no powers of two: the real atlas, a tolerance on the whole
+three-stage result.  Their bit-exact, per-element gate — class membership, slot pairs, parts, vertices per thread, meshes
+smaller than the workgroup, on values 1/2 and 1/4 — is tests/test_gpu_gcn_exact.py (``test_split_*``)."""
 import pytest
 import torch
 

@@ -11,9 +11,22 @@ pre-activations are exact, some 7 % of them are exactly 0, and ``relu'(0) = 0`` 
 
 Each case asserts through ``ops.path_counts`` that it reached the kernels it names, and prints its worst share of 2^24.
 
-Not covered here: the P + bipartite split kernels (csrc/gcn_csrqs.hip) need row-normalised values, whose hub rows carry 2^-7
-or finer — two such aggregations use up the 24 bits; they keep tests/test_gpu_csr_sliced.py.  The bf16 modes have their own
-rounding-exact gate (tests/test_gpu_bf16_exact.py).
+The P + bipartite split kernels (csrc/gcn_csrqs.hip: ``csrqs_kernel<MODE, VPT>`` and ``csrqs_image_kernel``; csrc/gcn_csr.hip:
+``csr3s_kernel<TRANSPOSED>``) are held to the same gate by the ``test_split_*`` cases.  They never compute 1 / row length: they
+take ``a3vt_adj_split.scale`` as data, and ``a3vt_adj_split_validate`` asks only that every value of row i of the full CSR is
+``scale[i]``.  So the graph is ``diag(s) (P + J)`` with s in {1/2, 1/4} (graph "s" of tests/gcn_exact_util.py, built by physical
+vertex index: where a vertex sits in the 512-thread workgroup is the point) — not row-normalised, on purpose — and each case
+installs the validated split on its ``ops.DeviceCSR`` itself.  Shapes: four and six vertices per thread, a last slot of four
+vertices with vertex n-1 (the one threads past the mesh's end copy) in S and in C, 16 / 10 (uneven) / 25 (clamped) / 3 / 1
+parts, a mesh smaller than the workgroup, batches that are and are not multiples of 8, cut_len 12, 99, 128 and 132 (not
+taken), forward only, csr3s_kernel alone below the hybrid threshold and its LDS limit, the plain CSR and the forced row
+kernels on the same inputs, and batch invariance.  ``csr3_split`` counts the csr3s_kernel launches.
+
+Not covered here: gemm mode ``fp32x3`` on the split graph.  Its dW condition (|dZ| of the hidden layers at most 255 quanta)
+is out of reach with class sums of some 250 terms (~1000 quanta on sparse inputs), and the mode aggregates with the same
+csrqs_kernel as fp32.  The real 1 / row length values of the fused vision + touch matrix, which are no powers of two, keep
+tests/test_gpu_csr_sliced.py.  The bf16 modes (the bf16-storage split walk included) have their own rounding-exact gate
+(tests/test_gpu_bf16_exact.py).
 """
 import ctypes
 
@@ -53,11 +66,13 @@ def _precondition(c):
     return worst, s.worst_name
 
 
-def _run(cuda, p, adj, mode=False):
-    """One forward (+ backward) of ``ops.gcn_stack`` on a lattice problem.  Returns (out, grad_feats, dWs, dbs, path counts)."""
+def _run(cuda, p, adj, mode=False, feats=None, gup=None):
+    """One forward (+ backward) of ``ops.gcn_stack`` on a lattice problem (``feats``, ``gup``: other meshes than the problem's
+    own, same weights).  Returns (out, grad_feats, dWs, dbs, path counts)."""
     from a3vt_amd import ops
     c = p.case
-    fd = torch.nn.functional.pad(p.feats, (0, 2)).to(cuda).requires_grad_(c.backward)
+    feats, gup = p.feats if feats is None else feats, p.grad_update if gup is None else gup
+    fd = torch.nn.functional.pad(feats, (0, 2)).to(cuda).requires_grad_(c.backward)
     ws = [w.to(cuda).requires_grad_(c.backward) for w in p.weights]
     bs = [b.to(cuda).requires_grad_(c.backward) for b in p.biases]
     ops.path_counts(reset=True)
@@ -67,7 +82,7 @@ def _run(cuda, p, adj, mode=False):
         torch.cuda.synchronize()
         return out, None, None, None, ops.path_counts()
     out = ops.gcn_stack(fd, adj, gx.IN_FEATURES, c.hidden, p.cut_len, ws, bs, bf16=mode)
-    (out * p.grad_update.to(cuda)).sum().backward()
+    (out * gup.to(cuda)).sum().backward()
     torch.cuda.synchronize()
     return out.detach(), fd.grad, [w.grad for w in ws], [b.grad for b in bs], ops.path_counts()
 
@@ -212,6 +227,139 @@ def test_backward_accumulates_exactly(cuda):
     for i in range(c.layers):
         _same(gw[i], pre_w[i] + 2 * ref.dws[i], f"accumulated dW{i}")
         _same(gb[i], pre_b[i] + 2 * ref.dbs[i], f"accumulated db{i}")
+
+
+# ---- the P + bipartite split: csrqs_kernel<MODE, VPT>, csrqs_image_kernel (csrc/gcn_csrqs.hip) and csr3s_kernel<TRANSPOSED> --------
+
+def _device_adj_split(cuda, g):
+    """``ops.DeviceCSR`` of the full CSR of a split graph, with the split installed the way ``DeviceCSR.__init__`` does it:
+    proven against the CSR by the library first.  ``CSRAdjacency.split()`` itself does not find it — the values are powers of
+    two, not 1 / row length (tests/test_gcn_exact_host.py)."""
+    from a3vt_amd import lib as _lib, mesh as amesh
+    adj = _device_adj(cuda, g)
+    assert adj.split is None and adj.split_struct is None and adj.max_degree > 8
+    sp = gx.split_arrays(g)
+    host = adj.host
+    _lib.check(_lib.load().a3vt_adj_split_validate(host.rowptr.ctypes.data, host.col.ctypes.data, host.val.ctypes.data, host.n,
+                                                   sp.p_rowptr.ctypes.data, sp.p_col.ctypes.data, sp.scale.ctypes.data,
+                                                   sp.cls.ctypes.data), "adj_split_validate")
+    hs = amesh.SplitAdjacency(sp.p_rowptr, sp.p_col, sp.scale, sp.cls)
+    assert hs.max_degree <= 12 and hs.n_centre == 4
+    adj.split = tuple(torch.from_numpy(a).to(cuda) for a in (hs.rowptr, hs.col, hs.scale, hs.cls))
+    adj.split_struct = _lib.AdjSplit(*[t.data_ptr() for t in adj.split], hs.max_degree, hs.n_seam, hs.n_centre)
+    return adj
+
+
+def _split_case(cuda, name, counts, algo="auto", use_split=True, more_meshes=0):
+    """Run one case of ``gx.SPLIT_CASES`` and compare everything bit for bit; ``counts``: the path counters of the call, exactly.
+    ``more_meshes``: the batch grows by copies of the first meshes with a zero ``grad_update`` — the reference stays the
+    case's own (they add exact zeros to dW and db), the launch gets other ``parts`` and other workgroups."""
+    from a3vt_amd import ops
+    c = gx.SPLIT_CASES[name]
+    worst, where = _precondition(c)
+    p = gx.problem(c)
+    adj = _device_adj_split(cuda, p.graph)
+    adj.use_split = use_split
+    feats = torch.cat((p.feats, p.feats[:more_meshes]))
+    gup = torch.cat((p.grad_update, torch.zeros_like(p.grad_update[:more_meshes])))
+    ops.dbg_csr_algo(algo)
+    try:
+        res = _run(cuda, p, adj, feats=feats, gup=gup)
+    finally:
+        ops.dbg_csr_algo("auto")
+    paths = res[-1]
+    what = f"{name}/{algo}/{'split' if use_split else 'plain'}/+{more_meshes}"
+    print(f"\n{what}: {feats.shape[0] * c.n} rows, cut_len {p.cut_len}, worst sum {where} at {worst:.3f} of 2^24; paths "
+          f"{ {k: v for k, v in paths.items() if v} }")
+    for k, v in counts.items():
+        assert paths[k] == v, (what, k, paths)
+    out, gf, dws, dbs, _ = res
+    if more_meshes:
+        ref = gx.reference(c)
+        _same(out[c.batch:], ref.out[:more_meshes], f"{what}: output of the further meshes")
+        if c.backward:
+            assert (gf[c.batch:] == 0).all(), f"{what}: grad_feats of the further meshes"
+            gf = gf[:c.batch]
+        out = out[:c.batch]
+    _compare(p, (out, gf, dws, dbs, paths), what)
+    return paths
+
+
+# hidden layers on csrqs_kernel (forward and backward), the output layer both ways on csr3s_kernel
+_ALL_SPLIT = dict(stack_split=1, stack_quad=1, stack_rows=0, csr3_split=2)
+
+
+@pytest.mark.parametrize("name", ["split_last_in_s", "split_last_in_c"])
+def test_split_four_vertices_per_thread(cuda, name):
+    """n = 1028, batch 12, cut_len 99: VPT 4, the third per-thread slot holds four live vertices (a centre or two among
+    them) and the fourth none, so threads 4 .. 511 of slot 2 and all of slot 3 copy vertex n-1 — a member of S in one variant,
+    a centre in the other: they must add nothing to its class sum.  16 parts of one or two quads; the tail quad carries a
+    pass-through channel; wave 0 of slot 0 walks one slot pair, others six."""
+    _split_case(cuda, name, _ALL_SPLIT)
+
+
+def test_split_uneven_parts(cuda):
+    """n = 516, batch 24 (a multiple of 8): 10 parts over 25 quads, two or three quads each; slot 1 holds four vertices."""
+    _split_case(cuda, "split_uneven_parts", _ALL_SPLIT)
+
+
+def test_split_mesh_smaller_than_the_workgroup(cuda):
+    """n = 96, batch 136: 416 of the 512 threads own no vertex; ``parts == 1``, so one workgroup parks and walks all 25
+    quads through the double buffer; 136 = 17 x 8 meshes over the XCD groups."""
+    _split_case(cuda, "split_small_mesh", _ALL_SPLIT)
+
+
+def test_split_six_vertices_per_thread(cuda):
+    """n = 2564, batch 5: VPT 6, slot 5 holds four vertices (vertex n-1 a centre); ``parts`` clamped to one quad each; the
+    workgroups of meshes 5 .. 7 of the XCD group exit."""
+    _split_case(cuda, "split_six_per_thread", _ALL_SPLIT)
+
+
+@pytest.mark.parametrize("name", ["split_cut_12", "split_cut_128"])
+def test_split_other_cuts(cuda, name):
+    """cut_len 12 (three quads, no tail quad, 16 parts clamped to 3) and 128 (the widest the split kernels take)."""
+    assert gx.problem(gx.SPLIT_CASES[name]).cut_len == int(name.rsplit("_", 1)[1])
+    _split_case(cuda, name, _ALL_SPLIT)
+
+
+def test_split_not_taken_past_128_channels(cuda):
+    """cut_len 132: csrqs_fits says no, the hidden layers fall back to the row kernels on the full CSR (hub rows on the heavy
+    pass) — exact as well; the output layer keeps csr3s_kernel."""
+    assert gx.problem(gx.SPLIT_CASES["split_cut_132"]).cut_len == 132
+    _split_case(cuda, "split_cut_132", dict(stack_split=0, stack_quad=0, stack_rows=1, csr3_split=2))
+
+
+def test_split_forward_only(cuda):
+    """``torch.no_grad()``: the null sign array of csrqs_kernel<0>; ordinary densities."""
+    _split_case(cuda, "split_forward_only", dict(stack_split=1, stack_quad=1, stack_rows=0, csr3_split=1))
+
+
+def test_split_below_the_hybrid_threshold(cuda):
+    """780 rows: the hidden layers on the row kernels (full CSR); the output layer and its transposed backward on
+    csr3s_kernel with ``parts = 8`` over 260 vertices, which 8 does not divide."""
+    _split_case(cuda, "split_below_threshold", dict(stack_split=0, stack_quad=0, stack_rows=1, csr3_split=2))
+
+
+def test_split_mesh_past_the_lds_of_csr3s(cuda):
+    """n = 3844: 3844 x 16 bytes are more than the 60 KB csr3s_kernel is given, so csr3_kernel + csr3_heavy_kernel must be
+    what runs (and the hidden layers are past the six vertices per thread of csrqs_kernel)."""
+    _split_case(cuda, "split_past_lds", dict(stack_split=0, stack_quad=0, stack_rows=1, csr3_split=0))
+
+
+@pytest.mark.parametrize("algo,use_split,counts", [
+    ("auto", False, dict(stack_split=0, stack_quad=0, stack_rows=1, csr3_split=0)),     # the plain CSR everywhere
+    ("rows", True, dict(stack_split=0, stack_quad=0, stack_rows=1, csr3_split=2)),      # row kernels; csr3s for the output layer
+    ("rows", False, dict(stack_split=0, stack_quad=0, stack_rows=1, csr3_split=0))])
+def test_split_and_plain_aggregation_agree_on_the_reference(cuda, algo, use_split, counts):
+    """The first shape again without the split and on the forced row kernels: the same fp64 reference, bit for bit, as
+    test_split_four_vertices_per_thread — so the split path and the plain path equal each other too."""
+    _split_case(cuda, "split_last_in_s", counts, algo=algo, use_split=use_split)
+
+
+def test_split_is_batch_invariant(cuda):
+    """The 12 meshes of the first shape inside a batch of 20 (10 parts instead of 16, 24 mesh slots instead of 16): the same
+    bits for them, whatever the workgroup and the part that computes them."""
+    _split_case(cuda, "split_last_in_s", _ALL_SPLIT, more_meshes=8)
 
 
 @pytest.mark.parametrize("name", list(gx.LAYER_CASES))
