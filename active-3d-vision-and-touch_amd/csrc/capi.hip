@@ -1,6 +1,7 @@
 // capi.hip — extern "C" entry points declared in include/a3vt.h, plus the GCN stack orchestration
 // (the layer loop of reconstruction/vision/model.py:316-331 lives here so that Python makes one call
 // per refinement stage and nothing syncs the host).
+#include <limits.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1418,6 +1419,41 @@ int a3vt_candidate_tally(const float *scores, const int32_t *candidates, const f
   return launch_candidate_tally(scores, candidates, first_score, taken, K, E, A, unvisited, sums, checks, votes, best, best_score,
                                 static_cast<hipStream_t>(stream));
 }
+
+// ---- the candidate inputs of a greedy step from the per-episode touch table (touch_assemble.hip) ---------------------------------
+namespace {
+LaunchCounts<1> g_touch_assemble_launches;
+}  // namespace
+
+int a3vt_touch_assemble(const float *table_charts, const int32_t *table_codes, const float *state_charts, const float *state_masks,
+                        const int32_t *candidates, int K, int E, int A, int F, int G, int C, int slot, float *charts, float *masks,
+                        void *stream) {
+  const char *who = "touch_assemble";
+  if (check_range(who, "K", K, 1, INT_MAX) || check_range(who, "E", E, 1, INT_MAX) || check_range(who, "A", A, 1, INT_MAX) ||
+      check_range(who, "F", F, 1, INT_MAX) || check_range(who, "G", G, 1, INT_MAX) || check_range(who, "C", C, 1, INT_MAX) ||
+      check_range(who, "slot", slot, 0, G - 1))
+    return -1;
+  const double floats = 3.0 * K * E * F * G * C;   // (six factors below 2^31 each: exact in a double wherever it decides)
+  if (floats >= 2147483648.0) {
+    set_error("%s: K*E*F*G*C*3=%.0f (K=%d E=%d F=%d G=%d C=%d) is not below 2147483648", who, floats, K, E, F, G, C);
+    return -1;
+  }
+  if (check_ptrs(who, {{"table_charts", table_charts, true, 4, "required"},
+                       {"table_codes", table_codes, true, 4, "required"},
+                       {"state_charts", state_charts, true, 4, "required"},
+                       {"state_masks", state_masks, true, 4, "required"},
+                       {"candidates", candidates, true, 4, "required"},
+                       {"charts", charts, true, 4, "required"},
+                       {"masks", masks, true, 4, "required"}}))
+    return -1;
+  if (int rc = launch_touch_assemble(table_charts, table_codes, state_charts, state_masks, candidates, K, E, A, F, G, C, slot, charts, masks,
+                                     static_cast<hipStream_t>(stream)))
+    return rc;
+  g_touch_assemble_launches.add(0, 1);
+  return 0;
+}
+
+int a3vt_touch_assemble_launches(long long *counts, int reset) { return g_touch_assemble_launches.read(counts, reset); }
 
 // ---- the rendered touch sampler (touch_render.hip) ---------------------------------------------------------------------------------
 namespace {

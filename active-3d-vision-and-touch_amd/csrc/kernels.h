@@ -391,6 +391,11 @@ int launch_candidate_tally(const float *scores, const int32_t *candidates, const
                            int A, double unvisited, double *sums, double *checks, double *votes, int32_t *best, float *best_score,
                            hipStream_t s);
 
+// touch_assemble.hip: the K * E candidate chart and mask tensors of a greedy step from the per-episode touch table — one launch
+int launch_touch_assemble(const float *table_charts, const int32_t *table_codes, const float *state_charts, const float *state_masks,
+                          const int32_t *candidates, int K, int E, int A, int F, int G, int C, int slot, float *charts, float *masks,
+                          hipStream_t s);
+
 // touch_render.hip: the rendered touch sampler (simulator/scene/instance.py:121-258) — a ray-cast depth map per finger view, then
 // status, gel image and contact points from it: two launches for a batch of views
 constexpr int kTouchRes = 121;            // the reference's point grid hard-codes it (instance.py:172-184)

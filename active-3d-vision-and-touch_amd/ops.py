@@ -1307,7 +1307,81 @@ def _candidate_tally_launch(scores, candidates, first_score, taken, sums, checks
     return best, best_score
 
 
-TOUCH_RES = 121                                     # csrc/kernels.h's kTouchRes
+def touch_assemble_launches(reset=False):
+    """``a3vt_touch_assemble`` calls that launched since the last reset (a test hook, as ``voxel_launches``)."""
+    return _launch_counts("a3vt_touch_assemble_launches", ("calls",), reset)
+
+
+def touch_assemble(table_charts, table_codes, state_charts, state_masks, candidates, slot):
+    """The touch charts and masks of K candidate action lists from the per-episode touch table, candidate-major, in the layout the
+    reconstructor takes -> ``(charts (K, E, F * G * C, 3), masks (K, E, F * G * C, 1))``.  ``table_charts`` (E, A, F, C, 3)
+    float32 and ``table_codes`` (E, A, F) int32 (2 = "touch", 1 = "no_touch", 0 = no contact: ``scoring.touch_slots``' codes);
+    ``state_charts`` (E, F, G, C, 3) and ``state_masks`` (E, F, G, C, 1) or (E, F, G, C): the episode's touch state, left as it
+    is; ``candidates`` (K, E): the action candidate k tries on element e.  Every block of the outputs is the state's, except
+    grasp slot ``slot``, which holds the table's chart of the candidate's action and its code as a float.  Values move as bits.
+    The whole contract is in ``include/a3vt.h``.  GPU tensors run ``a3vt_touch_assemble`` (csrc/touch_assemble.hip: one launch,
+    no host synchronisation); CPU tensors take the same contract from torch indexing.
+
+    ``candidates`` as a host sequence, array or CPU tensor is checked against ``[0, A)`` (``ValueError``) and uploaded once.  A
+    GPU int32 tensor is not read back: the kernel gives an action outside ``[0, A)`` a zero chart and mask 0."""
+    for t, name, dtype in ((table_charts, "table_charts", torch.float32), (table_codes, "table_codes", torch.int32),
+                           (state_charts, "state_charts", torch.float32), (state_masks, "state_masks", torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"a3vt: touch_assemble `{name}` must be a {dtype} tensor, got "
+                             f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.device != table_charts.device:
+            raise ValueError(f"a3vt: touch_assemble `{name}` is on {t.device}, the table on {table_charts.device}")
+    if table_charts.dim() != 5 or table_charts.shape[4] != 3 or min(table_charts.shape) < 1:
+        raise ValueError(f"a3vt: touch_assemble wants table_charts (E, A, F, C, 3), got {tuple(table_charts.shape)}")
+    E, A, F, C, _ = table_charts.shape
+    if table_codes.shape != (E, A, F):
+        raise ValueError(f"a3vt: touch_assemble wants table_codes ({E}, {A}, {F}), got {tuple(table_codes.shape)}")
+    if state_charts.dim() != 5 or state_charts.shape[2] < 1 or state_charts.shape != (E, F, state_charts.shape[2], C, 3):
+        raise ValueError(f"a3vt: touch_assemble wants state_charts ({E}, {F}, G, {C}, 3), got {tuple(state_charts.shape)}")
+    G = state_charts.shape[2]
+    if tuple(state_masks.shape) not in ((E, F, G, C), (E, F, G, C, 1)):
+        raise ValueError(f"a3vt: touch_assemble wants state_masks ({E}, {F}, {G}, {C}, 1), got {tuple(state_masks.shape)}")
+    slot = int(slot)
+    if not 0 <= slot < G:
+        raise ValueError(f"a3vt: touch_assemble: slot={slot} outside [0, {G})")
+    dev = table_charts.device
+    if isinstance(candidates, torch.Tensor) and candidates.is_cuda:
+        if candidates.dtype != torch.int32 or candidates.device != dev:
+            raise ValueError(f"a3vt: touch_assemble: device `candidates` must be int32 on {dev}, got {candidates.dtype} on "
+                             f"{candidates.device}")
+        cand = candidates.contiguous()
+    else:
+        host = np.asarray(candidates.numpy() if isinstance(candidates, torch.Tensor) else candidates)
+        if host.ndim != 2 or host.size == 0 or not np.issubdtype(host.dtype, np.integer):
+            raise ValueError(f"a3vt: touch_assemble wants integer candidates (K, {E}), got {host.dtype} {host.shape}")
+        low, high = int(host.min()), int(host.max())
+        if low < 0 or high >= A:
+            raise ValueError(f"a3vt: touch_assemble: candidates outside [0, {A}): min {low}, max {high}")
+        cand = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(dev)
+    if cand.dim() != 2 or cand.shape[1] != E or cand.shape[0] < 1:
+        raise ValueError(f"a3vt: touch_assemble wants candidates (K, {E}), got {tuple(cand.shape)}")
+    K = cand.shape[0]
+    if K * E * F * G * C * 3 >= 1 << 31:
+        raise ValueError(f"a3vt: touch_assemble: K*E*F*G*C*3={K * E * F * G * C * 3} is not below 2**31 (K={K} E={E} F={F} G={G} C={C})")
+    if dev.type != "cuda":
+        rows = cand.long()
+        columns = torch.arange(E).unsqueeze(0).expand(K, E)
+        charts = state_charts.unsqueeze(0).repeat(K, 1, 1, 1, 1, 1)
+        masks = state_masks.reshape(1, E, F, G, C).repeat(K, 1, 1, 1, 1)
+        charts[:, :, :, slot] = table_charts[columns, rows]
+        masks[:, :, :, slot] = table_codes[columns, rows].clamp(0, 2).to(torch.float32).unsqueeze(-1)
+        return charts.view(K, E, F * G * C, 3), masks.view(K, E, F * G * C, 1)
+    table_charts, table_codes = table_charts.contiguous(), table_codes.contiguous()
+    state_charts, state_masks = state_charts.contiguous(), state_masks.contiguous()
+    charts = torch.empty((K, E, F * G * C, 3), dtype=torch.float32, device=dev)
+    masks = torch.empty((K, E, F * G * C, 1), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().a3vt_touch_assemble(_lib.ptr(table_charts), _lib.ptr(table_codes), _lib.ptr(state_charts),
+                                               _lib.ptr(state_masks), _lib.ptr(cand), K, E, A, F, G, C, slot, _lib.ptr(charts),
+                                               _lib.ptr(masks), _stream()), "touch_assemble")
+    return charts, masks
+
+
+TOUCH_RES = 121                                    # csrc/kernels.h's kTouchRes
 TOUCH_DEFAULTS = dict(max_depth=0.025, yfov=40.0 / 180.0 * np.pi, znear=1e-4, zfar=10.0)   # the reference's sensor and camera
 
 

@@ -9,11 +9,22 @@ differs, and why:
   ``None`` the reference's simulator is imported when the environment is constructed — never at module import — and an
   ``ImportError`` names ``policies.recorded.RecordedSampler`` where it is not installed.
 * **One greedy step is one batch** (``args.batched_greedy``, default ``BATCHED_GREEDY_DEFAULT``).  The reference's ``best_step``
-  runs ``compute_obs`` once per candidate action (:174-180, :200-208).  Here the sampler is still asked once per candidate (a
-  simulator is sequential), then the K candidates x E elements go through ``scoring.touch_slots`` (one touch-encoder forward over
-  K*E*F images) and ``scoring.score_actions`` (one stack call per refinement stage on K*E meshes, three surface draws, one
+  runs ``compute_obs`` once per candidate action (:174-180, :200-208).  Here the K candidates x E elements go through
+  ``scoring.touch_slots`` (one touch-encoder forward over K*E*F images; not with the touch table, below) and
+  ``scoring.score_charts`` (one stack call per refinement stage on K*E meshes, three surface draws, one
   shared-target search), and the (K, E) score table comes to the host in one copy.  ``args.candidate_chunk`` (default ``None``:
   all K at once) bounds the batch for a large E.  With the knob off the reference's loop runs, one ``compute_obs`` per candidate.
+* **One touch table per episode** (``args.touch_table``, default ``TOUCH_TABLE_DEFAULT``; read with ``getattr``, no command-line
+  flag).  The touch of action a on object e does not depend on what was touched before, and the samplers of this package are
+  pure functions of (object, action, finger).  With the knob on, ``reset`` asks the sampler ONCE, for everything
+  (``sampler.sample_table``: one render call for a ``RenderedSampler``), runs ONE touch-encoder forward over the E * A * F views
+  (``scoring.touch_slots``) and keeps ``table_charts`` (E, A, F, 25, 3) and ``table_codes`` (E, A, F) on the device.  Every
+  ``step``, ``check_step`` and candidate phase of the episode is then a gather from that table — ``ops.touch_assemble``, one
+  library launch that writes the K * E stacked chart and mask tensors in their final layout — and neither the sampler, the
+  encoder nor the host takes part.  With the knob off the sampler is asked once per candidate (a simulator is sequential) and
+  every answer is encoded again; a sampler without ``sample_table`` (the reference's simulator) cannot serve the knob and is
+  refused with it.  An action outside ``[0, num_actions)`` is refused with the table (the plain path asks the sampler, which
+  answers "no_intersection").
 * **Candidates leave no trace.**  The reference writes every candidate into slot ``steps`` of ``touch_charts`` / ``touch_masks``
   and overwrites it in ``step``.  Here ``check_step`` and the candidates of ``best_step`` work on copies; only ``reset`` and
   ``step`` write the state.  What a caller observes is the same.
@@ -33,6 +44,7 @@ import random
 import numpy as np
 import torch
 
+from ... import ops
 from ..reconstruction.autoencoder import model as auto_model
 from ..reconstruction.touch import model as touch_model
 from ..reconstruction.vision import model as vision_model
@@ -42,6 +54,10 @@ from . import scoring
 # Whether best_step scores its candidates as one batch when args does not say: on only if the batched step's p90 lies below the
 # loop's p10 at both chart topologies on an MI355X (tools/env_bench.py -> profiles/env_greedy_step_ab.txt).
 BATCHED_GREEDY_DEFAULT = True
+
+# Whether an episode's touches come from one table built at reset when args does not say: off until the A/B of
+# tools/touch_table_bench.py (profiles/touch_table_ab.txt) is on file.
+TOUCH_TABLE_DEFAULT = False
 
 NUM_GRASPS = 5      # the literal 5 of the reference's chart views (:357, :361)
 
@@ -109,6 +125,7 @@ class ActiveTouch:
         self.setup_recon()
         self.get_loaders()
         self.sampler = sampler if self._sampler_factory is None else self._sampler_factory(self.args.env_batch_size, False)
+        self._use_table()
 
     @staticmethod
     def _factory_of(sampler):
@@ -182,6 +199,29 @@ class ActiveTouch:
             self.auto_encoder.load_state_dict(torch.load(self.args.auto_location + "/model", map_location=self.device), strict=False)
             self.auto_encoder.eval()
 
+    def _use_table(self):
+        """Whether the episode's touches come from the touch table (``args.touch_table``); a sampler that cannot build one is
+        refused."""
+        knob = getattr(self.args, "touch_table", None)
+        if not (TOUCH_TABLE_DEFAULT if knob is None else knob):
+            return False
+        if not callable(getattr(self.sampler, "sample_table", None)):
+            raise ValueError(f"ActiveTouch: args.touch_table is set, and the sampler ({type(self.sampler).__name__}) has no "
+                             "sample_table to build the table from")
+        return True
+
+    def build_touch_table(self):
+        """``table_charts`` (E, A, F, 25, 3) and ``table_codes`` (E, A, F) int32 of the loaded objects: one ``sample_table`` call,
+        one ``scoring.touch_slots`` call (one encoder forward) over the E * A * F views in (e, a, f) order."""
+        table = self.sampler.sample_table(self.args.num_actions, fingers=[1] if self.args.finger else None, to_host=False)
+        codes = table["touch_code"].to(self.device).to(torch.int32)
+        status = np.array(["no_intersection", "no_touch", "touch"], dtype=object)[codes.cpu().numpy()]
+        ref_frame = {"rot": table["finger_transform_rot_M"].to(self.device).float(),
+                     "pos": table["finger_transfrom_pos"].to(self.device).float()}
+        self.table_charts, _ = scoring.touch_slots(self.touch_prediction, self._images(table["touch_signal"]), ref_frame, status,
+                                                   self.touch_verts)
+        self.table_codes = codes.contiguous()
+
     # reset the environment with new objects
     def reset(self, batch):
         self.current_data = {}
@@ -190,6 +230,8 @@ class ActiveTouch:
         self.current_data["batch"] = batch
         self.current_data["mask"] = torch.zeros([self.args.env_batch_size, self.args.num_actions])
         self.sampler.load_objects(batch["names"], from_dataset=True)
+        if self._use_table():
+            self.build_touch_table()
         obs = self.compute_obs()
         self.current_data["score"] = obs["score"]
         return obs
@@ -236,22 +278,37 @@ class ActiveTouch:
         samples = self._samples()
         scores = []
         for k0 in range(0, K, chunk):
-            signals = [self._signals(self.sampler.sample(actions, touch_point_cloud=True)) for actions in candidates[k0:k0 + chunk]]
-            n = len(signals)
-            touch, pos, rot = (torch.stack([s[i] for s in signals]) for i in range(3))
-            slots, slot_masks = scoring.touch_slots(self.touch_prediction, touch, {"rot": rot, "pos": pos},
-                                                    [s[3] for s in signals], self.touch_verts)      # (n, E, F, 25, 3 | 1)
-            charts = self.touch_charts.unsqueeze(0).repeat(n, 1, 1, 1, 1, 1)
-            masks = self.touch_masks.unsqueeze(0).repeat(n, 1, 1, 1, 1, 1)
-            charts[:, :, :, self.steps] = slots
-            masks[:, :, :, self.steps] = slot_masks
-            charts_list = [{"touch_charts": charts[k].view(E, -1, 3), "vision_charts": self.vision_charts,
-                            "touch_masks": masks[k].view(E, -1, 1), "vision_masks": self.vision_masks} for k in range(n)]
-            score, _, _ = scoring.score_actions(self.deform, batch["img"], charts_list, gt, self.mesh_info["faces"],
-                                                self.args.number_points, self.args.loss_coeff, samples=samples)
+            part = candidates[k0:k0 + chunk]
+            stacked = self._table_candidates(part) if self._use_table() else self._sampled_candidates(part)
+            score, _, _ = scoring.score_charts(self.deform, batch["img"], stacked, len(part), gt, self.mesh_info["faces"],
+                                               self.args.number_points, self.args.loss_coeff, samples=samples)
             scores.append(score)
         scores = torch.cat(scores)
         return scores.cpu() if to_host else scores
+
+    def _sampled_candidates(self, candidates):
+        """The chart dict of n candidate action lists stacked over n * E, candidate-major: the sampler asked once per candidate,
+        one ``scoring.touch_slots`` call for all of them."""
+        E = self.args.env_batch_size
+        signals = [self._signals(self.sampler.sample(actions, touch_point_cloud=True)) for actions in candidates]
+        n = len(signals)
+        touch, pos, rot = (torch.stack([s[i] for s in signals]) for i in range(3))
+        slots, slot_masks = scoring.touch_slots(self.touch_prediction, touch, {"rot": rot, "pos": pos},
+                                                [s[3] for s in signals], self.touch_verts)      # (n, E, F, 25, 3 | 1)
+        charts = self.touch_charts.unsqueeze(0).repeat(n, 1, 1, 1, 1, 1)
+        masks = self.touch_masks.unsqueeze(0).repeat(n, 1, 1, 1, 1, 1)
+        charts[:, :, :, self.steps] = slots
+        masks[:, :, :, self.steps] = slot_masks
+        return scoring.stack_charts([{"touch_charts": charts[k].view(E, -1, 3), "vision_charts": self.vision_charts,
+                                      "touch_masks": masks[k].view(E, -1, 1), "vision_masks": self.vision_masks} for k in range(n)])
+
+    def _table_candidates(self, candidates):
+        """The same dict from the touch table: one ``ops.touch_assemble`` launch writes the stacked touch charts and masks."""
+        n, E = len(candidates), self.args.env_batch_size
+        charts, masks = ops.touch_assemble(self.table_charts, self.table_codes, self.touch_charts, self.touch_masks, candidates,
+                                           self.steps)                                          # (n, E, F * 5 * 25, 3 | 1)
+        return {"touch_charts": charts.view(n * E, -1, 3), "vision_charts": self.vision_charts.repeat(n, 1, 1),
+                "touch_masks": masks.view(n * E, -1, 1), "vision_masks": self.vision_masks.repeat(n, 1, 1)}
 
     # check the result of perfroming a specific action
     def check_step(self, actions):
@@ -305,17 +362,24 @@ class ActiveTouch:
         on the device, and the E x F status strings.  With ``finger`` it is finger 1 alone, its image truncated through uint8
         (:282-291); the four-finger branch takes the signal as it is (:319-327)."""
         status = signals["touch_status"]
+        touch = signals["touch_signal"]
         if self.args.finger:
-            touch = torch.FloatTensor(signals["touch_signal"].data.numpy().astype(np.uint8))[:, 1:2]
+            touch = touch[:, 1:2]
             pos = signals["finger_transfrom_pos"][:, 1:2]
             rot = signals["finger_transform_rot_M"][:, 1:2]
             status = [[row[1]] for row in status]
         else:
-            touch = signals["touch_signal"]
             pos, rot = signals["finger_transfrom_pos"], signals["finger_transform_rot_M"]
             status = [list(row[:4]) for row in status]
-        touch = touch.to(self.device).permute(0, 1, 4, 2, 3) / 255.0
-        return touch, pos.to(self.device).float(), rot.to(self.device).float(), status
+        return self._images(touch), pos.to(self.device).float(), rot.to(self.device).float(), status
+
+    def _images(self, signal):
+        """Sensor images (..., 121, 121, 3) in 0..255, of the fingers read -> (..., 3, 121, 121) in [0, 1] on the device, the
+        arithmetic of ``_signals`` and of the touch table alike: with ``finger`` truncated through uint8 first (:282-291), then
+        ``/ 255.0`` in fp32.  (The truncation of images already on the device is made there: the same for values in 0..255.)"""
+        if self.args.finger:
+            signal = signal.to(torch.uint8).float() if signal.is_cuda else torch.FloatTensor(signal.data.numpy().astype(np.uint8))
+        return signal.to(self.device).movedim(-1, -3) / 255.0
 
     # perform a given action and a convert the resulting signals into expected input for the reconstructor
     def get_inputs(self, actions=None, commit=True):
@@ -330,6 +394,15 @@ class ActiveTouch:
             self.vision_charts = self.initial_mesh.unsqueeze(0).repeat(E, 1, 1)
             self.vision_masks = 3 * torch.ones(self.vision_charts.shape[:-1], device=self.device).unsqueeze(-1)
             touch_charts, touch_masks = self.touch_charts, self.touch_masks
+        elif self._use_table():
+            # slot ``steps`` of every finger from the touch table; the result is a new tensor, so without commit the state is as it was
+            actions = np.asarray(torch.as_tensor(actions).cpu()).reshape(1, E)
+            touch_charts, touch_masks = ops.touch_assemble(self.table_charts, self.table_codes, self.touch_charts, self.touch_masks,
+                                                           actions, self.steps)
+            touch_charts = touch_charts.view(E, num_fingers, NUM_GRASPS, 25, 3)
+            touch_masks = touch_masks.view(E, num_fingers, NUM_GRASPS, 25, 1)
+            if commit:
+                self.touch_charts, self.touch_masks = touch_charts, touch_masks
         else:
             touch, pos, rot, status = self._signals(self.sampler.sample(actions, touch_point_cloud=True))
             # "touch": the predicted chart, mask 2; "no_touch": the finger's position repeated, mask 1; otherwise zeros, mask 0

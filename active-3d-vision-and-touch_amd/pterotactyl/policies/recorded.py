@@ -19,7 +19,10 @@ Sources:
 Conventions of THIS package (the reference never replays, so none of this restates it): in a dataset tree a finger with a touch
 image is "touch", a finger with only a frame file is "no_touch", a finger with neither is "no_intersection" and all zeros; the
 object id is the basename of the ``names`` entry given to ``load_objects``; an unknown ``(id, action)`` is "no_intersection" for
-all four fingers, like a grasp that failed (``sampler.py:115-121``)."""
+all four fingers, like a grasp that failed (``sampler.py:115-121``).
+
+``sample_table(num_actions, fingers=None)`` answers for every action of the loaded objects at once — the table ``ActiveTouch`` builds
+once per episode under ``args.touch_table`` — with status codes (``STATUS_CODES``) in place of the strings."""
 import os
 from collections.abc import Mapping
 
@@ -28,6 +31,15 @@ import torch
 
 FINGERS = 4
 NO_CONTACT = "no_intersection"
+STATUS_CODES = {"touch": 2, "no_touch": 1}     # ``sample_table``'s ``touch_code`` (``scoring.touch_slots``' codes); anything else is 0
+
+
+def table_fingers(fingers):
+    """The ``fingers`` argument of ``sample_table`` as a list of indices into 0..3 (None: all four).  (Shared with ``rendered.py``.)"""
+    fingers = list(range(FINGERS)) if fingers is None else [int(f) for f in fingers]
+    if not fingers or any(not 0 <= f < FINGERS for f in fingers):
+        raise ValueError(f"sample_table: fingers must be indices into 0..{FINGERS - 1}, got {fingers}")
+    return fingers
 
 
 def object_id(name):
@@ -102,6 +114,29 @@ class RecordedSampler:
             pos[e] = torch.as_tensor(np.asarray(rec["pos"]), dtype=torch.float32)
             rot[e] = torch.as_tensor(np.asarray(rec["rot"]), dtype=torch.float32)
         return {"touch_status": status, "touch_signal": touch, "finger_transfrom_pos": pos, "finger_transform_rot_M": rot}
+
+    def sample_table(self, num_actions, fingers=None, to_host=None):
+        """What ``sample`` answers for EVERY action of the loaded objects, as one table (``ActiveTouch`` builds its per-episode touch
+        table from it): ``touch_signal`` (E, A, Fs, 121, 121, 3), ``touch_code`` (E, A, Fs) int32 (``STATUS_CODES``; 0 for anything
+        else), ``finger_transfrom_pos`` (E, A, Fs, 3) and ``finger_transform_rot_M`` (E, A, Fs, 3, 3), CPU tensors.  Entry [e, a, j]
+        is bit for bit what ``sample(actions)`` with ``actions[e] = a`` returns for element e and finger ``fingers[j]`` (None: all
+        four); zeros and code 0 where it says "no_intersection".  ``to_host`` is accepted for ``RenderedSampler``'s signature."""
+        fingers = table_fingers(fingers)
+        E, A, Fs = len(self.ids), int(num_actions), len(fingers)
+        touch = torch.zeros((E, A, Fs, 121, 121, 3))
+        code = torch.zeros((E, A, Fs), dtype=torch.int32)
+        pos = torch.zeros((E, A, Fs, 3))
+        rot = torch.zeros((E, A, Fs, 3, 3))
+        for e, obj in enumerate(self.ids):
+            for a in range(A):
+                rec = self.record(obj, a)
+                if rec is None:
+                    continue
+                code[e, a] = torch.tensor([STATUS_CODES.get(str(rec["status"][f]), 0) for f in fingers], dtype=torch.int32)
+                touch[e, a] = torch.as_tensor(np.asarray(rec["touch"]), dtype=torch.float32)[fingers]
+                pos[e, a] = torch.as_tensor(np.asarray(rec["pos"]), dtype=torch.float32)[fingers]
+                rot[e, a] = torch.as_tensor(np.asarray(rec["rot"]), dtype=torch.float32)[fingers]
+        return {"touch_signal": touch, "touch_code": code, "finger_transfrom_pos": pos, "finger_transform_rot_M": rot}
 
     def disconnect(self):
         pass

@@ -26,6 +26,9 @@ Sources:
   ``{object_id: (verts (V, 3), faces (F, 3))}``.  Faces are taken as stored: the caster is two-sided, so the reference's
   ``add_faces`` duplicates are not needed.
 
+``sample_table(num_actions, fingers=None, to_host=None)`` answers for every action of the loaded objects at once, rendering only the
+fingers asked for, in one call: the table ``ActiveTouch`` builds once per episode under ``args.touch_table``.
+
 Out of scope: the grasp physics (frames are an input), the TACTO renderer and vision images."""
 import os
 from collections.abc import Mapping
@@ -33,10 +36,11 @@ from collections.abc import Mapping
 import numpy as np
 import torch
 
-from .recorded import FINGERS, NO_CONTACT, object_id, tree_frames
+from .recorded import FINGERS, NO_CONTACT, object_id, table_fingers, tree_frames
 
 RES = 121
 STATUS = ("no_touch", "touch")          # the library's status codes
+MAX_VIEWS = 1 << 16                     # views of one a3vt_touch_render call (csrc/kernels.h's kTouchMaxImages)
 
 
 class RenderedSampler:
@@ -162,6 +166,56 @@ class RenderedSampler:
                 result["touch_point_cloud"] = [clouds[(k * E + e) * FINGERS:(k * E + e + 1) * FINGERS] for e in range(E)]
             results.append(result)
         return results
+
+    def sample_table(self, num_actions, fingers=None, to_host=None):
+        """What ``sample`` answers for EVERY action of the loaded objects, as one table (``ActiveTouch`` builds its per-episode touch
+        table from it): ``touch_signal`` (E, A, Fs, 121, 121, 3), ``touch_code`` (E, A, Fs) int32 (2 = "touch", 1 = "no_touch", 0 =
+        "no_intersection"), ``finger_transfrom_pos`` (E, A, Fs, 3) and ``finger_transform_rot_M`` (E, A, Fs, 3, 3).  Entry [e, a, j]
+        is bit for bit what ``sample(actions)`` with ``actions[e] = a`` returns for element e and finger ``fingers[j]`` (indices
+        into 0..3; None: all four).  Every grasp's frames are read once, and the live views of the fingers asked for — no others —
+        are rendered in ONE call, without contact points.  ``to_host`` None: the instance's setting; False leaves the table on the
+        renderer's device."""
+        fingers = table_fingers(fingers)
+        E, A, Fs = len(self.ids), int(num_actions), len(fingers)
+        if self.table is None:
+            raise RuntimeError("RenderedSampler: load_objects has not been called")
+        n = E * A * Fs
+        if n > MAX_VIEWS:
+            raise ValueError(f"RenderedSampler: sample_table of {E} objects x {A} actions x {Fs} fingers is {n} views, more than the "
+                             f"{MAX_VIEWS} of one render call")
+        to_host = self.to_host if to_host is None else to_host
+        pos, rot, live = np.zeros((n, 3), np.float32), np.zeros((n, 3, 3), np.float32), np.zeros(n, bool)
+        mesh_of = np.repeat(np.arange(E, dtype=np.int32), A * Fs)
+        for e, obj in enumerate(self.ids):
+            for a in range(A):
+                found = self.frames_of(obj, a)
+                if found is None:
+                    continue
+                at = slice((e * A + a) * Fs, (e * A + a + 1) * Fs)
+                p, r, present = found
+                present = np.asarray(present, bool).reshape(FINGERS)
+                pos[at] = (np.asarray(p, np.float32).reshape(FINGERS, 3) * present[:, None])[fingers]
+                rot[at] = (np.asarray(r, np.float32).reshape(FINGERS, 3, 3) * present[:, None, None])[fingers]
+                live[at] = present[fingers]
+        index = np.flatnonzero(live)
+        out = None
+        if len(index):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+            out = self.render(*self.table, up(mesh_of[index]), up(pos[index]), up(rot[index]), want_touch=True, want_points=False,
+                              **self.camera)
+        where = torch.device("cpu") if to_host or out is None else out["touch"].device
+        if len(index) == n:
+            signal, code = out["touch"].to(where), out["status"].to(where).to(torch.int32) + 1
+        else:                                                        # zeros and code 0 at the views that were not rendered
+            signal = torch.zeros((n, RES, RES, 3), device=where)
+            code = torch.zeros(n, dtype=torch.int32, device=where)
+            if out is not None:
+                index_t = torch.from_numpy(index).to(where)
+                signal[index_t] = out["touch"].to(where)
+                code[index_t] = out["status"].to(where).to(torch.int32) + 1  # the library's 0 / 1 -> "no_touch" 1 / "touch" 2
+        return {"touch_signal": signal.reshape(E, A, Fs, RES, RES, 3), "touch_code": code.reshape(E, A, Fs),
+                "finger_transfrom_pos": torch.from_numpy(pos).to(where).reshape(E, A, Fs, 3),
+                "finger_transform_rot_M": torch.from_numpy(rot).to(where).reshape(E, A, Fs, 3, 3)}
 
     def disconnect(self):
         pass

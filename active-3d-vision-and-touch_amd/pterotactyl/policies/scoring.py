@@ -62,8 +62,13 @@ def score_actions(deform, img, charts_list, gt_points, faces, number_points, los
     samples      : optional injected (face_idx, u, v), each (repeat,E,number_points), reused for every candidate
     returns      : ``score`` (K,E) = loss_coeff * Chamfer (``get_score`` :252-257), ``verts`` (K,E,N,3), ``mask`` (K,E,N,1)
     """
-    K = len(charts_list)
-    charts = stack_charts(charts_list)
+    return score_charts(deform, img, stack_charts(charts_list), len(charts_list), gt_points, faces, number_points, loss_coeff,
+                        repeat=repeat, samples=samples)
+
+
+def score_charts(deform, img, charts, K, gt_points, faces, number_points, loss_coeff, repeat=3, samples=None):
+    """``score_actions`` on the chart dict already stacked over K * E, candidate-major (``stack_charts``' result, or what
+    ``ActiveTouch.score_candidates`` assembles from its touch table in one launch): the same arguments otherwise, the same results."""
     dev = charts["vision_charts"].device
     E = gt_points.shape[0]
     with torch.no_grad():

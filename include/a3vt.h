@@ -604,6 +604,43 @@ int a3vt_candidate_tally(const float *scores, const int32_t *candidates, const f
                          double unvisited, double *sums, double *checks, double *votes, int32_t *best, float *best_score, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The candidate inputs of one greedy step from the per-episode touch table (policies/environment.py:score_candidates, get_inputs).
+ *
+ * A touch does not depend on what was touched before, so ActiveTouch computes the chart and code of every (element, action,
+ * finger) once per episode.  a3vt_touch_assemble writes the touch charts and masks of K candidate action lists over E elements
+ * in the layout the reconstructor takes, candidate-major.
+ *   table_charts [E][A][F][C][3]   the chart action a would put on finger f of element e
+ *   table_codes  [E][A][F] int32   2 = "touch", 1 = "no_touch", 0 = no contact
+ *   state_charts [E][F][G][C][3], state_masks [E][F][G][C]   the episode's touch state: G grasp slots of C chart vertices
+ *   candidates   [K][E] int32      the action candidate k tries on element e
+ *   slot                           the grasp slot the candidates fill
+ *   charts       [K][E][F][G][C][3] out, masks [K][E][F][G][C] out
+ *
+ * Output rules.
+ * - For g != slot, block (k, e, f, g) of both outputs is a copy of the state's block (e, f, g).
+ * - For g == slot, with a = candidates[k][e]: charts[k][e][f][slot] = table_charts[e][a][f], and every value of
+ *   masks[k][e][f][slot] is (float) of table_codes[e][a][f] clamped into 0..2.
+ * - An action outside [0, A) gives a zero chart and mask 0 in that block.  It never indexes the table.  (The Python layer refuses
+ *   such a list when it has it on the host.)
+ * - Every value moves as 32 bits unchanged: NaN payloads, infinities and -0 survive.
+ * - No input is written.  The outputs must not overlap the inputs.
+ *
+ * One launch on `stream`.  No allocation, no host synchronisation, no atomics, no workspace, no environment variable: the same
+ * bits on every call.
+ *
+ * Limits.
+ * - K, E, A, F, G, C >= 1 and 0 <= slot < G.
+ * - K * E * F * G * C * 3 < 2^31.
+ * - Every pointer is required and 4-byte aligned; no wider alignment is assumed (a block of C = 25 vertices is 300 bytes).
+ * - Anything else returns non-zero with a message in a3vt_last_error that names the argument and its value.  Nothing is launched.
+ *
+ * a3vt_touch_assemble_launches: [0] the a3vt_touch_assemble calls that launched since the last reset; returns 1. */
+int a3vt_touch_assemble(const float *table_charts, const int32_t *table_codes, const float *state_charts, const float *state_masks,
+                        const int32_t *candidates, int K, int E, int A, int F, int G, int C, int slot, float *charts, float *masks,
+                        void *stream);
+int a3vt_touch_assemble_launches(long long *counts /*[1]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The rendered touch sampler: from finger frames and triangles to every signal of simulator/scene/instance.py:121-258.
  *
  * A batch of I finger views over a table of M meshes.
