@@ -1455,6 +1455,45 @@ int a3vt_touch_assemble(const float *table_charts, const int32_t *table_codes, c
 
 int a3vt_touch_assemble_launches(long long *counts, int reset) { return g_touch_assemble_launches.read(counts, reset); }
 
+// ---- the touch chart predictor's head: fc, template, finger frame and slot rule (chart_head.hip) ---------------------------------
+namespace {
+LaunchCounts<1> g_chart_head_launches;
+}  // namespace
+
+int a3vt_touch_chart_head(const float *features, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                          const float *b3, const float *tmpl, const float *rot, const float *pos, const int32_t *code, int n, float *rows,
+                          float *charts, float *masks, void *stream) {
+  const char *who = "touch_chart_head";
+  if (check_range(who, "n", n, 1, INT_MAX)) return -1;
+  const double floats = (double)kHeadIn * n;
+  if (floats >= 2147483648.0) {
+    set_error("%s: n*%d=%.0f (n=%d) is not below 2147483648", who, kHeadIn, floats, n);
+    return -1;
+  }
+  if (check_ptrs(who, {{"features", features, true, 16, "required"},
+                       {"w1", w1, true, 16, "required"},
+                       {"b1", b1, true, 4, "required"},
+                       {"w2", w2, true, 16, "required"},
+                       {"b2", b2, true, 4, "required"},
+                       {"w3", w3, true, 16, "required"},
+                       {"b3", b3, true, 4, "required"},
+                       {"tmpl", tmpl, true, 4, "required"},
+                       {"rot", rot, true, 4, "required"},
+                       {"pos", pos, true, 4, "required"},
+                       {"code", code, true, 4, "required"},
+                       {"rows", rows, true, 16, "required"},
+                       {"charts", charts, masks != nullptr, 4, "charts and masks go together"},
+                       {"masks", masks, charts != nullptr, 4, "charts and masks go together"}}))
+    return -1;
+  if (int rc = launch_touch_chart_head(features, w1, b1, w2, b2, w3, b3, tmpl, rot, pos, code, n, rows, charts, masks,
+                                       static_cast<hipStream_t>(stream)))
+    return rc;
+  g_chart_head_launches.add(0, 1);
+  return 0;
+}
+
+int a3vt_touch_chart_head_launches(long long *counts, int reset) { return g_chart_head_launches.read(counts, reset); }
+
 // ---- the rendered touch sampler (touch_render.hip) ---------------------------------------------------------------------------------
 namespace {
 // The finish launch's own arguments (shared by both entries): 0, or -1 with the message set.

@@ -396,6 +396,13 @@ int launch_touch_assemble(const float *table_charts, const int32_t *table_codes,
                           const int32_t *candidates, int K, int E, int A, int F, int G, int C, int slot, float *charts, float *masks,
                           hipStream_t s);
 
+// chart_head.hip: the touch chart predictor's three Linear layers, the template add, the move into the finger's frame and
+// touch_slots' select on the status code — one launch, a tile of kHeadRows views per workgroup
+constexpr int kHeadRows = 16, kHeadIn = 512, kHeadHidden1 = 256, kHeadHidden2 = 128, kHeadVerts = 25, kHeadOut = 3 * kHeadVerts;
+int launch_touch_chart_head(const float *features, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                            const float *b3, const float *tmpl, const float *rot, const float *pos, const int32_t *code, int n, float *rows,
+                            float *charts, float *masks, hipStream_t s);
+
 // touch_render.hip: the rendered touch sampler (simulator/scene/instance.py:121-258) — a ray-cast depth map per finger view, then
 // status, gel image and contact points from it: two launches for a batch of views
 constexpr int kTouchRes = 121;            // the reference's point grid hard-codes it (instance.py:172-184)

@@ -1381,6 +1381,85 @@ def touch_assemble(table_charts, table_codes, state_charts, state_masks, candida
     return charts, masks
 
 
+def chart_head_launches(reset=False):
+    """``a3vt_touch_chart_head`` calls that launched since the last reset (a test hook, as ``touch_assemble_launches``)."""
+    return _launch_counts("a3vt_touch_chart_head_launches", ("calls",), reset)
+
+
+CHART_HEAD_SHAPES = ((256, 512), (128, 256), (75, 128))     # fc.0.0, fc.1.0, fc.2.0 of the touch ``Encoder``
+
+
+def _chart_head_torch(features, fc, template, rot, pos, code):
+    """The torch formulation of ``touch_chart_head``: the lines of ``Encoder.forward`` (``fc``, the template add,
+    ``transform_verts``) and of ``scoring.touch_slots`` (the two ``where`` and the ``expand``), on any device."""
+    n = features.shape[0]
+    verts = template.view(1, -1, 3).repeat(n, 1, 1)
+    verts = verts + fc(features).view(-1, verts.shape[1], 3)
+    pred = torch.bmm(rot, verts.permute(0, 2, 1)).permute(0, 2, 1) + pos.view(-1, 1, 3)
+    code = code.to(torch.float32).view(n, 1, 1)
+    code = torch.where(code == 2, code, torch.where(code == 1, code, torch.zeros_like(code)))     # (any other code is 0)
+    charts = torch.where(code == 2, pred, torch.where(code == 1, pos.view(n, 1, 3).expand_as(pred), torch.zeros_like(pred)))
+    masks = code.expand(n, verts.shape[1], 1)
+    return charts.contiguous(), masks.contiguous()
+
+
+def touch_chart_head(features, fc, template, rot, pos, code, want_slots=False):
+    """The head of the touch chart predictor and the slot rule of ``scoring.touch_slots`` for n views -> ``rows`` (n, 25, 4)
+    float32: x, y, z, mask — the layout of a data set's ``touch_charts.npy``; with ``want_slots`` ``(rows, charts (n, 25, 3),
+    masks (n, 25, 1))``, the two tensors ``touch_slots`` returns.
+
+    ``features`` (n, 512) float32: ``Encoder.predict_features``; ``fc``: the encoder's ``fc`` (three ``Linear``, 512 -> 256 ->
+    128 -> 75, ReLU after the first two); ``template`` (25, 3); ``rot`` (n, 3, 3), ``pos`` (n, 3): the finger frames; ``code``
+    (n,) integers: 2 = "touch" (the predicted chart in the finger's frame, mask 2), 1 = "no_touch" (the finger's position 25
+    times, mask 1), anything else zeros and mask 0.  A select: a NaN in the features of a view whose code is not 2 does not reach
+    its rows.  Forward only: nothing carries an autograd graph.
+
+    GPU tensors run ``a3vt_touch_chart_head`` (csrc/chart_head.hip: ONE launch, exact fp32 in a fixed order of every sum, so a
+    view's rows are the same bits alone and inside any batch; the contract is in ``include/a3vt.h``).  CPU tensors take the torch
+    lines the kernel replaces (``Encoder.forward`` + ``touch_slots``), bit for bit what those give."""
+    layers = [fc[i][0] for i in range(3)]
+    dev = features.device
+    for t, name, shape in ((features, "features", (-1, CHART_HEAD_SHAPES[0][1])), (template, "template", (25, 3)),
+                           (rot, "rot", (-1, 3, 3)), (pos, "pos", (-1, 3))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != len(shape) or \
+                any(s != -1 and s != d for s, d in zip(shape, t.shape)):
+            raise ValueError(f"a3vt: touch_chart_head wants `{name}` float32 {shape} (-1: n), got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.device != dev:
+            raise ValueError(f"a3vt: touch_chart_head `{name}` is on {t.device}, the features on {dev}")
+    n = features.shape[0]
+    if n < 1 or rot.shape[0] != n or pos.shape[0] != n:
+        raise ValueError(f"a3vt: touch_chart_head wants n >= 1 views in features, rot and pos, got {n}, {rot.shape[0]}, {pos.shape[0]}")
+    if not isinstance(code, torch.Tensor) or code.is_floating_point() or tuple(code.shape) != (n,) or code.device != dev:
+        raise ValueError(f"a3vt: touch_chart_head wants `code` ({n},) integers on {dev}, got "
+                         f"{(code.dtype, tuple(code.shape), code.device) if isinstance(code, torch.Tensor) else type(code).__name__}")
+    for layer, shape in zip(layers, CHART_HEAD_SHAPES):
+        if tuple(layer.weight.shape) != shape or layer.bias is None or layer.weight.dtype != torch.float32 or layer.weight.device != dev:
+            raise ValueError(f"a3vt: touch_chart_head wants a float32 Linear {shape[1]} -> {shape[0]} with bias on {dev}, got {layer} "
+                             f"({layer.weight.dtype} on {layer.weight.device})")
+    if n * CHART_HEAD_SHAPES[0][1] >= 1 << 31:
+        raise ValueError(f"a3vt: touch_chart_head: n*512={n * 512} is not below 2**31 (n={n})")
+    with torch.no_grad():
+        if dev.type != "cuda":
+            charts, masks = _chart_head_torch(features, fc, template, rot, pos, code)
+            rows = torch.cat((charts, masks), dim=-1)
+            return (rows, charts, masks) if want_slots else rows
+
+        def operand(t):                     # contiguous, and on a 16-byte boundary (a view into a larger tensor need not be)
+            t = t.detach().contiguous()
+            return t.clone() if t.data_ptr() % 16 else t
+        weights = [operand(p) for layer in layers for p in (layer.weight, layer.bias)]
+        features, template, rot, pos = operand(features), operand(template), operand(rot), operand(pos)
+        code = code.to(torch.int32).contiguous()
+        rows = torch.empty((n, 25, 4), dtype=torch.float32, device=dev)
+        charts = torch.empty((n, 25, 3), dtype=torch.float32, device=dev) if want_slots else None
+        masks = torch.empty((n, 25, 1), dtype=torch.float32, device=dev) if want_slots else None
+        _lib.check(_lib.load().a3vt_touch_chart_head(_lib.ptr(features), *(_lib.ptr(w) for w in weights), _lib.ptr(template),
+                                                     _lib.ptr(rot), _lib.ptr(pos), _lib.ptr(code), n, _lib.ptr(rows), _lib.ptr(charts),
+                                                     _lib.ptr(masks), _stream()), "touch_chart_head")
+    return (rows, charts, masks) if want_slots else rows
+
+
 TOUCH_RES = 121                                    # csrc/kernels.h's kTouchRes
 TOUCH_DEFAULTS = dict(max_depth=0.025, yfov=40.0 / 180.0 * np.pi, znear=1e-4, zfar=10.0)   # the reference's sensor and camera
 

@@ -25,6 +25,8 @@ differs, and why:
   every answer is encoded again; a sampler without ``sample_table`` (the reference's simulator) cannot serve the knob and is
   refused with it.  An action outside ``[0, num_actions)`` is refused with the table (the plain path asks the sampler, which
   answers "no_intersection").
+* **The predictor's head in one launch** (``args.fused_head``, default ``scoring.FUSED_HEAD_DEFAULT``; read with ``getattr``, no
+  command-line flag): every ``scoring.touch_slots`` call below passes it on.  Off, the torch lines run as they always have.
 * **Candidates leave no trace.**  The reference writes every candidate into slot ``steps`` of ``touch_charts`` / ``touch_masks``
   and overwrites it in ``step``.  Here ``check_step`` and the candidates of ``best_step`` work on copies; only ``reset`` and
   ``step`` write the state.  What a caller observes is the same.
@@ -219,7 +221,7 @@ class ActiveTouch:
         ref_frame = {"rot": table["finger_transform_rot_M"].to(self.device).float(),
                      "pos": table["finger_transfrom_pos"].to(self.device).float()}
         self.table_charts, _ = scoring.touch_slots(self.touch_prediction, self._images(table["touch_signal"]), ref_frame, status,
-                                                   self.touch_verts)
+                                                   self.touch_verts, fused_head=getattr(self.args, "fused_head", None))
         self.table_codes = codes.contiguous()
 
     # reset the environment with new objects
@@ -294,7 +296,8 @@ class ActiveTouch:
         n = len(signals)
         touch, pos, rot = (torch.stack([s[i] for s in signals]) for i in range(3))
         slots, slot_masks = scoring.touch_slots(self.touch_prediction, touch, {"rot": rot, "pos": pos},
-                                                [s[3] for s in signals], self.touch_verts)      # (n, E, F, 25, 3 | 1)
+                                                [s[3] for s in signals], self.touch_verts,
+                                                fused_head=getattr(self.args, "fused_head", None))      # (n, E, F, 25, 3 | 1)
         charts = self.touch_charts.unsqueeze(0).repeat(n, 1, 1, 1, 1, 1)
         masks = self.touch_masks.unsqueeze(0).repeat(n, 1, 1, 1, 1, 1)
         charts[:, :, :, self.steps] = slots
@@ -407,7 +410,8 @@ class ActiveTouch:
             touch, pos, rot, status = self._signals(self.sampler.sample(actions, touch_point_cloud=True))
             # "touch": the predicted chart, mask 2; "no_touch": the finger's position repeated, mask 1; otherwise zeros, mask 0
             # (:304-315, :339-353); predictions are indexed element * num_fingers + finger, as there
-            slots, slot_masks = scoring.touch_slots(self.touch_prediction, touch, {"rot": rot, "pos": pos}, status, self.touch_verts)
+            slots, slot_masks = scoring.touch_slots(self.touch_prediction, touch, {"rot": rot, "pos": pos}, status, self.touch_verts,
+                                                    fused_head=getattr(self.args, "fused_head", None))
             if commit:
                 touch_charts, touch_masks = self.touch_charts, self.touch_masks
             else:

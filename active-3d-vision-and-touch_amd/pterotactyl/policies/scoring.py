@@ -13,7 +13,15 @@ shared by the K candidates (the reference recomputes them per candidate).
 """
 import torch
 
+from ... import ops
 from ..utility import utils
+
+# Whether touch_slots runs the predictor's head as one launch (ops.touch_chart_head) when the caller does not say: on only if the
+# fused head's p90 lies below the torch tail's p10 at both n = 12 and n = 600 on an MI355X (tools/touch_bake_bench.py ->
+# profiles/touch_bake_ab.txt).  The A/B on file meets the rule (the head alone: 0.10 ms against 0.27 at both sizes), and the default
+# is still off: on, every caller's charts change in their last bits (another order of the fp32 sums), which is a change of its own —
+# end to end the launch saves 1 % of a 600-view touch_slots call.
+FUSED_HEAD_DEFAULT = False
 
 
 def stack_charts(charts_list):
@@ -22,7 +30,7 @@ def stack_charts(charts_list):
     return {key: torch.cat([c[key] for c in charts_list], dim=0) for key in charts_list[0]}
 
 
-def touch_slots(encoder, touch, ref_frame, status, template):
+def touch_slots(encoder, touch, ref_frame, status, template, fused_head=None):
     """The touch charts and masks of a batch of sensor readings — what ``ActiveTouch.get_inputs`` (``policies/environment.py:
     294-353``) does with the touch model's predictions, for any leading shape at once (environments x fingers, or candidates x
     environments x fingers: one ``Encoder`` forward for all of them).
@@ -34,13 +42,22 @@ def touch_slots(encoder, touch, ref_frame, status, template):
     template   : (25, 3) chart template
     returns    : charts (..., 25, 3), masks (..., 25, 1): "touch" -> the predicted chart, mask 2; "no_touch" -> the chart collapsed
                  to the finger's position, mask 1; otherwise zeros, mask 0 — the ``touch_charts`` / ``touch_masks`` slots of
-                 ``prepare_mesh`` / ``score_actions``' chart dicts."""
+                 ``prepare_mesh`` / ``score_actions``' chart dicts.
+    fused_head : with GPU inputs, the encoder's convolutions (``predict_features``) and then ONE ``ops.touch_chart_head`` launch for
+                 the three linear layers, the template, the frame and the two selects; None: ``FUSED_HEAD_DEFAULT``.  Off, and on
+                 the CPU, the torch lines below run as they always have."""
     import numpy as np
     lead = tuple(touch.shape[:-3])
     dev = touch.device
     status = np.asarray(status, dtype=object).reshape(lead)
     code = torch.from_numpy(np.where(status == "touch", 2, np.where(status == "no_touch", 1, 0)).astype(np.float32)).to(dev)
     n = int(code.numel())
+    if (FUSED_HEAD_DEFAULT if fused_head is None else fused_head) and touch.is_cuda:
+        with torch.no_grad():
+            features = encoder.predict_features(touch.reshape(n, *touch.shape[-3:]))
+        _, charts, masks = ops.touch_chart_head(features, encoder.fc, template.to(dev), ref_frame["rot"].to(dev).reshape(n, 3, 3),
+                                                ref_frame["pos"].to(dev).reshape(n, 3), code.reshape(n).to(torch.int32), want_slots=True)
+        return charts.reshape(*lead, -1, 3), masks.reshape(*lead, -1, 1)
     pos = ref_frame["pos"].to(dev).reshape(n, 3)
     ref = {"rot": ref_frame["rot"].to(dev).reshape(n, 3, 3), "pos": pos}
     verts = template.to(dev).view(1, -1, 3).repeat(n, 1, 1)

@@ -13,6 +13,10 @@ matrix pipe) over channels-last maps, their eval-mode BatchNorm and ReLU folded 
 linear layers stay on torch, as does everything in training (the kernels are forward-only), on the CPU, or with the knob off.
 The default of the knob is ``FUSED_STEM_DEFAULT``: the result of the A/B in profiles/touch_encoder_ab.txt.
 
+This package's own entry points: ``predict_features`` (everything before ``fc``: the (B, 512) vectors ``ops.touch_chart_head``
+takes; ``predict_verts`` is ``fc`` of them) and ``predict_features_nhwc`` (the same from channels-last images, which the fused
+stem takes as they are).
+
 Differences from the reference: ``transform_verts`` does not write into its argument (the reference's ``verts += pos`` is
 applied to a fresh tensor there too, the result of ``bmm``; here nothing is in place) and moves ``ref`` to the vertices' device
 instead of calling ``.cuda()``; the BatchNorm layers are ``BatchNorm2d`` below (training passes avoid MIOpen's kernels);
@@ -113,22 +117,41 @@ class Encoder(nn.Module):
     def stem(self, touch):
         """Blocks 1-3: (B,3,121,121) -> (B,32,16,16)."""
         if self.takes_fused_stem(touch):
-            x = touch.permute(0, 2, 3, 1).contiguous()          # channels-last once; the kernels keep it
-            for block in self.CNN_layers[:FUSED_BLOCKS]:
-                x = block.forward_fused(x)
-            # (B,32,16,16) for torch's convolutions, as a CONTIGUOUS copy (32 KB per image): on a channels-last view MIOpen's
-            # deterministic kernels (repeatable_torch_kernels) take 61 ms for blocks 4-6 at B = 600 instead of 2.5
-            return x.permute(0, 3, 1, 2).contiguous()
+            return self.stem_nhwc(touch.permute(0, 2, 3, 1).contiguous())          # channels-last once; the kernels keep it
         for block in self.CNN_layers[:FUSED_BLOCKS]:
             touch = block(touch)
         return touch
 
-    def predict_verts(self, touch):
+    def stem_nhwc(self, x):
+        """Blocks 1-3 on the fused kernels from a contiguous channels-last map: (B,121,121,3) -> (B,32,16,16)."""
+        for block in self.CNN_layers[:FUSED_BLOCKS]:
+            x = block.forward_fused(x)
+        # (B,32,16,16) for torch's convolutions, as a CONTIGUOUS copy (32 KB per image): on a channels-last view MIOpen's
+        # deterministic kernels (repeatable_torch_kernels) take 61 ms for blocks 4-6 at B = 600 instead of 2.5
+        return x.permute(0, 3, 1, 2).contiguous()
+
+    def _features(self, x):
+        """Blocks 4-6 on the stem's output -> the (B, 512) vectors ``fc`` takes."""
+        for block in self.CNN_layers[FUSED_BLOCKS:]:
+            x = block(x)
+        return x.contiguous().view(-1, 512)
+
+    def predict_features(self, touch):
+        """(B,3,121,121) -> (B,512): everything before ``fc``."""
         with repeatable_torch_kernels():
-            touch = self.stem(touch)
-            for block in self.CNN_layers[FUSED_BLOCKS:]:
-                touch = block(touch)
-            return self.fc(touch.contiguous().view(-1, 512))
+            return self._features(self.stem(touch))
+
+    def predict_features_nhwc(self, signal):
+        """``predict_features`` of sensor images as the samplers deliver them, channels LAST: (B,121,121,3) in [0, 1].  With the
+        fused stem taken the images feed ``conv5f`` as they are — no pass that moves the channels first and none that moves them
+        back — and the result is ``predict_features(signal.movedim(-1, -3))`` bit for bit; otherwise they are permuted once."""
+        with repeatable_torch_kernels():
+            if self.takes_fused_stem(signal):
+                return self._features(self.stem_nhwc(signal.contiguous()))
+            return self._features(self.stem(signal.permute(0, 3, 1, 2).contiguous()))
+
+    def predict_verts(self, touch):
+        return self.fc(self.predict_features(touch))
 
     def transform_verts(self, verts, ref):
         """Chart vertices from the sensor's frame into the world's: ``rot . v + pos`` per sample; the inputs are left alone."""

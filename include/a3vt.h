@@ -641,6 +641,42 @@ int a3vt_touch_assemble(const float *table_charts, const int32_t *table_codes, c
 int a3vt_touch_assemble_launches(long long *counts /*[1]*/, int reset);
 
 /* ---------------------------------------------------------------------------------------------
+ * The head of the touch chart predictor (reconstruction/touch/model.py: Encoder.fc, the template add, transform_verts) and the slot
+ * rule of policies/scoring.py:touch_slots, for n views in one launch.
+ *   features [n][512]            what the encoder's convolutions leave per view
+ *   w1 [256][512], b1 [256]      fc.0.0, as torch stores a Linear: weight [out][in]
+ *   w2 [128][256], b2 [128]      fc.1.0
+ *   w3 [75][128],  b3 [75]       fc.2.0
+ *   tmpl [25][3]                 the chart template
+ *   rot [n][3][3], pos [n][3]    the finger frames
+ *   code [n] int32               2 = "touch", 1 = "no_touch", anything else = no contact
+ *   rows   [n][25][4] out        x, y, z, mask: the layout of a data set's touch_charts.npy
+ *   charts [n][25][3], masks [n][25] out, both or neither (NULL): the same values as touch_slots' two tensors
+ *
+ * Per view: v = tmpl + fc(features) as 25 x 3, with ReLU after the first two layers (a NaN stays a NaN); w = rot . v + pos
+ * (w[p][a] = ((rot[a][0] v[p][0] + rot[a][1] v[p][1]) + rot[a][2] v[p][2]) + pos[a], one rounding per multiply-add, then the add).
+ *   code 2: w, mask 2.    code 1: pos in all 25 rows, mask 1.    otherwise: zeros, mask 0.
+ * The rule is a select: no value of a view whose code is not 2 comes from its features or rot, and with any code but 1 and 2 none
+ * comes from pos, so a NaN there does not reach the outputs.  No view's output depends on another view.
+ *
+ * Exact fp32.  The order of every sum is fixed and does not depend on n or on the view's index (csrc/chart_head.hip states it): the
+ * same view gives the same bits alone, inside any batch and at any position.  One launch on `stream`.  No allocation, no host
+ * synchronisation, no atomics, no workspace, no environment variable.  No input is written; outputs must not overlap inputs.
+ *
+ * Limits.
+ * - n >= 1 and n * 512 < 2^31.
+ * - features, w1, w2, w3 and rows are 16-byte aligned, every other pointer 4-byte aligned; all are required except charts and
+ *   masks, which come together.
+ * - Anything else returns non-zero with a message in a3vt_last_error that names touch_chart_head, the argument and its value.
+ *   Nothing is launched.
+ *
+ * a3vt_touch_chart_head_launches: [0] the a3vt_touch_chart_head calls that launched since the last reset; returns 1. */
+int a3vt_touch_chart_head(const float *features, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                          const float *b3, const float *tmpl, const float *rot, const float *pos, const int32_t *code, int n, float *rows,
+                          float *charts, float *masks, void *stream);
+int a3vt_touch_chart_head_launches(long long *counts /*[1]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The rendered touch sampler: from finger frames and triangles to every signal of simulator/scene/instance.py:121-258.
  *
  * A batch of I finger views over a table of M meshes.
