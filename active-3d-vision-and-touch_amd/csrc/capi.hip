@@ -1551,6 +1551,36 @@ int a3vt_touch_render(const float *verts, int V, const int32_t *faces, int F, co
   return launch_touch_finish(depth, cam_pos, cam_rot, I, max_depth, yfov, touch, points, count, status, s);
 }
 
+// ---- the renderer's outputs as a data set stores them (touch_pack.hip) -------------------------------------------------------------
+namespace {
+LaunchCounts<1> g_touch_pack_launches;
+}  // namespace
+
+int a3vt_touch_pack(const float *touch, const float *points, const int32_t *count, const int32_t *status, int I, int capacity,
+                    uint8_t *touch_u8, int32_t *offsets, float *cloud, void *stream) {
+  const char *who = "touch_pack";
+  if (check_range(who, "I", I, 1, kTouchMaxImages) || check_range(who, "capacity", capacity, 0, INT_MAX)) return -1;
+  const bool cloudy = points || count || status || offsets || cloud;
+  if (!touch && !touch_u8 && !cloudy) {
+    set_error("%s: touch=NULL and points=NULL: nothing to pack", who);
+    return -1;
+  }
+  if (check_ptrs(who, {{"touch", touch, touch_u8 != nullptr, 16, "touch and touch_u8 go together"},
+                       {"touch_u8", touch_u8, touch != nullptr, 4, "touch and touch_u8 go together"},
+                       {"points", points, cloudy, 4, "points, count, status and offsets go together"},
+                       {"count", count, cloudy, 4, "points, count, status and offsets go together"},
+                       {"status", status, cloudy, 4, "points, count, status and offsets go together"},
+                       {"offsets", offsets, cloudy, 4, "points, count, status and offsets go together"},
+                       {"cloud", cloud, cloudy && capacity > 0, 4, "required with points when capacity > 0"}}))
+    return -1;
+  if (int rc = launch_touch_pack(touch, points, count, status, I, capacity, touch_u8, offsets, cloud, static_cast<hipStream_t>(stream)))
+    return rc;
+  g_touch_pack_launches.add(0, 1);
+  return 0;
+}
+
+int a3vt_touch_pack_launches(long long *counts, int reset) { return g_touch_pack_launches.read(counts, reset); }
+
 // ---- mesh and point-cloud rendering (scene_render.hip) -----------------------------------------------------------------------------
 namespace {
 LaunchCounts<2> g_scene_launches;

@@ -414,6 +414,11 @@ int launch_touch_depth(const float *verts, int V, const int32_t *faces, int F, c
 int launch_touch_finish(const float *depth, const float *cam_pos, const float *cam_rot, int I, float max_depth, float yfov, float *touch,
                         float *points, int32_t *count, int32_t *status, hipStream_t s);
 
+// touch_pack.hip: touch_render's images as uint8 and its contact clouds packed behind an offsets table — one launch, every cloud
+// workgroup forms its prefix from count / status itself
+int launch_touch_pack(const float *touch, const float *points, const int32_t *count, const int32_t *status, int I, int capacity,
+                      uint8_t *touch_u8, int32_t *offsets, float *cloud, hipStream_t s);
+
 // scene_render.hip: colour, depth and primitive-index images of triangle + sphere scenes (utility/pretty_render.py's job): a ray
 // cast per pixel with Lambert shading, one launch per kSceneImagesPerLaunch images.  The small tables travel by value in the kernel
 // arguments: the host has checked them, and nothing on the device has to be trusted or clamped.

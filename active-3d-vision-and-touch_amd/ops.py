@@ -1532,6 +1532,81 @@ def touch_finish(depth, cam_pos, cam_rot, max_depth=TOUCH_DEFAULTS["max_depth"],
     return _touch_result(depth, touch, points, count, status)
 
 
+def touch_pack_launches(reset=False):
+    """``a3vt_touch_pack`` calls that launched since the last reset (a test hook, as ``touch_assemble_launches``)."""
+    return _launch_counts("a3vt_touch_pack_launches", ("calls",), reset)
+
+
+def touch_pack(out, want_touch=True, want_points=True, capacity=None):
+    """What ``touch_render`` / ``touch_finish`` returned (``out``: that dict) in the form a data set stores it, on the device
+    (``a3vt_touch_pack``, csrc/touch_pack.hip: ONE launch on the current stream, no host synchronisation) -> a dict with, under
+    ``want_touch``, ``touch_u8`` (I, 121, 121, 3) uint8 — ``out["touch"]`` clamped to [0, 255] and truncated, NaN 0: for the
+    renderer's values ``.to(torch.uint8)`` — and, under ``want_points``, ``offsets`` (I + 1,) int32, the exclusive prefix sum of
+    ``n_i = count[i] if status[i] == 1 else 0``, and ``cloud`` (capacity, 3) float32 whose rows ``[offsets[i], offsets[i + 1])``
+    are ``points[i, :n_i]`` bit for bit.  The rows from ``offsets[I]`` on are not written.
+
+    ``capacity`` None sizes ``cloud`` for the worst case, I * 14641 rows, and nothing is read back.  With a bound the launch
+    writes no row when the total exceeds it; this function then reads ``offsets[I]`` (one synchronisation) and raises
+    ``RuntimeError``.  The whole contract is in ``include/a3vt.h``."""
+    want_touch, want_points = bool(want_touch), bool(want_points)
+    if not want_touch and not want_points:
+        raise ValueError("a3vt: touch_pack: neither want_touch nor want_points")
+    status = _req(out["status"], "status", torch.int32)
+    I, dev, pix = status.shape[0], status.device, TOUCH_RES * TOUCH_RES
+    if status.shape != (I,) or I < 1:
+        raise ValueError(f"a3vt: touch_pack wants status (I,), I >= 1, got {tuple(status.shape)}")
+    touch = points = count = touch_u8 = offsets = cloud = None
+    if want_touch:
+        if "touch" not in out:
+            raise ValueError("a3vt: touch_pack: want_touch, but the render was made without want_touch")
+        touch = _req(out["touch"], "touch")
+        if touch.shape != (I, TOUCH_RES, TOUCH_RES, 3) or touch.device != dev:
+            raise ValueError(f"a3vt: touch_pack wants touch ({I}, {TOUCH_RES}, {TOUCH_RES}, 3) on {dev}, got {tuple(touch.shape)} on "
+                             f"{touch.device}")
+        if touch.data_ptr() % 16:                       # (a view into a larger tensor need not sit on a 16-byte boundary)
+            touch = touch.clone()
+        touch_u8 = torch.empty((I, TOUCH_RES, TOUCH_RES, 3), dtype=torch.uint8, device=dev)
+    if want_points:
+        if "points" not in out or "count" not in out:
+            raise ValueError("a3vt: touch_pack: want_points, but the render was made without want_points")
+        points, count = _req(out["points"], "points"), _req(out["count"], "count", torch.int32)
+        if points.shape != (I, pix, 3) or count.shape != (I,) or points.device != dev or count.device != dev:
+            raise ValueError(f"a3vt: touch_pack wants points ({I}, {pix}, 3) and count ({I},) on {dev}, got {tuple(points.shape)} on "
+                             f"{points.device} and {tuple(count.shape)} on {count.device}")
+        rows = I * pix if capacity is None else int(capacity)
+        if rows < 0:
+            raise ValueError(f"a3vt: touch_pack: capacity={capacity} is negative")
+        offsets = torch.empty(I + 1, dtype=torch.int32, device=dev)
+        cloud = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+    return _touch_pack_into(touch, points, count, status if want_points else None, I, touch_u8, offsets, cloud, capacity is not None)
+
+
+def _touch_pack_into(touch, points, count, status, I, touch_u8, offsets, cloud, bounded):
+    """The library call of ``touch_pack`` into buffers the caller made (tests hand in a pre-filled ``cloud``)."""
+    rows = 0 if cloud is None else cloud.shape[0]
+    _lib.check(_lib.load().a3vt_touch_pack(_lib.ptr(touch), _lib.ptr(points), _lib.ptr(count), _lib.ptr(status), I, rows,
+                                           _lib.ptr(touch_u8), _lib.ptr(offsets), _lib.ptr(cloud) if rows else None, _stream()),
+               "touch_pack")
+    result = {}
+    if touch_u8 is not None:
+        result["touch_u8"] = touch_u8
+    if offsets is not None:
+        result["offsets"], result["cloud"] = offsets, cloud
+        if bounded:
+            total = int(offsets[I].item())
+            if total > rows:
+                raise RuntimeError(f"a3vt: touch_pack: the views hold {total} contact points, more than capacity={rows}; no row of "
+                                   "cloud was written")
+    return result
+
+
+# The reference's vision scene (simulator/rendering/vision_renderer.py:35-77): the camera 0.4243 from the origin and looking at it,
+# pyrender's default background as RENDER_DEFAULTS has it, the object's colour, four point lights (x, y, z, intensity).
+VISION_DEFAULTS = dict(yfov=60.0 / 180.0 * np.pi, znear=0.01, zfar=10.0, width=256, height=256,
+                       cam_pos=(-0.3, 0.0, 0.3), cam_euler_xyz_deg=(45.0, 0.0, 270.0),
+                       lights=((0.0, -0.8, 0.3, 1.0), (0.0, 0.8, 0.3, 1.0), (-1.0, 0.0, 1.0, 1.0), (1.0, 0.0, 1.0, 1.0)),
+                       ambient=0.3, colour=(228, 217, 111), background=(255, 255, 255))
+
 # The reference's camera, lights and colours (utility/pretty_render.py:35-76, :129): what CameraRenderer starts from.
 RENDER_DEFAULTS = dict(yfov=60.0 / 180.0 * np.pi, znear=0.01, zfar=10.0, width=512, height=512,
                        cam_pos=(0.0, 0.6, 0.6), cam_euler_xyz_deg=(45.0, 0.0, 180.0),

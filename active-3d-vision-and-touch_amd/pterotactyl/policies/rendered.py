@@ -16,6 +16,7 @@ The result dict has the reference's keys (its spellings included):
     finger_transfrom_pos     (E, 4, 3) float32
     finger_transform_rot_M   (E, 4, 3, 3) float32
     touch_point_cloud        on request: per element four float32 arrays (n, 3), empty (0, 3) for a finger that is not "touch"
+    vision                   on request: E arrays (H, W, 3) uint8, the object alone under the reference's vision scene
 
 Sources:
 * frames: a mapping ``{(object_id, action): (pos (4, 3), rot (4, 3, 3), present (4,) bool)}`` or a dataset root holding
@@ -27,9 +28,15 @@ Sources:
   ``add_faces`` duplicates are not needed.
 
 ``sample_table(num_actions, fingers=None, to_host=None)`` answers for every action of the loaded objects at once, rendering only the
-fingers asked for, in one call: the table ``ActiveTouch`` builds once per episode under ``args.touch_table``.
+fingers asked for, in one call: the table ``ActiveTouch`` builds once per episode under ``args.touch_table``.  With
+``touch_point_cloud`` or ``as_uint8`` it also carries what a data set stores per view — the uint8 images and the contact clouds packed
+end to end (``ops.touch_pack``, one more launch) — which is what ``data_making.save_touch_signals`` writes.
 
-Out of scope: the grasp physics (frames are an input), the TACTO renderer and vision images."""
+``vision=True`` adds the reference's ``"vision"`` images (``sampler.py:162-173``): all E from one ``ops.scene_render`` call under
+``ops.VISION_DEFAULTS`` (``simulator/rendering/vision_renderer.py:35-77``).  THE SHADING IS NOT PYRENDER'S: it is ``scene_render``'s
+Lambert model on ray-cast hits at pixel centres, and no image of it has been compared with one of pyrender's.
+
+Out of scope: the grasp physics (frames are an input), the TACTO renderer and the hand model (``vision_occluded``)."""
 import os
 from collections.abc import Mapping
 
@@ -39,18 +46,55 @@ import torch
 from .recorded import FINGERS, NO_CONTACT, object_id, table_fingers, tree_frames
 
 RES = 121
+PIXELS = RES * RES
 STATUS = ("no_touch", "touch")          # the library's status codes
 MAX_VIEWS = 1 << 16                     # views of one a3vt_touch_render call (csrc/kernels.h's kTouchMaxImages)
+# Whether ``touch_point_cloud=True`` reads the clouds back packed (``ops.touch_pack``: offsets, then the rows that exist) when the
+# caller does not say: on only where tools/touch_signals_bench.py measured the packed read's p90 below the padded read's p10 at both
+# sizes (profiles/touch_signals_ab.txt).  Measured: 1.49 x at 1 600 views with a fifth of the pixels in contact, no difference at 12
+# views or with every pixel in contact — the rule is not met, the packed read is an option.
+PACK_POINTS_DEFAULT = False
+
+
+def pack_host(out, want_touch=True, want_points=True, capacity=None):
+    """``ops.touch_pack``'s contract on CPU tensors, for a sampler whose ``render`` is a host callable."""
+    result = {}
+    if want_touch:
+        result["touch_u8"] = torch.nan_to_num(out["touch"], nan=0.0).clamp(0, 255).to(torch.uint8)
+    if want_points:
+        rows = torch.where(out["status"] == 1, out["count"].clamp(0, PIXELS), torch.zeros_like(out["count"])).to(torch.int64)
+        result["offsets"] = torch.cat((rows.new_zeros(1), rows.cumsum(0))).to(torch.int32)
+        parts = [out["points"][i, :int(n)] for i, n in enumerate(rows)]
+        result["cloud"] = torch.cat(parts) if parts else out["points"].new_zeros((0, 3))
+    return result
+
+
+def camera_matrix(orientation):
+    """A camera orientation as ``Renderer.update_camera_pose`` takes it (``vision_renderer.py:180-186``): a 3 x 3 matrix, or three
+    xyz Euler angles in degrees."""
+    from ..utility import utils
+    orientation = np.asarray(orientation, np.float64)
+    if orientation.shape == (3,):
+        return utils.euler_matrix(orientation, "xyz", degrees=True)
+    if orientation.shape != (3, 3):
+        raise ValueError(f"RenderedSampler: a camera orientation is a 3 x 3 matrix or three Euler angles, got shape {orientation.shape}")
+    return orientation
 
 
 class RenderedSampler:
     def __init__(self, frames, geometry=None, bs=None, vision=False, render=None, to_host=True, device=None, max_depth=0.025,
-                 yfov=40.0 / 180.0 * np.pi, znear=1e-4, zfar=10.0):
+                 yfov=40.0 / 180.0 * np.pi, znear=1e-4, zfar=10.0, resolution=[256, 256], object_colours=None, render_scene=None,
+                 pack=None, pack_points=None):
         """``frames`` / ``geometry``: the sources described above (``geometry=None``: the ``.npy`` files beside the names).  ``bs``
         and ``vision`` are accepted for the reference's constructor shape and not needed.  ``render``: a callable with the
         signature and result of ``ops.touch_render`` that replaces it — it then gets CPU tensors unless ``device`` says otherwise
         (tests run this class's host logic so).  ``to_host=True`` returns CPU tensors, as ``ActiveTouch`` expects of a sampler;
-        ``to_host=False`` leaves them where the renderer put them."""
+        ``to_host=False`` leaves them where the renderer put them.
+
+        ``resolution`` (width, height) and ``object_colours`` — one RGB(A) colour or one per loaded object, None: the reference's
+        (228, 217, 111); alpha is ignored — are the reference's, for ``vision=True``.  ``render_scene`` / ``pack``: callables that
+        replace ``ops.scene_render`` / ``ops.touch_pack`` (with a ``render`` given, ``pack`` defaults to ``pack_host``).
+        ``pack_points``: whether contact clouds are read back packed; None: ``PACK_POINTS_DEFAULT``.  The results are the same bits."""
         if not isinstance(frames, Mapping) and not os.path.isdir(os.path.join(str(frames), "grasp_info")):
             raise ValueError(f"RenderedSampler: {frames!r} is neither a mapping of frames nor a directory holding grasp_info/")
         if geometry is not None and not isinstance(geometry, Mapping):
@@ -61,9 +105,14 @@ class RenderedSampler:
             from ... import ops
             render = ops.touch_render
             device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.render = render
+            if pack is None:
+                pack = ops.touch_pack
+        self.render, self.render_scene = render, render_scene
+        self.pack = pack_host if pack is None else pack
+        self.pack_points = PACK_POINTS_DEFAULT if pack_points is None else bool(pack_points)
         self.device = torch.device("cpu") if device is None else torch.device(device)
-        self.ids, self.table = [], None
+        self.resolution, self.object_colours = (int(resolution[0]), int(resolution[1])), object_colours
+        self.ids, self.table, self.face_offset = [], None, [0]
 
     def load_objects(self, batch, from_dataset=True, scale=3.1):
         """The batch's meshes as ONE table on the renderer's device (``scale`` is accepted and unused: the stored vertices are
@@ -87,22 +136,71 @@ class RenderedSampler:
         up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype)).to(self.device)  # noqa: E731
         self.table = (up(np.concatenate(verts) if verts else np.zeros((0, 3)), np.float32),
                       up(np.concatenate(faces) if faces else np.zeros((0, 3)), np.int32), up(np.array(offsets), np.int32))
+        self.face_offset = offsets
 
     def frames_of(self, obj, action):
         if isinstance(self.frames, Mapping):
             return self.frames.get((obj, int(action)))
         return tree_frames(str(self.frames), obj, int(action))
 
-    def sample(self, actions, touch=True, touch_point_cloud=False, **unused):
-        return self.sample_many([actions], touch=touch, touch_point_cloud=touch_point_cloud)[0]
+    def vision_images(self, parameters=None):
+        """The ``"vision"`` entry: the loaded objects, each alone under the reference's vision scene, as E images (H, W, 3) uint8
+        from ONE ``ops.scene_render`` call without the primitive image — arrays with ``to_host``, else device tensors.
+        ``parameters``: None, or per element None or a ``(position, orientation)`` pair that moves that element's camera
+        (``camera_matrix`` states the orientation's forms).  Faces are taken as stored: the caster is two-sided.  Lambert shading,
+        not pyrender's."""
+        from ... import ops
+        D, E = ops.VISION_DEFAULTS, len(self.ids)
+        if self.table is None:
+            raise RuntimeError("RenderedSampler: load_objects has not been called")
+        if parameters is not None and len(parameters) != E:
+            raise ValueError(f"RenderedSampler: {len(parameters)} camera parameters for {E} loaded objects")
+        if E == 0:
+            return []
+        cam_pos, cam_rot = np.tile(np.asarray(D["cam_pos"], np.float32), (E, 1)), np.zeros((E, 3, 3), np.float32)
+        cam_rot[:] = camera_matrix(D["cam_euler_xyz_deg"])
+        for e, pair in enumerate(parameters or ()):
+            if pair is not None:
+                cam_pos[e], cam_rot[e] = np.asarray(pair[0], np.float32).reshape(3), camera_matrix(pair[1])
+        colours = np.asarray(D["colour"] if self.object_colours is None else self.object_colours)
+        if colours.ndim == 1:
+            colours = np.tile(colours, (E, 1))
+        if colours.shape not in ((E, 3), (E, 4)):
+            raise ValueError(f"RenderedSampler: object_colours is one RGB(A) colour or one per object ({E}), got shape {colours.shape}")
+        per_face = np.repeat(np.ascontiguousarray(colours[:, :3], np.uint8), np.diff(self.face_offset), axis=0)
+        verts, faces, _ = self.table
+        dev = verts.device
+        render_scene = ops.scene_render if self.render_scene is None else self.render_scene
+        rgb = render_scene(verts, faces, torch.from_numpy(per_face).to(dev), torch.zeros((0, 3), device=dev), torch.zeros(0, device=dev),
+                           torch.zeros((0, 3), dtype=torch.uint8, device=dev), list(self.face_offset), [0] * (E + 1), list(range(E)),
+                           torch.from_numpy(cam_pos).to(dev), torch.from_numpy(cam_rot).to(dev), yfov=D["yfov"], znear=D["znear"],
+                           zfar=D["zfar"], width=self.resolution[0], height=self.resolution[1], lights=D["lights"],
+                           ambient=D["ambient"], background=D["background"], want_prim=False)["rgb"]
+        return list(rgb.cpu().numpy()) if self.to_host else list(rgb)
 
-    def sample_many(self, action_lists, touch=True, touch_point_cloud=False, **unused):
+    def sample(self, actions, touch=True, touch_point_cloud=False, vision=False, vision_occluded=False, parameters=None,
+               pack_points=None, **unused):
+        return self.sample_many([actions], touch=touch, touch_point_cloud=touch_point_cloud, vision=vision,
+                                vision_occluded=vision_occluded, parameters=parameters, pack_points=pack_points)[0]
+
+    def sample_many(self, action_lists, touch=True, touch_point_cloud=False, vision=False, vision_occluded=False, parameters=None,
+                    pack_points=None, **unused):
         """``[sample(actions) for actions in action_lists]`` with all K * E * 4 views rendered in ONE call — what a greedy step's
-        candidate loop asks for.  Every view is rendered on its own, so the results are those of the single calls bit for bit."""
+        candidate loop asks for.  Every view is rendered on its own, so the results are those of the single calls bit for bit.
+        ``vision``: every result carries the same ``"vision"`` list (``vision_images(parameters)``: the images do not depend on the
+        actions, so they are rendered once).  ``pack_points`` (None: the instance's): the clouds reach the host as the offsets
+        table, one small read, and the rows that exist; the padded buffer is not copied."""
+        if vision_occluded:
+            raise NotImplementedError("RenderedSampler: vision_occluded needs the hand model (the reference's objects/hand meshes "
+                                      "posed by the grasp), which this package does not carry")
         K, E = len(action_lists), len(self.ids)
         for actions in action_lists:
             if len(actions) != E:
                 raise ValueError(f"RenderedSampler: {len(actions)} actions for {E} loaded objects")
+        if vision:
+            images = self.vision_images(parameters)
+            return [dict(result, vision=images) for result in self.sample_many(action_lists, touch, touch_point_cloud,
+                                                                               pack_points=pack_points)]
         if not touch:
             return [{} for _ in range(K)]
         if self.table is None:
@@ -149,7 +247,15 @@ class RenderedSampler:
         clouds = None
         if touch_point_cloud:
             clouds = [np.zeros((0, 3), np.float32) if self.to_host else torch.zeros((0, 3), device=where) for _ in range(n)]
-            if out is not None:
+            if out is not None and (self.pack_points if pack_points is None else pack_points):
+                packed = self.pack(out, want_touch=False, want_points=True)
+                offsets = packed["offsets"].cpu().numpy()
+                rows = packed["cloud"][:int(offsets[-1])].to(where)
+                for j, i in enumerate(index):
+                    if status[i] == 1:
+                        cloud = rows[int(offsets[j]):int(offsets[j + 1])]
+                        clouds[i] = cloud.numpy().copy() if self.to_host else cloud
+            elif out is not None:
                 points, count = out["points"].to(where), out["count"].cpu().numpy()
                 for j, i in enumerate(index):
                     if status[i] == 1:
@@ -167,14 +273,21 @@ class RenderedSampler:
             results.append(result)
         return results
 
-    def sample_table(self, num_actions, fingers=None, to_host=None):
+    def sample_table(self, num_actions, fingers=None, to_host=None, touch_point_cloud=False, as_uint8=False):
         """What ``sample`` answers for EVERY action of the loaded objects, as one table (``ActiveTouch`` builds its per-episode touch
         table from it): ``touch_signal`` (E, A, Fs, 121, 121, 3), ``touch_code`` (E, A, Fs) int32 (2 = "touch", 1 = "no_touch", 0 =
         "no_intersection"), ``finger_transfrom_pos`` (E, A, Fs, 3) and ``finger_transform_rot_M`` (E, A, Fs, 3, 3).  Entry [e, a, j]
         is bit for bit what ``sample(actions)`` with ``actions[e] = a`` returns for element e and finger ``fingers[j]`` (indices
         into 0..3; None: all four).  Every grasp's frames are read once, and the live views of the fingers asked for — no others —
         are rendered in ONE call, without contact points.  ``to_host`` None: the instance's setting; False leaves the table on the
-        renderer's device."""
+        renderer's device.
+
+        With ``touch_point_cloud`` or ``as_uint8`` the render also makes the contact points and ONE ``ops.touch_pack`` launch
+        follows it; the table then carries as well ``touch_u8`` (E, A, Fs, 121, 121, 3) uint8 — ``touch_signal`` truncated, as a data
+        set stores it —, ``cloud_offsets`` (E * A * Fs + 1,) int32 and ``cloud`` (total, 3) float32: view v = (e * A + a) * Fs + j
+        owns the rows ``[cloud_offsets[v], cloud_offsets[v + 1])``, ``sample``'s ``touch_point_cloud`` of that finger bit for bit
+        (no rows unless its code is 2).  On the device ``cloud`` keeps its worst-case rows; only the first ``cloud_offsets[-1]``
+        are written.  On the host it is cut to them."""
         fingers = table_fingers(fingers)
         E, A, Fs = len(self.ids), int(num_actions), len(fingers)
         if self.table is None:
@@ -201,9 +314,28 @@ class RenderedSampler:
         out = None
         if len(index):
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
-            out = self.render(*self.table, up(mesh_of[index]), up(pos[index]), up(rot[index]), want_touch=True, want_points=False,
-                              **self.camera)
+            out = self.render(*self.table, up(mesh_of[index]), up(pos[index]), up(rot[index]), want_touch=True,
+                              want_points=bool(touch_point_cloud or as_uint8), **self.camera)
         where = torch.device("cpu") if to_host or out is None else out["touch"].device
+        extra = {}
+        if touch_point_cloud or as_uint8:
+            if out is None:
+                extra = {"touch_u8": torch.zeros((E, A, Fs, RES, RES, 3), dtype=torch.uint8, device=where),
+                         "cloud_offsets": torch.zeros(n + 1, dtype=torch.int32, device=where), "cloud": torch.zeros((0, 3), device=where)}
+            else:
+                packed = self.pack(out, want_touch=True, want_points=True)
+                offsets, small, cloud = packed["offsets"], packed["touch_u8"], packed["cloud"]
+                if len(index) != n:                                  # a view that was not rendered owns no rows and a zero image
+                    live_before = torch.searchsorted(torch.from_numpy(index).to(offsets.device),
+                                                     torch.arange(n + 1, device=offsets.device))
+                    offsets = offsets[live_before]
+                    small = torch.zeros((n, RES, RES, 3), dtype=torch.uint8, device=small.device)
+                    small[torch.from_numpy(index).to(small.device)] = packed["touch_u8"]
+                if to_host:
+                    offsets = offsets.cpu()
+                    cloud = cloud[:int(offsets[-1])].cpu()
+                    small = small.cpu()
+                extra = {"touch_u8": small.reshape(E, A, Fs, RES, RES, 3), "cloud_offsets": offsets, "cloud": cloud}
         if len(index) == n:
             signal, code = out["touch"].to(where), out["status"].to(where).to(torch.int32) + 1
         else:                                                        # zeros and code 0 at the views that were not rendered
@@ -215,7 +347,7 @@ class RenderedSampler:
                 code[index_t] = out["status"].to(where).to(torch.int32) + 1  # the library's 0 / 1 -> "no_touch" 1 / "touch" 2
         return {"touch_signal": signal.reshape(E, A, Fs, RES, RES, 3), "touch_code": code.reshape(E, A, Fs),
                 "finger_transfrom_pos": torch.from_numpy(pos).to(where).reshape(E, A, Fs, 3),
-                "finger_transform_rot_M": torch.from_numpy(rot).to(where).reshape(E, A, Fs, 3, 3)}
+                "finger_transform_rot_M": torch.from_numpy(rot).to(where).reshape(E, A, Fs, 3, 3), **extra}
 
     def disconnect(self):
         pass

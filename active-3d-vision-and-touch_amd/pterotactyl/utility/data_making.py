@@ -1,10 +1,16 @@
 """Drop-in for the mesh half of ``pterotactyl/utility/data_making.py``: from object files to the ``_verts.npy`` / ``_faces.npy`` pairs
 and the ground-truth clouds ``point_cloud_info/<obj>.npy`` that every loader of ``data_loaders.py`` asks for.
 
-Reference symbols mirrored: ``extract_points`` :50-72, ``save_object_info`` :76-95 (without the URDF), ``save_point_info`` :99-118.
-``make_data_split`` and ``save_simulation`` are not here.  This package's own: ``extract_points_batch``, one pass of the kernels
-over many meshes; ``touch_charts_batch`` / ``save_touch_info``, which write ``touch_charts/<obj>/touch_charts.npy`` from an
-object's finger frames (the reference has no writer for that file: it comes with its download).
+Reference symbols mirrored: ``make_data_split`` :22-46, ``extract_points`` :50-72, ``save_object_info`` :76-95 (without the URDF),
+``save_point_info`` :99-118, and of ``save_simulation`` :122-209 what follows the grasp: ``save_image_info`` (the vision image,
+:157-166) and ``save_touch_signals`` (the touch records, :186-199).  The grasp physics is not here: the finger frames
+``<action>/<finger>_ref_frame.npy`` are an input.  This package's own: ``extract_points_batch``, one pass of the kernels over many
+meshes; ``touch_charts_batch`` / ``save_touch_info``, which write ``touch_charts/<obj>/touch_charts.npy`` from an object's finger
+frames (the reference has no writer for that file: it comes with its download).
+
+The chain from object files to a tree that ``data_loaders.py``'s three loaders and the trainers read: ``save_object_info`` ->
+``save_point_info`` -> ``save_image_info`` -> frames from a simulator -> ``save_touch_signals`` -> ``save_touch_info`` ->
+``make_data_split``.
 
 The cloud of a mesh is the reference's, row for row: voxelise by adaptive subdivision, carve with the six depth maps, take the
 surface voxels, realign them to the mesh (``a3vt_voxel_surface`` / ``a3vt_voxel_points``, csrc/voxel.hip, for GPU tensors; the
@@ -12,6 +18,7 @@ same contract on NumPy for CPU tensors), double the cloud until it has ``num_poi
 ``np.random.choice(n, num_points, replace=False)`` — the reference's own call, so a seeded NumPy gives the reference's cloud.
 """
 import os
+import random
 from glob import glob
 
 import numpy as np
@@ -200,6 +207,197 @@ def save_touch_info(data_root, encoder=None, touch_location=None, sampler="rende
             for name, value in (("touch", 2), ("no_touch", 1), ("no_intersection", 0)):
                 counts[name] += int((code == value).sum())
     return counts
+
+
+def _save_atomic(directory, name, array):
+    """``<directory>/<name>`` under a temporary name in the same directory, then renamed: no reader ever sees half a file."""
+    temporary = os.path.join(directory, f".{name}.{os.getpid()}.tmp")
+    try:
+        with open(temporary, "wb") as f:
+            np.save(f, array)
+        os.replace(temporary, os.path.join(directory, name))
+    finally:
+        if os.path.exists(temporary):
+            os.remove(temporary)
+
+
+def _object_ids(data_root):
+    return sorted(os.path.basename(f)[:-len("_verts.npy")] for f in glob(os.path.join(data_root, "object_info", "*_verts.npy")))
+
+
+def save_image_info(data_root, batch=16, overwrite=False, resolution=(256, 256), colour=_ops.VISION_DEFAULTS["colour"], device=None,
+                    sampler=None):
+    """``<data_root>/images_colourful/<id>.npy`` — the (height, width, 3) uint8 image ``mesh_loader_vision`` / ``_active`` read and
+    whose presence all three loaders take as "this object exists" — for every ``_verts.npy`` / ``_faces.npy`` pair of
+    ``<data_root>/object_info/``, in sorted order of the ids, ``batch`` objects per ``ops.scene_render`` call (at most 128: that
+    call's images per launch) and one host read per batch.  The image is ``RenderedSampler``'s ``"vision"``: the object alone under
+    the reference's vision scene (``ops.VISION_DEFAULTS``), with ``scene_render``'s Lambert shading, NOT pyrender's — a model
+    trained on the reference's images has not been evaluated on these.  ``sampler``: an object with ``load_objects`` and
+    ``vision_images`` in place of the ``RenderedSampler`` made here.  Existing files are kept unless ``overwrite``; each file is
+    written under a temporary name and renamed.
+
+    Returns the counts ``written``, ``skipped_existing`` and ``skipped_no_surface`` (objects without faces)."""
+    from ..policies import rendered
+    batch = max(int(batch), 1)
+    if batch > 128:
+        raise ValueError(f"a3vt: save_image_info batch={batch} is more than the 128 images of one scene_render launch")
+    object_dir, image_dir = os.path.join(data_root, "object_info"), os.path.join(data_root, "images_colourful")
+    counts = dict(written=0, skipped_existing=0, skipped_no_surface=0)
+    todo = []
+    for obj in _object_ids(data_root):
+        faces = os.path.join(object_dir, f"{obj}_faces.npy")
+        if not os.path.exists(faces):
+            continue
+        if np.load(faces, mmap_mode="r").size == 0:
+            counts["skipped_no_surface"] += 1
+        elif not overwrite and os.path.exists(os.path.join(image_dir, f"{obj}.npy")):
+            counts["skipped_existing"] += 1
+        else:
+            todo.append(obj)
+    if not todo:
+        return counts
+    os.makedirs(image_dir, exist_ok=True)
+    if sampler is None:
+        sampler = rendered.RenderedSampler({}, to_host=True, resolution=list(resolution), object_colours=colour,
+                                           device=utils._device() if device is None else torch.device(device))
+    for at in range(0, len(todo), batch):
+        group = todo[at:at + batch]
+        sampler.load_objects([os.path.join(object_dir, obj) for obj in group])
+        for obj, image in zip(group, sampler.vision_images()):
+            _save_atomic(image_dir, f"{obj}.npy", np.ascontiguousarray(image, dtype=np.uint8))
+            counts["written"] += 1
+    return counts
+
+
+# Whether save_touch_signals reads the batch's clouds and images back packed (ops.touch_pack) when the caller does not say: the
+# rule and the measurement of rendered.PACK_POINTS_DEFAULT (profiles/touch_signals_ab.txt), which is not met.  (The same file has
+# the bake itself at 8 objects: 68 ms packed against 303 ms padded before the file writes, 291 against 540 with them.)
+BAKE_PACK_POINTS = False
+BAKING_MARKER = ".baking"
+
+
+def _touch_records(sampler, names, num_actions, pack_points):
+    """One batch of ``save_touch_signals`` -> ``(codes (E, A, 4) int array, {(e, a, finger): (image uint8 (121, 121, 3), points
+    float32 (n, 3))})`` for the views whose code is 2.  Packed: one table call and two host reads — the codes with the offsets,
+    then ONE buffer holding the clouds' rows and the "touch" views' uint8 images.  Otherwise the calls the package had before
+    ``ops.touch_pack``: the float table, truncated here, and ``sample_many`` with the padded points buffer."""
+    sampler.load_objects(names)
+    E, A, F = len(names), num_actions, 4
+    if not pack_points:
+        table = sampler.sample_table(A, fingers=None, to_host=True)
+        codes = table["touch_code"].numpy()
+        images = table["touch_signal"].numpy().astype(np.uint8)
+        clouds = sampler.sample_many([[a] * E for a in range(A)], touch=True, touch_point_cloud=True, pack_points=False)
+        return codes, {(e, a, j): (images[e, a, j], np.asarray(torch.as_tensor(clouds[a]["touch_point_cloud"][e][j]).cpu().numpy(), np.float32))
+                       for e, a, j in zip(*np.nonzero(codes == 2))}
+    table = sampler.sample_table(A, fingers=None, to_host=False, touch_point_cloud=True, as_uint8=True)
+    n = E * A * F
+    small = torch.cat((table["touch_code"].reshape(-1).to(torch.int32), table["cloud_offsets"].to(torch.int32))).cpu().numpy()   # read 1
+    codes, offsets = small[:n].reshape(E, A, F), small[n:]
+    views = np.flatnonzero(small[:n] == 2)
+    total = int(offsets[-1])
+    pick = torch.from_numpy(views).to(table["touch_u8"].device)
+    payload = torch.cat((table["cloud"][:total].reshape(-1).view(torch.uint8),
+                         table["touch_u8"].reshape(n, -1)[pick].reshape(-1))).cpu().numpy()                                       # read 2
+    cloud = payload[:total * 12].view(np.float32).reshape(total, 3)
+    images = payload[total * 12:].reshape(len(views), 121, 121, 3)
+    return codes, {(v // (A * F), v // F % A, v % F): (images[k], cloud[offsets[v]:offsets[v + 1]]) for k, v in enumerate(views)}
+
+
+def save_touch_signals(data_root, batch=8, num_actions=50, overwrite=False, device=None, sampler=None, pack_points=None, write=True):
+    """The touch records of a data set — the part of the reference's ``save_simulation`` that follows the grasp (:186-199): for every
+    object of ``<data_root>/object_info/`` with a ``<data_root>/grasp_info/<id>/`` directory, ``<action>/<finger>_touch.npy``
+    (121, 121, 3) uint8 and ``<action>/<finger>_points.npy`` (n, 3) for the fingers whose status is "touch", and for no other
+    finger — what ``mesh_loader_touch`` reads.  The signals are rendered from the object's triangles and the frames
+    ``<action>/<finger>_ref_frame.npy`` (``RenderedSampler``), which are read and never written.  ``batch`` objects per pass, in
+    sorted order of the ids: one ``load_objects``, one ``sample_table`` call (two render launches and one ``ops.touch_pack``
+    launch) and two host reads.
+
+    Deviation: the points are stored as float32, the renderer's own values.  The reference stores NumPy's float64, and the loader
+    converts to float32 at once (``standerdize_point_size``).
+
+    A downloaded data set's files are never silently replaced: without ``overwrite``, an object that already holds any
+    ``*_touch.npy`` or ``*_points.npy`` is skipped whole (``skipped_existing``).  While an object's files are being written a
+    marker ``grasp_info/<id>/.baking`` exists; it is removed after the last rename.  An object found with the marker counts as not
+    yet written: its records are removed and written again.  (So are, under ``overwrite``, those of any object.)  An object
+    none of whose fingers touches leaves no file, and a later run renders it again.
+
+    ``sampler``: an object with ``load_objects``, ``sample_table`` and ``sample_many`` in place of the ``RenderedSampler`` made
+    here.  ``pack_points`` None: ``BAKE_PACK_POINTS``; the files are the same bytes either way.  ``write=False`` does everything
+    but touch the tree (for measuring).
+
+    Returns the counts ``written``, ``skipped_existing``, ``skipped_no_grasps`` (objects) and ``views``, ``touch``, ``no_touch``,
+    ``no_intersection`` (the views of the written objects by their status)."""
+    from ..policies import recorded, rendered
+    batch, num_actions = max(int(batch), 1), int(num_actions)
+    if batch * num_actions * recorded.FINGERS > rendered.MAX_VIEWS:
+        raise ValueError(f"a3vt: save_touch_signals batch={batch} x num_actions={num_actions} x {recorded.FINGERS} fingers is "
+                         f"{batch * num_actions * recorded.FINGERS} views, more than the {rendered.MAX_VIEWS} of one pass")
+    object_dir, grasp_dir = os.path.join(data_root, "object_info"), os.path.join(data_root, "grasp_info")
+    counts = dict(written=0, skipped_existing=0, skipped_no_grasps=0, views=0, touch=0, no_touch=0, no_intersection=0)
+    records = lambda obj: [f for kind in ("touch", "points") for f in glob(os.path.join(grasp_dir, obj, "*", f"*_{kind}.npy"))]  # noqa: E731
+    todo = []
+    for obj in _object_ids(data_root):
+        if not os.path.isdir(os.path.join(grasp_dir, obj)):
+            counts["skipped_no_grasps"] += 1
+        elif not overwrite and not os.path.exists(os.path.join(grasp_dir, obj, BAKING_MARKER)) and records(obj):
+            counts["skipped_existing"] += 1
+        else:
+            todo.append(obj)
+    if not todo:
+        return counts
+    pack_points = BAKE_PACK_POINTS if pack_points is None else bool(pack_points)
+    if sampler is None:                                 # (padded: the sampler copies the buffers whole and slices them on the host)
+        sampler = rendered.RenderedSampler(data_root, to_host=not pack_points,
+                                           device=utils._device() if device is None else torch.device(device))
+    for at in range(0, len(todo), batch):
+        group = todo[at:at + batch]
+        codes, found = _touch_records(sampler, [os.path.join(object_dir, obj) for obj in group], num_actions, pack_points)
+        for e, obj in enumerate(group):
+            if write:
+                with open(os.path.join(grasp_dir, obj, BAKING_MARKER), "w"):
+                    pass
+                for stale in records(obj):
+                    os.remove(stale)
+                for (_, a, j), (image, points) in sorted((kv for kv in found.items() if kv[0][0] == e), key=lambda kv: kv[0]):
+                    directory = os.path.join(grasp_dir, obj, str(a))
+                    os.makedirs(directory, exist_ok=True)
+                    _save_atomic(directory, f"{j}_touch.npy", np.ascontiguousarray(image, dtype=np.uint8))
+                    _save_atomic(directory, f"{j}_points.npy", np.ascontiguousarray(points, dtype=np.float32))
+                os.remove(os.path.join(grasp_dir, obj, BAKING_MARKER))
+            counts["written"] += 1
+            counts["views"] += codes[e].size
+            for name, value in (("touch", 2), ("no_touch", 1), ("no_intersection", 0)):
+                counts[name] += int((codes[e] == value).sum())
+    return counts
+
+
+SPLIT_SETS = ("recon_train", "auto_train", "RL_train", "valid", "test")
+SPLIT_SIZES = (7700, 7700, 7700, 2000, 1000)            # the reference's (:34-38)
+
+
+def make_data_split(data_root, sizes=None, destination=None):
+    """The reference's split rule (:22-46) over a tree's own objects: the ids of ``<data_root>/object_info/*_verts.npy`` (the
+    reference takes them from ``initial_objects/*``), sorted as strings, shuffled by ``random.Random(0).shuffle`` and cut
+    consecutively into ``recon_train``, ``auto_train``, ``RL_train``, ``valid`` and ``test`` of ``sizes`` objects (None: the
+    reference's 7700 / 7700 / 7700 / 2000 / 1000).  A tree with fewer ids than the sizes sum to raises ``ValueError`` — the
+    reference's slices would silently come out short or empty.  Writes the dict, pickled, to ``destination`` (None:
+    ``<data_root>/data_split.npy``, the file ``data_loaders.load_split`` reads) and returns it."""
+    sizes = SPLIT_SIZES if sizes is None else tuple(int(s) for s in sizes)
+    if len(sizes) != len(SPLIT_SETS) or min(sizes) < 0:
+        raise ValueError(f"a3vt: make_data_split wants {len(SPLIT_SETS)} sizes >= 0 for {SPLIT_SETS}, got {sizes}")
+    ids = _object_ids(data_root)
+    if len(ids) < sum(sizes):
+        raise ValueError(f"a3vt: make_data_split: {data_root!r} holds {len(ids)} objects, fewer than the {sum(sizes)} that the sets "
+                         f"{dict(zip(SPLIT_SETS, sizes))} take: pass `sizes` that fit the tree")
+    ids.sort()
+    random.Random(0).shuffle(ids)
+    cuts = np.concatenate(([0], np.cumsum(sizes)))
+    split = {name: ids[cuts[k]:cuts[k + 1]] for k, name in enumerate(SPLIT_SETS)}
+    destination = os.path.join(data_root, "data_split.npy") if destination is None else destination
+    with open(destination, "wb") as f:
+        np.save(f, split, allow_pickle=True)
+    return split
 
 
 def save_point_info(object_dir, point_dir, batch=16, dim=128, num_points=30000, device=None):

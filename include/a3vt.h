@@ -732,6 +732,36 @@ int a3vt_touch_finish(const float *depth, const float *cam_pos, const float *cam
                       float *points, int32_t *count, int32_t *status, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The outputs of a3vt_touch_render / a3vt_touch_finish for I views in the form a data set stores them (the reference's
+ * save_simulation, utility/data_making.py:186-199): images as uint8, contact clouds without their padding.
+ *   touch    [I][121][121][3] fp32, or NULL       with touch_u8 [I][121][121][3] uint8 out: both or neither
+ *   points   [I][14641][3] fp32, count [I] int32, status [I] int32, or all three NULL
+ *            with offsets [I + 1] int32 out and cloud [capacity][3] fp32 out: all five or none
+ *
+ * - touch_u8 is each value clamped to [0, 255], then truncated toward zero; NaN gives 0 (so does -0).  For the values
+ *   a3vt_touch_finish writes (0 <= v <= 255) that is C's (uint8_t) v, tensor.to(torch.uint8) and NumPy's .astype(np.uint8).
+ * - n_i = count[i] where status[i] == 1, else 0; a count outside 0..14641 is clamped into it.  offsets is the exclusive prefix sum
+ *   of n: offsets[0] = 0, offsets[I] the total.  I * 14641 <= 65536 * 14641 < 2^31.
+ * - Rows [offsets[i], offsets[i + 1]) of cloud are points[i][0 .. n_i) in order, as 32-bit patterns unchanged.  Rows from
+ *   offsets[I] on are not written (a3vt_touch_render's own convention for points).
+ * - If offsets[I] > capacity, offsets is written in full and NO row of cloud is written: the caller reads offsets[I] and knows.
+ *
+ * One launch on `stream`.  No allocation, no host synchronisation, no atomics, no fence between workgroups, no workspace, no
+ * environment variable: every workgroup that copies forms its prefix from count and status itself, in integers, so the result does
+ * not depend on the launch geometry and is the same bits on every call.  No input is written; outputs must not overlap inputs.
+ *
+ * Limits.
+ * - 1 <= I <= 65536; 0 <= capacity.
+ * - touch is 16-byte aligned, every other pointer 4-byte aligned.  cloud may be NULL when capacity == 0.
+ * - Both groups NULL, a group given in part, or anything else outside the limits returns non-zero with a message in
+ *   a3vt_last_error that names touch_pack, the argument and its value.  Nothing is launched.
+ *
+ * a3vt_touch_pack_launches: [0] the a3vt_touch_pack calls that launched since the last reset; returns 1. */
+int a3vt_touch_pack(const float *touch, const float *points, const int32_t *count, const int32_t *status, int I, int capacity,
+                    uint8_t *touch_u8, int32_t *offsets, float *cloud, void *stream);
+int a3vt_touch_pack_launches(long long *counts /*[1]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The ground-truth point cloud of a mesh: utility/data_making.py::extract_points (mesh_to_voxel, extract_ODMs, apply_ODMs,
  * voxel_to_pointcloud, realign_points of utility/utils.py) for a batch of M meshes.
  *
