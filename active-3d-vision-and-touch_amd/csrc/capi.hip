@@ -1581,6 +1581,158 @@ int a3vt_touch_pack(const float *touch, const float *points, const int32_t *coun
 
 int a3vt_touch_pack_launches(long long *counts, int reset) { return g_touch_pack_launches.read(counts, reset); }
 
+// ---- the finger closing of the kinematic grasp (grasp_close.hip) -------------------------------------------------------------------
+namespace {
+LaunchCounts<2> g_grasp_launches;
+
+// The HOST hand table (28 x 26 doubles) and rest angles as the kernel's argument block: 0, or -1 with the message set.
+int grasp_hand(const char *who, const double *table, const double *q0, int steps, GraspHand *hand) {
+  auto finite = [](double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; };
+  for (int row = 0; row < kGraspLinks; ++row) {
+    const double *t = table + row * kGraspTableCols;
+    for (int col = 0; col < kGraspTableCols; ++col) {
+      if (!finite(t[col])) {
+        set_error("%s: hand_table[%d][%d]=%g is not finite", who, row, col, t[col]);
+        return -1;
+      }
+    }
+    const int c = row / kGraspChain, k = row % kGraspChain;
+    const int parent = (int)t[0], want_parent_lo = k == 0 ? -1 : c * kGraspChain, want_parent_hi = k == 0 ? -1 : row - 1;
+    if ((double)parent != t[0] || parent < want_parent_lo || parent > want_parent_hi) {
+      set_error("%s: hand_table[%d][0]=%g: the parent of link %d of chain %d must lie in %d..%d", who, row, t[0], k, c, want_parent_lo,
+                want_parent_hi);
+      return -1;
+    }
+    const double want_type = k < kGraspJoints ? 1.0 : 0.0;
+    if (t[1] != want_type) {
+      set_error("%s: hand_table[%d][1]=%g: link %d of a chain must be %s", who, row, t[1], k, k < kGraspJoints ? "revolute (1)" : "fixed (0)");
+      return -1;
+    }
+    const double axis2 = t[14] * t[14] + t[15] * t[15] + t[16] * t[16];
+    if (t[1] != 0.0 && !(axis2 > 0.999 && axis2 < 1.001)) {
+      set_error("%s: hand_table[%d][14..16]: the axis has squared length %g, not 1", who, row, axis2);
+      return -1;
+    }
+    if (t[17] > t[18]) {
+      set_error("%s: hand_table[%d][17]=%g (lower) is above [18]=%g (upper)", who, row, t[17], t[18]);
+      return -1;
+    }
+    if ((t[19] != 0.0 && t[19] != 1.0) || t[23] < 0.0 || t[24] < 0.0 || t[25] < 0.0) {
+      set_error("%s: hand_table[%d][19]=%g must be 0 or 1 and the half-extents [23..25] must not be negative", who, row, t[19]);
+      return -1;
+    }
+    if (q0 && !finite(q0[row])) {
+      set_error("%s: q0[%d]=%g is not finite", who, row, q0[row]);
+      return -1;
+    }
+    GraspLink &L = hand->link[row];
+    for (int i = 0; i < 3; ++i) L.xyz[i] = (float)t[2 + i], L.axis[i] = (float)t[14 + i], L.bc[i] = (float)t[20 + i], L.bh[i] = (float)t[23 + i];
+    for (int i = 0; i < 9; ++i) L.rot[i] = (float)t[5 + i];
+    const double rest = q0 ? q0[row] : 0.0;
+    L.q0 = (float)rest;
+    L.upper = (float)t[18];
+    L.delta = (float)((t[18] - rest) / (double)steps);
+    L.parent = parent < 0 ? -1 : parent - c * kGraspChain;
+    L.revolute = t[1] != 0.0;
+    L.has_box = t[19] != 0.0;
+  }
+  // reach: a link's origin is no further from the chain's first joint than the joint offsets on its path sum to, and no point of
+  // its box further from the origin than |centre| + |half|
+  auto norm = [](const double *v) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+  for (int c = 0; c < kGraspFingers; ++c) {
+    double path[kGraspChain] = {0.0}, reach = 0.0;
+    for (int k = 0; k < kGraspChain; ++k) {
+      const double *t = table + (c * kGraspChain + k) * kGraspTableCols;
+      if (k > 0) path[k] = path[(int)t[0] - c * kGraspChain] + norm(t + 2);
+      if (t[19] != 0.0) reach = fmax(reach, path[k] + norm(t + 20) + norm(t + 23));
+    }
+    hand->reach[c] = (float)(reach * (1.0 + 1e-6));
+  }
+  return 0;
+}
+}  // namespace
+
+int a3vt_grasp_close(const float *verts, int V, const int32_t *faces, int F, const int32_t *face_offset, int M, const int32_t *grasp_mesh,
+                     const float *base_pos, const float *base_rot, int G, const double *hand_table, const double *q0, int steps,
+                     float *q_out, int32_t *blocked_step, float *link_pos, float *link_rot, float *frame_pos, float *frame_rot,
+                     void *stream) {
+  const char *who = "grasp_close";
+  if (check_range(who, "G", G, 0, kGraspMaxGrasps) || check_range(who, "M", M, 1, kGraspMaxMeshes) ||
+      check_range(who, "V", V, 0, kGraspMaxIndex) || check_range(who, "F", F, 0, kGraspMaxIndex) ||
+      check_range(who, "steps", steps, 1, kGraspMaxSteps))
+    return -1;
+  if (check_ptrs(who, {{"verts", verts, V > 0, 4, "required when V > 0"},
+                       {"faces", faces, F > 0, 4, "required when F > 0"},
+                       {"face_offset", face_offset, true, 4, "required (a host table)"},
+                       {"grasp_mesh", grasp_mesh, G > 0, 4, "required when G > 0 (a host table)"},
+                       {"base_pos", base_pos, G > 0, 4, "required when G > 0"},
+                       {"base_rot", base_rot, G > 0, 4, "required when G > 0"},
+                       {"hand_table", hand_table, true, 8, "required (a host table)"},
+                       {"q0", q0, true, 8, "required (a host table)"},
+                       {"q_out", q_out, G > 0, 4, "required when G > 0"},
+                       {"blocked_step", blocked_step, G > 0, 4, "required when G > 0"},
+                       {"link_pos", link_pos, G > 0, 4, "required when G > 0"},
+                       {"link_rot", link_rot, G > 0, 4, "required when G > 0"},
+                       {"frame_pos", frame_pos, G > 0, 4, "required when G > 0"},
+                       {"frame_rot", frame_rot, G > 0, 4, "required when G > 0"}}))
+    return -1;
+  // the host tables' contents
+  if (face_offset[0] < 0) {
+    set_error("%s: face_offset[0]=%d is below 0", who, (int)face_offset[0]);
+    return -1;
+  }
+  for (int m = 0; m < M; ++m) {
+    if (face_offset[m + 1] < face_offset[m]) {
+      set_error("%s: face_offset[%d]=%d is below face_offset[%d]=%d: offsets must not decrease", who, m + 1, (int)face_offset[m + 1], m,
+                (int)face_offset[m]);
+      return -1;
+    }
+  }
+  if (face_offset[M] > F) {
+    set_error("%s: face_offset[%d]=%d runs past F=%d", who, M, (int)face_offset[M], F);
+    return -1;
+  }
+  for (int g = 0; g < G; ++g) {
+    if (grasp_mesh[g] < 0 || grasp_mesh[g] >= M) {
+      set_error("%s: grasp_mesh[%d]=%d outside 0..%d", who, g, (int)grasp_mesh[g], M - 1);
+      return -1;
+    }
+  }
+  GraspHand hand;
+  if (grasp_hand(who, hand_table, q0, steps, &hand)) return -1;
+  if (G == 0) return 0;
+  int32_t *range = static_cast<int32_t *>(malloc(sizeof(int32_t) * 2 * (size_t)G));
+  if (!range) {
+    set_error("%s: no host memory for the ranges of G=%d grasps", who, G);
+    return -1;
+  }
+  for (int g = 0; g < G; ++g) {
+    range[g] = face_offset[grasp_mesh[g]];
+    range[G + g] = face_offset[grasp_mesh[g] + 1];
+  }
+  const int rc = launch_grasp_close(verts, V, faces, range, range + G, base_pos, base_rot, G, hand, steps, q_out, blocked_step, link_pos,
+                                    link_rot, frame_pos, frame_rot, static_cast<hipStream_t>(stream));
+  free(range);
+  if (rc < 0) return rc;
+  g_grasp_launches.add(0, 1);
+  g_grasp_launches.add(1, rc);
+  return 0;
+}
+
+int a3vt_grasp_limit(int which) { return which == 0 ? kGraspCapacity : which == 1 ? kGraspPerLaunch : which == 2 ? kGraspTableCols : 0; }
+
+double a3vt_grasp_reach(const double *hand_table, int chain) {
+  GraspHand hand;
+  if (!hand_table || chain < 0 || chain >= kGraspFingers) {
+    set_error("grasp_reach: hand_table=%p chain=%d: a table and a chain in 0..%d", (const void *)hand_table, chain, kGraspFingers - 1);
+    return -1.0;
+  }
+  if (grasp_hand("grasp_reach", hand_table, nullptr, 1, &hand)) return -1.0;
+  return (double)hand.reach[chain];
+}
+
+int a3vt_grasp_launches(long long *counts, int reset) { return g_grasp_launches.read(counts, reset); }
+
 // ---- mesh and point-cloud rendering (scene_render.hip) -----------------------------------------------------------------------------
 namespace {
 LaunchCounts<2> g_scene_launches;

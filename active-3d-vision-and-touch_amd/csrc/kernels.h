@@ -419,6 +419,33 @@ int launch_touch_finish(const float *depth, const float *cam_pos, const float *c
 int launch_touch_pack(const float *touch, const float *points, const int32_t *count, const int32_t *status, int I, int capacity,
                       uint8_t *touch_u8, int32_t *offsets, float *cloud, hipStream_t s);
 
+// grasp_close.hip: the finger closing of the kinematic grasp (simulator/physics/grasping.py) — one workgroup per (grasp, finger),
+// 4 * steps sequential box-against-triangles queries each.  The hand table and the launch's face ranges travel by value in the
+// kernel arguments: the host has checked them.
+constexpr int kGraspFingers = 4, kGraspChain = 7, kGraspJoints = 4;   // chains; links of a chain; its leading revolute joints
+constexpr int kGraspLinks = kGraspFingers * kGraspChain;
+constexpr int kGraspTableCols = 26;           // a3vt_grasp_close's hand_table (include/a3vt.h)
+constexpr int kGraspCapacity = 3072;          // candidate triangles held in LDS: 108 KiB of the CU's 160, one workgroup per CU
+constexpr int kGraspPerLaunch = 64;           // grasps of one launch (8 bytes each of the kernel-argument block): 256 workgroups
+constexpr int kGraspMaxGrasps = 1 << 20, kGraspMaxMeshes = 1 << 20, kGraspMaxIndex = 1 << 28, kGraspMaxSteps = 1 << 16;
+struct GraspLink {
+  float xyz[3], rot[9], axis[3];              // the joint's origin in the parent's frame; its (unit) axis
+  float q0, delta, upper;                     // rest angle, (upper - q0) / steps, upper limit (revolute links)
+  float bc[3], bh[3];                         // the collision box: centre and half-extents in the link's frame
+  int32_t parent, revolute, has_box;          // parent: index within the chain, -1 = the hand's base
+};
+struct GraspHand {
+  GraspLink link[kGraspLinks];
+  float reach[kGraspFingers];                 // no point of a chain's boxes is further than this from the chain's first joint
+};
+struct GraspRanges {
+  int32_t f0[kGraspPerLaunch], f1[kGraspPerLaunch];   // a grasp's faces f0 .. f1 - 1
+};
+// f0 / f1: G entries each on the HOST.  Returns the number of launches, or a negative error code with the message set.
+int launch_grasp_close(const float *verts, int V, const int32_t *faces, const int32_t *f0, const int32_t *f1, const float *base_pos,
+                       const float *base_rot, int G, const GraspHand &hand, int steps, float *q_out, int32_t *blocked_step, float *link_pos,
+                       float *link_rot, float *frame_pos, float *frame_rot, hipStream_t s);
+
 // scene_render.hip: colour, depth and primitive-index images of triangle + sphere scenes (utility/pretty_render.py's job): a ray
 // cast per pixel with Lambert shading, one launch per kSceneImagesPerLaunch images.  The small tables travel by value in the kernel
 // arguments: the host has checked them, and nothing on the device has to be trusted or clamped.

@@ -1600,6 +1600,234 @@ def _touch_pack_into(touch, points, count, status, I, touch_u8, offsets, cloud, 
     return result
 
 
+# ---- the finger closing of the kinematic grasp (csrc/grasp_close.hip; the rule is stated in include/a3vt.h) ----
+GRASP_FINGERS, GRASP_CHAIN, GRASP_JOINTS, GRASP_TABLE_COLS = 4, 7, 4, 26     # csrc/kernels.h's kGrasp*
+GRASP_LINKS = GRASP_FINGERS * GRASP_CHAIN
+GRASP_MIN_AXIS2 = 1e-24                                                     # a cross-product axis shorter than this (squared) is skipped
+GRASP_SLACK = 1e-4                                                          # csrc/grasp_close.hip's kGraspSlack
+
+
+def grasp_launches(reset=False):
+    """``a3vt_grasp_close`` calls that launched since the last reset, and the kernels they launched (a test hook)."""
+    return _launch_counts("a3vt_grasp_launches", ("calls", "launches"), reset)
+
+
+def grasp_limits():
+    """``capacity`` (candidate triangles a workgroup of ``a3vt_grasp_close`` holds in LDS), ``per_launch`` (grasps of one launch)
+    and ``table_cols``, from the library."""
+    L = _lib.load()
+    return dict(capacity=L.a3vt_grasp_limit(0), per_launch=L.a3vt_grasp_limit(1), table_cols=L.a3vt_grasp_limit(2))
+
+
+def _grasp_tables(hand_table, q0):
+    table = np.ascontiguousarray(hand_table.cpu().numpy() if isinstance(hand_table, torch.Tensor) else hand_table, np.float64)
+    rest = np.ascontiguousarray(q0.cpu().numpy() if isinstance(q0, torch.Tensor) else q0, np.float64)
+    if table.shape != (GRASP_LINKS, GRASP_TABLE_COLS) or rest.shape != (GRASP_LINKS,):
+        raise ValueError(f"a3vt: grasp_close wants hand_table ({GRASP_LINKS}, {GRASP_TABLE_COLS}) and q0 ({GRASP_LINKS},), got "
+                         f"{table.shape} and {rest.shape}")
+    return table, rest
+
+
+def grasp_reach(hand_table):
+    """The four chains' reach radii as ``a3vt_grasp_close``'s cull uses them (``a3vt_grasp_reach``; host arithmetic, no GPU)."""
+    table, _ = _grasp_tables(hand_table, np.zeros(GRASP_LINKS))
+    out = [_lib.load().a3vt_grasp_reach(table.ctypes.data_as(ctypes.c_void_p), c) for c in range(GRASP_FINGERS)]
+    if min(out) < 0:
+        _lib.check(-1, "grasp_reach")
+    return out
+
+
+def _grasp_rotation(axis, angle):
+    x, y, z = axis
+    c, s = np.cos(angle), np.sin(angle)
+    t = 1.0 - c
+    return np.array([[t * x * x + c, t * x * y - s * z, t * x * z + s * y], [t * x * y + s * z, t * y * y + c, t * y * z - s * x],
+                     [t * x * z - s * y, t * y * z + s * x, t * z * z + c]])
+
+
+def _grasp_chain_from(rows, base_pos, base_rot, angles, first, pos, rot):
+    """The poses of the chain's links ``first``.. from their parents' (``pos`` / ``rot`` hold the links before ``first``), in place."""
+    for k in range(first, GRASP_CHAIN):
+        t = rows[k]
+        parent = int(t[0])
+        p, R = (base_pos, base_rot) if parent < 0 else (pos[parent], rot[parent])
+        pos[k] = p + R @ t[2:5]
+        rot[k] = R @ t[5:14].reshape(3, 3)
+        if t[1]:
+            rot[k] = rot[k] @ _grasp_rotation(t[14:17], angles[k])
+
+
+def _grasp_overlap(centre, axes, half, tri):
+    """Any overlap between the boxes (centre (b, 3), axes (b, 3, 3) with the box's axes as columns, half (b, 3)) and the triangles
+    (n, 3, 3): the 13-axis test in each box's frame, all pairs at once."""
+    if len(tri) == 0 or len(centre) == 0:
+        return False
+    p = np.einsum("bji,bnkj->bnki", axes, tri[None] - centre[:, None, None, :])          # (b, n, vertex, component)
+    h = half[:, None, :]
+    if not ((p.min(axis=2) <= h) & (p.max(axis=2) >= -h)).all(axis=-1).any():
+        return False
+    e = p[:, :, [1, 2, 0]] - p                                                              # p1 - p0, p2 - p1, p0 - p2
+    candidates = [np.cross(e[:, :, 0], e[:, :, 1])]
+    for j in range(3):
+        ex, ey, ez = e[:, :, j, 0], e[:, :, j, 1], e[:, :, j, 2]
+        zero = np.zeros_like(ex)
+        candidates += [np.stack((zero, -ez, ey), -1), np.stack((ez, zero, -ex), -1), np.stack((-ey, ex, zero), -1)]
+    a = np.stack(candidates, axis=2)                                                        # (b, n, 10, 3)
+    d = np.einsum("bnai,bnki->bnak", a, p)
+    r = np.einsum("bnai,bi->bna", np.abs(a), half)
+    separated = ((a * a).sum(-1) >= GRASP_MIN_AXIS2) & ((d.min(-1) > r) | (d.max(-1) < -r))
+    inside = ((p.min(axis=2) <= h) & (p.max(axis=2) >= -h)).all(axis=-1)
+    return bool((inside & ~separated.any(-1)).any())
+
+
+def _grasp_reach_host(rows):
+    path, reach = np.zeros(GRASP_CHAIN), 0.0
+    for k in range(GRASP_CHAIN):
+        if k > 0:
+            path[k] = path[int(rows[k][0])] + np.linalg.norm(rows[k][2:5])
+        if rows[k][19]:
+            reach = max(reach, path[k] + np.linalg.norm(rows[k][20:23]) + np.linalg.norm(rows[k][23:26]))
+    return reach
+
+
+def _grasp_close_host(verts, faces, face_offset, grasp_mesh, base_pos, base_rot, table, q0, steps):
+    """The rule of ``a3vt_grasp_close`` in float64 NumPy, a query's boxes and triangles all at once."""
+    G, V = len(grasp_mesh), len(verts)
+    q_out, blocked = np.zeros((G, 16)), np.zeros((G, 16), np.int32)
+    link_pos, link_rot = np.zeros((G, GRASP_LINKS, 3)), np.zeros((G, GRASP_LINKS, 3, 3))
+    triangles = {}
+    for g in range(G):
+        m = int(grasp_mesh[g])
+        if m not in triangles:
+            f = faces[int(face_offset[m]):int(face_offset[m + 1])]
+            f = f[((f >= 0) & (f < V)).all(axis=1)] if len(f) else f.reshape(0, 3)
+            tri = verts[f].reshape(-1, 3, 3)
+            tri = tri[np.isfinite(tri).all(axis=(1, 2))]
+            mid = tri.mean(axis=1)
+            triangles[m] = (tri, mid, np.linalg.norm(tri - mid[:, None, :], axis=2).max(axis=1) if len(tri) else np.zeros(0))
+        tri, mid, spread = triangles[m]
+        for c in range(GRASP_FINGERS):
+            rows = table[c * GRASP_CHAIN:(c + 1) * GRASP_CHAIN].copy()
+            rows[1:, 0] -= c * GRASP_CHAIN                                                  # parents within the chain
+            angles = q0[c * GRASP_CHAIN:(c + 1) * GRASP_CHAIN].copy()
+            upper, delta = rows[:, 18], (rows[:, 18] - angles) / steps
+            pos, rot = np.zeros((GRASP_CHAIN, 3)), np.zeros((GRASP_CHAIN, 3, 3))
+            _grasp_chain_from(rows, base_pos[g], base_rot[g], angles, 0, pos, rot)
+            near = np.linalg.norm(mid - pos[0], axis=1) <= _grasp_reach_host(rows) + GRASP_SLACK + spread
+            cand, cand_mid, cand_spread = tri[near], mid[near], spread[near]
+            boxed = rows[:, 19] != 0
+            size = np.linalg.norm(rows[:, 23:26], axis=1)
+            took = np.full(GRASP_JOINTS, steps, np.int32)
+            frozen = np.zeros(GRASP_JOINTS, bool)
+            for step in range(1, steps + 1):
+                if frozen.all():
+                    break
+                for j in range(GRASP_JOINTS):
+                    if frozen[j]:
+                        continue
+                    tried = angles.copy()
+                    tried[j] = upper[j] if step == steps else q0[c * GRASP_CHAIN + j] + step * delta[j]
+                    hit = False
+                    if len(cand):
+                        tp, tr = pos.copy(), rot.copy()
+                        _grasp_chain_from(rows, base_pos[g], base_rot[g], tried, j, tp, tr)
+                        links = [k for k in range(j, GRASP_CHAIN) if boxed[k]]
+                        centre = np.array([tp[k] + tr[k] @ rows[k][20:23] for k in links]).reshape(-1, 3)
+                        close = np.zeros(len(cand), bool)
+                        for b, k in enumerate(links):
+                            close |= np.linalg.norm(cand_mid - centre[b], axis=1) <= size[k] + cand_spread + GRASP_SLACK
+                        if close.any():
+                            hit = _grasp_overlap(centre, tr[links], rows[links, 23:26], cand[close])
+                    if hit:
+                        frozen[j], took[j] = True, step - 1
+                    else:
+                        angles = tried
+                        if len(cand):
+                            pos, rot = tp, tr
+            if not len(cand):
+                _grasp_chain_from(rows, base_pos[g], base_rot[g], angles, 0, pos, rot)
+            q_out[g, 4 * c:4 * c + 4], blocked[g, 4 * c:4 * c + 4] = angles[:GRASP_JOINTS], took
+            link_pos[g, c * GRASP_CHAIN:(c + 1) * GRASP_CHAIN], link_rot[g, c * GRASP_CHAIN:(c + 1) * GRASP_CHAIN] = pos, rot
+    last = [c * GRASP_CHAIN + GRASP_CHAIN - 1 for c in range(GRASP_FINGERS)]
+    return q_out, blocked, link_pos, link_rot, link_pos[:, last], link_rot[:, last]
+
+
+def grasp_candidates(verts, faces, face_offset, grasp_mesh, base_pos, base_rot, hand_table):
+    """(G, 4) int64: per (grasp, finger) the triangles that pass the cull of ``a3vt_grasp_close`` — the count its workgroup holds in
+    LDS up to ``grasp_limits()["capacity"]`` — formed on the host in float32 with the kernel's test (arrays or tensors; a
+    measuring and test aid: a triangle within float32 rounding of the sphere may be counted differently)."""
+    f32 = np.float32
+    as_np = lambda a, dtype: np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype)  # noqa: E731
+    verts, faces, base_pos, base_rot = as_np(verts, f32), as_np(faces, np.int64), as_np(base_pos, f32), as_np(base_rot, f32)
+    table, _ = _grasp_tables(hand_table, np.zeros(GRASP_LINKS))
+    reach = grasp_reach(table)
+    counts = np.zeros((len(grasp_mesh), GRASP_FINGERS), np.int64)
+    for g, m in enumerate(np.asarray(grasp_mesh).tolist()):
+        f = faces[int(face_offset[m]):int(face_offset[m + 1])]
+        f = f[((f >= 0) & (f < len(verts))).all(axis=1)] if len(f) else f.reshape(0, 3)
+        tri = verts[f].reshape(-1, 3, 3)
+        mid = (tri[:, 0] + tri[:, 1] + tri[:, 2]) * f32(1.0 / 3.0)
+        spread = np.sqrt(((tri - mid[:, None, :]) ** 2).sum(-1).max(axis=1)) if len(tri) else np.zeros(0, f32)
+        for c in range(GRASP_FINGERS):
+            centre = base_pos[g] + base_rot[g].reshape(3, 3) @ table[c * GRASP_CHAIN, 2:5].astype(f32)
+            with np.errstate(invalid="ignore"):
+                counts[g, c] = int((np.sqrt(((mid - centre) ** 2).sum(-1)) <= f32(reach[c]) + f32(GRASP_SLACK) + spread).sum())
+    return counts
+
+
+def grasp_close(verts, faces, face_offset, grasp_mesh, base_pos, base_rot, hand_table, q0, steps=64):
+    """The finger closing of G placed hands over a table of M meshes (``a3vt_grasp_close``, csrc/grasp_close.hip: one launch per 64
+    grasps on the current stream, no host synchronisation; the rule and the table's columns are stated in ``include/a3vt.h``).
+    **A kinematic stand-in for the reference's five ``stepSimulation`` calls under position control, not pybullet: no frame of it
+    has been compared with one of pybullet's.**
+
+    ``verts`` (V, 3) float32 and ``faces`` (F, 3) int32 with global indices (``touch_render``'s layout); ``face_offset`` (M + 1,)
+    and ``grasp_mesh`` (G,): lists, arrays or tensors, read on the host; ``base_pos`` (G, 3) / ``base_rot`` (G, 3, 3) float32;
+    ``hand_table`` (28, 26) and ``q0`` (28,) float64 (``HandModel.table()`` / ``.q0``).  Returns a dict: ``q`` (G, 16) float32 and
+    ``blocked_step`` (G, 16) int32 (entry 4 c + j: joint j of finger c), ``link_pos`` (G, 28, 3), ``link_rot`` (G, 28, 3, 3),
+    ``frame_pos`` (G, 4, 3), ``frame_rot`` (G, 4, 3, 3) float32.
+
+    GPU tensors run the kernel in float32.  CPU tensors take the same rule in float64 NumPy (the results are then float64 but
+    for ``blocked_step``): the pattern of ``voxel_surface``, for hosts without a GPU and for tests."""
+    table, rest = _grasp_tables(hand_table, q0)
+    steps = int(steps)
+    to_list = lambda a: [int(x) for x in (a.tolist() if hasattr(a, "tolist") else a)]  # noqa: E731
+    face_offset, grasp_mesh = to_list(face_offset), to_list(grasp_mesh)
+    G, M = len(grasp_mesh), len(face_offset) - 1
+    if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or \
+            faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("a3vt: grasp_close wants tensors verts (V, 3) and faces (F, 3)")
+    if tuple(base_pos.shape) != (G, 3) or tuple(base_rot.shape) != (G, 3, 3):
+        raise ValueError(f"a3vt: grasp_close wants base_pos ({G}, 3) and base_rot ({G}, 3, 3), got {tuple(base_pos.shape)} and "
+                         f"{tuple(base_rot.shape)}")
+    names = ("q", "blocked_step", "link_pos", "link_rot", "frame_pos", "frame_rot")
+    if not verts.is_cuda:
+        F = faces.shape[0]
+        if steps < 1 or M < 1 or face_offset[0] < 0 or any(b < a for a, b in zip(face_offset, face_offset[1:])) or face_offset[-1] > F \
+                or any(not 0 <= m < M for m in grasp_mesh):
+            raise ValueError(f"a3vt: grasp_close: steps={steps} must be >= 1, face_offset={face_offset} must start at >= 0, not "
+                             f"decrease and end at <= F={F}, and grasp_mesh must lie in 0..{M - 1}")
+        out = _grasp_close_host(verts.detach().numpy().astype(np.float64), faces.numpy().astype(np.int64), face_offset, grasp_mesh,
+                                np.asarray(base_pos, np.float64).reshape(G, 3), np.asarray(base_rot, np.float64).reshape(G, 3, 3), table,
+                                rest, steps)
+        return {name: torch.from_numpy(np.ascontiguousarray(a)) for name, a in zip(names, out)}
+    dev = verts.device
+    verts, faces = _req(verts, "verts"), _req(faces, "faces", torch.int32)
+    base_pos, base_rot = _req(base_pos, "base_pos"), _req(base_rot, "base_rot")
+    offsets, which = np.array(face_offset, np.int32), np.array(grasp_mesh if G else [0], np.int32)
+    out = (torch.empty((G, 16), dtype=torch.float32, device=dev), torch.empty((G, 16), dtype=torch.int32, device=dev),
+           torch.empty((G, GRASP_LINKS, 3), dtype=torch.float32, device=dev), torch.empty((G, GRASP_LINKS, 3, 3), dtype=torch.float32, device=dev),
+           torch.empty((G, GRASP_FINGERS, 3), dtype=torch.float32, device=dev),
+           torch.empty((G, GRASP_FINGERS, 3, 3), dtype=torch.float32, device=dev))
+    host = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().a3vt_grasp_close(_lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], host(offsets), M,
+                                                host(which), _lib.ptr(base_pos) if G else None, _lib.ptr(base_rot) if G else None, G,
+                                                host(table), host(rest), steps, *((_lib.ptr(t) if G else None) for t in out), _stream()),
+                   "grasp_close")
+    return dict(zip(names, out))
+
+
 # The reference's vision scene (simulator/rendering/vision_renderer.py:35-77): the camera 0.4243 from the origin and looking at it,
 # pyrender's default background as RENDER_DEFAULTS has it, the object's colour, four point lights (x, y, z, intensity).
 VISION_DEFAULTS = dict(yfov=60.0 / 180.0 * np.pi, znear=0.01, zfar=10.0, width=256, height=256,

@@ -36,7 +36,9 @@ end to end (``ops.touch_pack``, one more launch) — which is what ``data_making
 ``ops.VISION_DEFAULTS`` (``simulator/rendering/vision_renderer.py:35-77``).  THE SHADING IS NOT PYRENDER'S: it is ``scene_render``'s
 Lambert model on ray-cast hits at pixel centres, and no image of it has been compared with one of pyrender's.
 
-Out of scope: the grasp physics (frames are an input), the TACTO renderer and the hand model (``vision_occluded``)."""
+Frames are an input here.  ``simulator/physics/grasping.py::GraspFrames`` makes them from the meshes by a KINEMATIC grasp (not
+pybullet's dynamics, never compared with pybullet's frames) and is passed as ``frames`` unchanged.  Out of scope: Bullet's grasp
+physics, the TACTO renderer and the hand meshes in the vision scene (``vision_occluded``)."""
 import os
 from collections.abc import Mapping
 

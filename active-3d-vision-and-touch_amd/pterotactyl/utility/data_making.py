@@ -3,14 +3,15 @@ and the ground-truth clouds ``point_cloud_info/<obj>.npy`` that every loader of 
 
 Reference symbols mirrored: ``make_data_split`` :22-46, ``extract_points`` :50-72, ``save_object_info`` :76-95 (without the URDF),
 ``save_point_info`` :99-118, and of ``save_simulation`` :122-209 what follows the grasp: ``save_image_info`` (the vision image,
-:157-166) and ``save_touch_signals`` (the touch records, :186-199).  The grasp physics is not here: the finger frames
-``<action>/<finger>_ref_frame.npy`` are an input.  This package's own: ``extract_points_batch``, one pass of the kernels over many
+:157-166) and ``save_touch_signals`` (the touch records, :186-199).  Bullet's grasp physics is not here: for those two the finger
+frames ``<action>/<finger>_ref_frame.npy`` are an input, and ``save_simulation`` writes them with a KINEMATIC grasp
+(``simulator/physics/grasping.py``: not pybullet, never compared with pybullet's frames) before it calls them.  This package's own: ``extract_points_batch``, one pass of the kernels over many
 meshes; ``touch_charts_batch`` / ``save_touch_info``, which write ``touch_charts/<obj>/touch_charts.npy`` from an object's finger
 frames (the reference has no writer for that file: it comes with its download).
 
 The chain from object files to a tree that ``data_loaders.py``'s three loaders and the trainers read: ``save_object_info`` ->
 ``save_point_info`` -> ``save_image_info`` -> frames from a simulator -> ``save_touch_signals`` -> ``save_touch_info`` ->
-``make_data_split``.
+``make_data_split``; ``save_simulation`` is the three middle steps with the kinematic grasp as the simulator.
 
 The cloud of a mesh is the reference's, row for row: voxelise by adaptive subdivision, carve with the six depth maps, take the
 surface voxels, realign them to the mesh (``a3vt_voxel_surface`` / ``a3vt_voxel_points``, csrc/voxel.hip, for GPU tensors; the
@@ -369,6 +370,72 @@ def save_touch_signals(data_root, batch=8, num_actions=50, overwrite=False, devi
             counts["views"] += codes[e].size
             for name, value in (("touch", 2), ("no_touch", 1), ("no_intersection", 0)):
                 counts[name] += int((codes[e] == value).sum())
+    return counts
+
+
+def save_simulation(data_root, hand, batch=8, num_actions=50, overwrite=False, steps=64, device=None, signals=True):
+    """The reference's ``save_simulation`` (:122-209) on a tree: the grasp of every action of every object of
+    ``<data_root>/object_info/``, then the vision image and the touch records.  **The grasp is ``KinematicGrasp``'s
+    (``simulator/physics/grasping.py``): the reference's hand placement, and a kinematic closing rule that is a stand-in for five
+    ``stepSimulation`` calls under position control.  No frame of it has been compared with one of pybullet's.**
+
+    Writes ``grasp_info/<id>/<action>/<finger>_ref_frame.npy`` — the reference's pickled ``{"pos": (3,), "rot": (3, 3)}`` float32
+    dict, which ``recorded.tree_frames`` reads — one file for every finger of a placed grasp and none for a grasp that could not
+    be placed ("no_intersection"; the action's directory is made either way, as the reference makes it).  ``batch`` objects per
+    ``KinematicGrasp.grasp_table`` call (one ``ops.grasp_close`` call each), in sorted order of the ids.  ``hand``: a ``HandModel``
+    or a path ``HandModel.load`` takes (None: ``PTEROTACTYL_HAND``).
+
+    Frames are never silently replaced: without ``overwrite`` an object that already holds any ``*_ref_frame.npy`` is skipped
+    (``skipped_existing``) unless it carries the marker ``grasp_info/<id>/.baking`` of an interrupted run; such an object's frames,
+    and under ``overwrite`` any object's, are removed and written again.  Each file is written under a temporary name and renamed.
+
+    Then, with ``signals``, the existing ``save_image_info`` and ``save_touch_signals`` run on the tree with the same ``batch``
+    (capped at ``save_image_info``'s 128), ``overwrite`` and ``device``.  With ``save_object_info``, ``save_point_info``,
+    ``save_touch_info`` and ``make_data_split`` a folder of ``.obj`` files is then enough for every file the loaders read.
+
+    Returns the counts ``written``, ``skipped_existing`` (objects), ``grasps``, ``placed`` and, with ``signals``, ``images`` and
+    ``touch``: the two calls' own counts."""
+    from ..simulator.hand import HandModel
+    from ..simulator.physics.grasping import KinematicGrasp
+    batch, num_actions = max(int(batch), 1), int(num_actions)
+    if not isinstance(hand, HandModel):
+        hand = HandModel.load(hand)
+    object_dir, grasp_dir = os.path.join(data_root, "object_info"), os.path.join(data_root, "grasp_info")
+    counts = dict(written=0, skipped_existing=0, grasps=0, placed=0)
+    frames = lambda obj: glob(os.path.join(grasp_dir, obj, "*", "*_ref_frame.npy"))  # noqa: E731
+    todo = []
+    for obj in _object_ids(data_root):
+        if not os.path.exists(os.path.join(object_dir, f"{obj}_faces.npy")):
+            continue
+        if not overwrite and not os.path.exists(os.path.join(grasp_dir, obj, BAKING_MARKER)) and frames(obj):
+            counts["skipped_existing"] += 1
+        else:
+            todo.append(obj)
+    grasper = KinematicGrasp(hand, steps=steps, device=utils._default_device() if device is None else torch.device(device)) if todo else None
+    for at in range(0, len(todo), batch):
+        group = todo[at:at + batch]
+        geometry = {obj: (np.load(os.path.join(object_dir, f"{obj}_verts.npy")), np.load(os.path.join(object_dir, f"{obj}_faces.npy")))
+                    for obj in group}
+        table = grasper.grasp_table(geometry, group, num_actions)
+        for e, obj in enumerate(group):
+            os.makedirs(os.path.join(grasp_dir, obj), exist_ok=True)
+            with open(os.path.join(grasp_dir, obj, BAKING_MARKER), "w"):
+                pass
+            for stale in frames(obj):
+                os.remove(stale)
+            for a in range(num_actions):
+                directory = os.path.join(grasp_dir, obj, str(a))
+                os.makedirs(directory, exist_ok=True)
+                for j in np.flatnonzero(table["present"][e, a]):
+                    _save_atomic(directory, f"{j}_ref_frame.npy", np.array({"pos": table["pos"][e, a, j].copy(),
+                                                                           "rot": table["rot"][e, a, j].copy()}, dtype=object))
+                counts["placed"] += int(table["present"][e, a].any())
+            os.remove(os.path.join(grasp_dir, obj, BAKING_MARKER))
+            counts["written"] += 1
+            counts["grasps"] += num_actions
+    if signals:
+        counts["images"] = save_image_info(data_root, batch=min(batch, 128), overwrite=overwrite, device=device)
+        counts["touch"] = save_touch_signals(data_root, batch=batch, num_actions=num_actions, overwrite=overwrite, device=device)
     return counts
 
 

@@ -364,6 +364,41 @@ def add_faces(faces):
     return np.concatenate((faces, np.concatenate((f1, f3, f2), axis=-1), np.concatenate((f3, f2, f1), axis=-1)), axis=0)
 
 
+# ---- the grasp's vector helpers (reference :289-327), used by simulator/physics/grasping.py ----
+def normalize_vector(vector):
+    """A (1, 1, 3) array divided by its norm, in place (reference :297-302)."""
+    n = np.linalg.norm(vector, axis=2)
+    for k in range(3):
+        vector[:, :, k] /= n
+    return vector
+
+
+def normal_from_triangle(a, b, c):
+    """The unit normal (b - a) x (c - a) of a triangle (reference :289-294)."""
+    return normalize_vector(np.cross(b - a, c - a).reshape(1, 1, 3)).reshape(3)
+
+
+def quats_from_vectors(vec1, vec2):
+    """The quaternion (x, y, z, w) of the rotation that turns ``vec1`` onto ``vec2`` about their common normal (reference
+    :305-320): I + K + K K (1 - c) / s^2 with K the cross-product matrix of a x b; s = 0 (parallel vectors) is replaced by 1, so
+    opposite vectors give what the reference gives, a reflection that SciPy then projects onto a rotation."""
+    from scipy.spatial.transform import Rotation
+    a, b = np.array(vec1, np.float64), np.array(vec2, np.float64)
+    a, b = (a / np.linalg.norm(a)).reshape(3), (b / np.linalg.norm(b)).reshape(3)
+    v = np.cross(a, b)
+    c, s = np.dot(a, b), np.linalg.norm(v)
+    if s == 0:
+        s = 1
+    kmat = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+    return Rotation.from_matrix(np.eye(3) + kmat + kmat.dot(kmat) * ((1 - c) / (s ** 2))).as_quat()
+
+
+def combine_quats(q1, q2):
+    """The quaternion of R(q1) R(q2) (reference :323-327)."""
+    from scipy.spatial.transform import Rotation
+    return Rotation.from_matrix(np.matmul(Rotation.from_quat(q1).as_matrix(), Rotation.from_quat(q2).as_matrix())).as_quat()
+
+
 def _sphere_cell(point, num_actions):
     """The (row, column) of a unit vector on ``visualize_actions``' (2 num_actions, 4 num_actions) map (reference :573-579)."""
     x, y, z = (float(v) for v in point)

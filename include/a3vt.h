@@ -762,6 +762,63 @@ int a3vt_touch_pack(const float *touch, const float *points, const int32_t *coun
 int a3vt_touch_pack_launches(long long *counts /*[1]*/, int reset);
 
 /* ---------------------------------------------------------------------------------------------
+ * The finger closing of the kinematic grasp (pterotactyl/simulator/physics/grasping.py, csrc/grasp_close.hip): from G placed hands
+ * and a table of M meshes to the angles at which each finger stops, the links' poses and the finger frames.
+ *
+ * THE CLOSING RULE IS A KINEMATIC STAND-IN for the reference's five stepSimulation calls under position control
+ * (simulator/physics/grasping.py:54-63).  It is not pybullet: no frame of it has been compared with one of pybullet's.
+ *
+ * The hand.  hand_table is a HOST table of 28 rows of 26 doubles, the hand's links without the base in depth-first order: four
+ * chains of 7 links (rows 7 c .. 7 c + 6), the first four of a chain revolute, the last three fixed.  Columns:
+ *   [0] parent row (-1: the base; otherwise a lower row of the same chain)   [1] 1 revolute, 0 fixed
+ *   [2..4] the joint's origin in the parent's frame   [5..13] its rotation, row-major   [14..16] the joint's axis (unit length)
+ *   [17] lower and [18] upper limit   [19] 1 when the link carries a collision box   [20..22] the box's centre and [23..25] its
+ *   half-extents in the link's frame.
+ * q0: a HOST table of 28 doubles, the rest angles (the entry of a fixed joint is ignored).
+ * A link's pose is  R = R_parent * R_origin * Rot(axis, angle),  p = p_parent + R_parent * xyz;  the base's is base_pos[g] (3) and
+ * base_rot[g] (3 x 3 row-major), DEVICE arrays.  The kernel works in float32.
+ *
+ * The meshes: verts (V, 3) and faces (F, 3, global vertex indices) on the DEVICE, a3vt_touch_render's layout; face_offset (M + 1)
+ * and grasp_mesh (G) are HOST tables: grasp g closes on the faces [face_offset[m], face_offset[m + 1]), m = grasp_mesh[g].  A
+ * face with an index outside [0, V) or a non-finite coordinate is skipped.
+ *
+ * The rule, for every grasp and each chain on its own (fingers do not see each other; the base is not tested).  Joint j of the
+ * chain (j = 0..3, proximal to distal) has delta_j = (upper_j - q0_j) / steps and stands after k accepted steps at
+ * q0_j + k * delta_j, at upper_j exactly for k = steps.  For step = 1..steps, and within a step for j = 0..3: unless joint j is
+ * frozen it tries the angle of `step` steps.  The try is accepted iff no collision box of link j or of a link behind it in the
+ * chain overlaps a triangle of the grasp's mesh under the tentative angles; otherwise the joint is frozen for good and
+ * blocked_step[j] = step - 1, the steps it took.  A joint never blocked ends at upper_j with blocked_step[j] = steps.
+ * Overlap is the 13-axis separating-axis test of an oriented box against a triangle — the box's three axes, the triangle's
+ * normal, the nine cross products — in the box's frame; touching counts as overlap; a cross-product axis (the normal included)
+ * whose squared length is below 1e-24 is skipped.
+ *
+ * Outputs (DEVICE), written for every grasp: q_out (G, 16) and blocked_step (G, 16), entry 4 c + j for joint j of chain c;
+ * link_pos (G, 28, 3) and link_rot (G, 28, 3, 3), the poses of all links at q_out; frame_pos (G, 4, 3) and frame_rot (G, 4, 3, 3),
+ * those of each chain's last link (the finger's camera link).  No atomics: two calls write the same bytes, and a grasp's rows do
+ * not depend on the other grasps of the call.
+ *
+ * One launch per 64 grasps on `stream`, no host synchronisation.  G == 0 launches nothing and returns 0.
+ *
+ * Limits: 0 <= G <= 2^20; 1 <= M <= 2^20; 0 <= V, F <= 2^28; 1 <= steps <= 65536; face_offset starts at >= 0, does not decrease and
+ * ends at <= F; grasp_mesh[g] in [0, M); the table as described above, its numbers finite, lower <= upper, half-extents >= 0.
+ * Pointers 4-byte aligned (hand_table and q0: 8).  Anything else returns non-zero with a message in a3vt_last_error that names
+ * grasp_close, the argument and its value.  Nothing is launched.
+ *
+ * a3vt_grasp_limit(which): [0] the candidate triangles a workgroup holds in LDS (more are read from global memory in every
+ * query), [1] the grasps of one launch, [2] the columns of hand_table; 0 otherwise.
+ * a3vt_grasp_reach: the radius of chain c's reach sphere about the chain's first joint, as the kernel's cull uses it (without
+ * the 1e-4 slack), from a hand_table; negative with the message set for a table that a3vt_grasp_close would refuse.
+ * a3vt_grasp_launches: [0] the a3vt_grasp_close calls that launched since the last reset (G > 0), [1] the kernels they launched;
+ * returns 2. */
+int a3vt_grasp_close(const float *verts, int V, const int32_t *faces, int F, const int32_t *face_offset, int M, const int32_t *grasp_mesh,
+                     const float *base_pos, const float *base_rot, int G, const double *hand_table, const double *q0, int steps,
+                     float *q_out, int32_t *blocked_step, float *link_pos, float *link_rot, float *frame_pos, float *frame_rot,
+                     void *stream);
+int a3vt_grasp_limit(int which);
+double a3vt_grasp_reach(const double *hand_table, int chain);
+int a3vt_grasp_launches(long long *counts /*[2]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The ground-truth point cloud of a mesh: utility/data_making.py::extract_points (mesh_to_voxel, extract_ODMs, apply_ODMs,
  * voxel_to_pointcloud, realign_points of utility/utils.py) for a batch of M meshes.
  *
