@@ -1733,6 +1733,77 @@ double a3vt_grasp_reach(const double *hand_table, int chain) {
 
 int a3vt_grasp_launches(long long *counts, int reset) { return g_grasp_launches.read(counts, reset); }
 
+// ---- the hand's placement without a hull (hull_place.hip) --------------------------------------------------------------------------
+namespace {
+LaunchCounts<2> g_hull_launches;
+}  // namespace
+
+int a3vt_hull_place(const float *verts, int V, const int32_t *vert_offset, int M, const double *directions, int A, double hand_distance,
+                    const double *tip_offset, int32_t *status, float *base_pos, float *base_rot, int32_t *simplex, double *t, void *stream) {
+  const char *who = "hull_place";
+  auto finite = [](double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; };
+  if (check_range(who, "M", M, 1, kHullMaxMeshes) || check_range(who, "A", A, 1, kHullMaxActions) ||
+      check_range(who, "M*A", (long long)M * A, 1, kHullMaxPairs) || check_range(who, "V", V, 0, kHullMaxVerts))
+    return -1;
+  if (check_ptrs(who, {{"verts", verts, V > 0, 4, "required when V > 0"},
+                       {"vert_offset", vert_offset, true, 4, "required (a host table)"},
+                       {"directions", directions, true, 8, "required (a host table)"},
+                       {"tip_offset", tip_offset, true, 8, "required (a host table)"},
+                       {"status", status, true, 4, "required"},
+                       {"base_pos", base_pos, true, 4, "required"},
+                       {"base_rot", base_rot, true, 4, "required"},
+                       {"simplex", simplex, true, 4, "required"},
+                       {"t", t, true, 8, "required"}}))
+    return -1;
+  // the host tables' contents
+  if (vert_offset[0] < 0) {
+    set_error("%s: vert_offset[0]=%d is below 0", who, (int)vert_offset[0]);
+    return -1;
+  }
+  for (int m = 0; m < M; ++m) {
+    if (vert_offset[m + 1] < vert_offset[m]) {
+      set_error("%s: vert_offset[%d]=%d is below vert_offset[%d]=%d: offsets must not decrease", who, m + 1, (int)vert_offset[m + 1], m,
+                (int)vert_offset[m]);
+      return -1;
+    }
+  }
+  if (vert_offset[M] > V) {
+    set_error("%s: vert_offset[%d]=%d runs past V=%d", who, M, (int)vert_offset[M], V);
+    return -1;
+  }
+  for (int a = 0; a < A; ++a) {
+    const double *d = directions + 3 * a;
+    for (int i = 0; i < 3; ++i) {
+      if (!finite(d[i])) {
+        set_error("%s: directions[%d][%d]=%g is not finite", who, a, i, d[i]);
+        return -1;
+      }
+    }
+    if (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0) {
+      set_error("%s: directions[%d] is zero", who, a);
+      return -1;
+    }
+  }
+  if (!finite(hand_distance)) {
+    set_error("%s: hand_distance=%g is not finite", who, hand_distance);
+    return -1;
+  }
+  for (int i = 0; i < 3; ++i) {
+    if (!finite(tip_offset[i])) {
+      set_error("%s: tip_offset[%d]=%g is not finite", who, i, tip_offset[i]);
+      return -1;
+    }
+  }
+  const int rc = launch_hull_place(verts, vert_offset, M, directions, A, hand_distance, tip_offset, status, base_pos, base_rot, simplex, t,
+                                   static_cast<hipStream_t>(stream));
+  if (rc < 0) return rc;
+  g_hull_launches.add(0, 1);
+  g_hull_launches.add(1, rc);
+  return 0;
+}
+
+int a3vt_hull_place_launches(long long *counts, int reset) { return g_hull_launches.read(counts, reset); }
+
 // ---- mesh and point-cloud rendering (scene_render.hip) -----------------------------------------------------------------------------
 namespace {
 LaunchCounts<2> g_scene_launches;

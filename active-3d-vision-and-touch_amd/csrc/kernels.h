@@ -446,6 +446,23 @@ int launch_grasp_close(const float *verts, int V, const int32_t *faces, const in
                        const float *base_rot, int G, const GraspHand &hand, int steps, float *q_out, int32_t *blocked_step, float *link_pos,
                        float *link_rot, float *frame_pos, float *frame_rot, hipStream_t s);
 
+// hull_place.hip: the hand's base pose for every (mesh, action) without a hull (grasping.py::place_hand) — one workgroup per pair,
+// support passes over the mesh's vertices in float64.  The directions and the launch's vertex ranges travel by value in the kernel
+// arguments: the host has checked them.
+constexpr int kHullMaxActions = 128;          // (24 bytes each of the kernel-argument block)
+constexpr int kHullMeshesPerLaunch = 128;     // meshes of one launch (4 bytes each): up to 128 x A workgroups
+constexpr int kHullGjkPasses = 32, kHullPivotPasses = 64;   // the pass caps of the rule's two phases
+constexpr int kHullMaxMeshes = 1 << 20, kHullMaxPairs = 1 << 20, kHullMaxVerts = 1 << 28;
+struct HullBatch {
+  double direction[kHullMaxActions][3];
+  int32_t offset[kHullMeshesPerLaunch + 1];   // mesh i of the launch owns the vertices offset[i] .. offset[i + 1] - 1
+};
+// vert_offset (M + 1), directions (A x 3) and tip_offset (3) on the HOST.  Returns the number of launches, or a negative error code
+// with the message set.
+int launch_hull_place(const float *verts, const int32_t *vert_offset, int M, const double *directions, int A, double hand_distance,
+                      const double *tip_offset, int32_t *status, float *base_pos, float *base_rot, int32_t *simplex, double *t,
+                      hipStream_t s);
+
 // scene_render.hip: colour, depth and primitive-index images of triangle + sphere scenes (utility/pretty_render.py's job): a ray
 // cast per pixel with Lambert shading, one launch per kSceneImagesPerLaunch images.  The small tables travel by value in the kernel
 // arguments: the host has checked them, and nothing on the device has to be trusted or clamped.

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT
 SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "conv5f.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
            "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip", "latent_nn.hip", "latent_policy.hip", "ddqn_latent.hip",
            "candidate_tally.hip", "touch_render.hip", "voxel.hip", "scene_render.hip", "touch_assemble.hip", "chart_head.hip",
-           "touch_pack.hip", "grasp_close.hip"]
+           "touch_pack.hip", "grasp_close.hip", "hull_place.hip"]
 # Per-file extra flags (none at present; sample.hip / gcn_csr.hip rely on IEEE NaN semantics — the reference's NaN
 # scrubs, a3vt_check_finite — so fast-math style flags must never be applied globally).
 # chamfer.hip: keep the nearest-neighbour loop on scalar fp32 ops (the SLP vectoriser would re-pack it into v_pk_*_f32,
@@ -23,9 +23,11 @@ SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm
 # gcn_csrq.hip: scalar fma chains keep one register per edge weight (v_pk_fma_f32 wants (w, w) pairs): see the file header
 # voxel.hip: no multiply-add may be fused: its grids equal the reference's bit for bit (the steps are spelled with __f*_rn as well)
 # grasp_close.hip: no multiply-add may be fused: the LDS walk and the global-memory walk of a query must give the same booleans
+# hull_place.hip: no multiply-add may be fused: ops.py's float64 NumPy form of the rule states the same operations in the same order
 EXTRA_FLAGS = {"chamfer.hip": ["-fno-slp-vectorize"], "nn_prune.hip": ["-fno-slp-vectorize"],
                "gcn_csrq.hip": ["-fno-slp-vectorize"], "gcn_csrqs.hip": ["-fno-slp-vectorize"],
                "voxel.hip": ["-ffp-contract=off"], "grasp_close.hip": ["-ffp-contract=off"],
+               "hull_place.hip": ["-ffp-contract=off"],
                "gcn_gemmw.hip": ["-std=c++20"], "gcn_dww.hip": ["-std=c++20"]}   # (templated lambdas over the chunk / column-tile index)
 
 _vp, _i, _sz, _u64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_float

@@ -1828,6 +1828,212 @@ def grasp_close(verts, faces, face_offset, grasp_mesh, base_pos, base_rot, hand_
     return dict(zip(names, out))
 
 
+# ---- the hand's placement on the convex hull without a hull (csrc/hull_place.hip; the rule is stated in include/a3vt.h) ----
+HULL_MAX_ACTIONS, HULL_GJK_PASSES, HULL_PIVOT_PASSES = 128, 32, 64          # csrc/kernels.h's kHull*
+HULL_FLAT, HULL_MIN_SIN2 = 1e-12, 1e-24
+
+
+def hull_place_launches(reset=False):
+    """``a3vt_hull_place`` calls that launched since the last reset, and the kernels they launched (a test hook)."""
+    return _launch_counts("a3vt_hull_place_launches", ("calls", "launches"), reset)
+
+
+def _cross2(p, q):
+    return p[0] * q[1] - p[1] * q[0]
+
+
+def _hull_place_steps(V, d, hand_distance, tip, largest):
+    """The rule of ``a3vt_hull_place`` for one (mesh, action) as a generator: it yields the normal of the next support pass, is
+    sent ``(w, hi, lo)`` — the lowest index of the largest ``n . v_i``, that value and the smallest — and returns
+    ``(status, base_pos, base_rot, simplex, t)``.  Scalar float64 steps in the kernel's order, operation for operation."""
+    none = (np.zeros(3), np.zeros((3, 3)), (-1, -1, -1), 0.0)
+    dot = lambda n, v: (n[0] * v[0] + n[1] * v[1]) + n[2] * v[2]  # noqa: E731
+    k = 0 if abs(d[0]) <= abs(d[1]) and abs(d[0]) <= abs(d[2]) else 1 if abs(d[1]) <= abs(d[2]) else 2
+    e = np.zeros(3)
+    e[k] = 1.0
+    x = np.array([d[1] * e[2] - d[2] * e[1], d[2] * e[0] - d[0] * e[2], d[0] * e[1] - d[1] * e[0]])
+    x = x / np.sqrt(dot(x, x))
+    y = np.array([d[1] * x[2] - d[2] * x[1], d[2] * x[0] - d[0] * x[2], d[0] * x[1] - d[1] * x[0]])
+    y = y / np.sqrt(dot(y, y))
+    proj = lambda i: (dot(V[i], x), dot(V[i], y))  # noqa: E731
+    lift = lambda u: np.array([u[0] * x[0] + u[1] * y[0], u[0] * x[1] + u[1] * y[1], u[0] * x[2] + u[1] * y[2]])  # noqa: E731
+    # phase 1: a triangle whose projection holds the origin
+    ia, _, _ = yield x
+    pa = proj(ia)
+    if pa[0] < 0.0:
+        return (1,) + none
+    if pa[0] == 0.0:
+        return (2,) + none
+    u = (-pa[0], -pa[1])
+    ib, _, _ = yield lift(u)
+    pb = proj(ib)
+    sv = pb[0] * u[0] + pb[1] * u[1]
+    if sv < 0.0:
+        return (1,) + none
+    if sv == 0.0 or ib == ia:
+        return (2,) + none
+    for step in range(HULL_GJK_PASSES):
+        ex, ey = pb[0] - pa[0], pb[1] - pa[1]
+        orient = ey * pa[0] - ex * pa[1]
+        if orient == 0.0 and step > 0:           # (on the opening edge the origin lies between a and b: see the header)
+            return (2,) + none
+        u = (-ey, ex) if orient >= 0.0 else (ey, -ex)
+        ic, _, _ = yield lift(u)
+        pc = proj(ic)
+        sv = pc[0] * u[0] + pc[1] * u[1]
+        if sv < 0.0:
+            return (1,) + none
+        if sv == 0.0 or ic == ia or ic == ib:
+            return (2,) + none
+        ac, bc = (pc[0] - pa[0], pc[1] - pa[1]), (pc[0] - pb[0], pc[1] - pb[1])
+        o_ac, b_ac = _cross2(ac, (-pa[0], -pa[1])), _cross2(ac, (pb[0] - pa[0], pb[1] - pa[1]))
+        o_bc, a_bc = _cross2(bc, (-pb[0], -pb[1])), _cross2(bc, (pa[0] - pb[0], pa[1] - pb[1]))
+        if o_ac == 0.0 or o_bc == 0.0 or b_ac == 0.0 or a_bc == 0.0:
+            return (2,) + none
+        if (o_ac > 0.0) != (b_ac > 0.0):         # the origin is outside edge a c: b leaves
+            ib, pb = ic, pc
+        elif (o_bc > 0.0) != (a_bc > 0.0):       # outside edge b c: a leaves
+            ia, pa = ic, pc
+        else:
+            break
+    else:
+        return (2,) + none
+    # phase 2: pivots to the optimal basis
+    for _ in range(HULL_PIVOT_PASSES):
+        a, b, c = V[ia], V[ib], V[ic]
+        e1, e2 = (b[0] - a[0], b[1] - a[1], b[2] - a[2]), (c[0] - a[0], c[1] - a[1], c[2] - a[2])
+        N = (e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0])
+        den = dot(N, d)
+        if den == 0.0:
+            return (2,) + none
+        n = np.array([N[0] / den, N[1] / den, N[2] / den])
+        t = dot(n, a)
+        w, hi, lo = yield n
+        if hi <= t or w == ia or w == ib or w == ic:
+            break
+        pw = proj(w)
+        area = _cross2((pb[0] - pa[0], pb[1] - pa[1]), (pc[0] - pa[0], pc[1] - pa[1]))
+        if area == 0.0:
+            return (2,) + none
+        rel = lambda p, q: (p[0] - q[0], p[1] - q[1])  # noqa: E731
+        lam = [max(_cross2(pb, pc) / area, 0.0), max(_cross2(pc, pa) / area, 0.0), max(_cross2(pa, pb) / area, 0.0)]
+        mu = [_cross2(rel(pb, pw), rel(pc, pw)) / area, _cross2(rel(pc, pw), rel(pa, pw)) / area, _cross2(rel(pa, pw), rel(pb, pw)) / area]
+        leave, best = -1, 0.0
+        for j in range(3):
+            if mu[j] > 0.0 and (leave < 0 or lam[j] / mu[j] < best):
+                leave, best = j, lam[j] / mu[j]
+        if leave < 0:
+            return (2,) + none
+        if leave == 0:
+            ia, pa = w, pw
+        elif leave == 1:
+            ib, pb = w, pw
+        else:
+            ic, pc = w, pw
+    else:
+        return (2,) + none
+    # the checks
+    if t <= 0.0:
+        return (1,) + none
+    if hi - lo <= HULL_FLAT * largest:
+        return (2,) + none
+    # the pose: place_hand line for line
+    point = np.array([d[0] * t, d[1] * t, d[2] * t])
+    length = np.sqrt(dot(N, N))
+    normal = np.array([N[0] / length, N[1] / length, N[2] / length])
+    moved = point + normal * 0.0001
+    if dot(point, point) > dot(moved, moved):
+        normal = -normal
+    position = point + normal * hand_distance
+    normal = normal - 0.001
+    length = np.sqrt(dot(normal, normal))
+    bx, by, bz = normal[0] / length, normal[1] / length, normal[2] / length
+    v = (0.0, bz, -by)                                  # (-1, 0, 0) x b
+    cosine, sin2 = -bx, bz * bz + by * by
+    if sin2 < HULL_MIN_SIN2:
+        return (2,) + none
+    K = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    f = (1.0 - cosine) / sin2
+    R = np.zeros((3, 3))
+    for i in range(3):
+        for j in range(3):
+            kk = (K[i, 0] * K[0, j] + K[i, 1] * K[1, j]) + K[i, 2] * K[2, j]
+            R[i, j] = ((1.0 if i == j else 0.0) + K[i, j]) + kk * f
+    base = np.array([position[i] - ((R[i, 0] * tip[0] + R[i, 1] * tip[1]) + R[i, 2] * tip[2]) for i in range(3)])
+    return 0, base, R, (int(ia), int(ib), int(ic)), float(t)
+
+
+def _hull_place_host(verts, vert_offset, directions, hand_distance, tip):
+    """The rule of ``a3vt_hull_place`` in float64 NumPy: per mesh every action's scalar steps run side by side, and each round's
+    support passes are one (V, actions) product."""
+    M, A = len(vert_offset) - 1, len(directions)
+    status, t = np.ones((M, A), np.int32), np.zeros((M, A))
+    base_pos, base_rot, simplex = np.zeros((M, A, 3)), np.zeros((M, A, 3, 3)), np.full((M, A, 3), -1, np.int32)
+    for m in range(M):
+        V = verts[vert_offset[m]:vert_offset[m + 1]].astype(np.float64)
+        if len(V) < 4 or not np.isfinite(V).all():
+            continue
+        largest = float(np.abs(V).max())
+        runs = {a: _hull_place_steps(V, directions[a], hand_distance, tip, largest) for a in range(A)}
+        asks = {a: next(run) for a, run in runs.items()}
+        while asks:
+            who = sorted(asks)
+            n = np.array([asks[a] for a in who])                                              # (k, 3)
+            values = (V[:, 0:1] * n[:, 0] + V[:, 1:2] * n[:, 1]) + V[:, 2:3] * n[:, 2]        # (V, k), the kernel's order
+            w, lo = values.argmax(axis=0), values.min(axis=0)
+            asks = {}
+            for j, a in enumerate(who):
+                try:
+                    asks[a] = runs[a].send((int(w[j]), float(values[w[j], j]), float(lo[j])))
+                except StopIteration as done:
+                    status[m, a], base_pos[m, a], base_rot[m, a], simplex[m, a], t[m, a] = done.value
+    return status, base_pos, base_rot, simplex, t
+
+
+def hull_place(verts, vert_offset, directions, hand_distance=0.013, tip_offset=(0.0, 0.0, 0.133)):
+    """The hand's base pose for every one of A actions on every one of M meshes (``a3vt_hull_place``, csrc/hull_place.hip: one
+    workgroup per (mesh, action), one launch per 128 meshes on the current stream, no host synchronisation).  It is the placement of
+    ``simulator.physics.grasping.place_hand`` without a hull: the farthest point of the ray along ``directions[a]`` in the convex
+    hull of the mesh's vertices is a linear programme in three variables, solved by support queries over the vertices in float64
+    (``include/a3vt.h`` states the rule in full).
+
+    ``verts`` (V, 3) float32; ``vert_offset`` (M + 1,) and ``directions`` (A, 3): lists, arrays or tensors, read on the host.
+    Returns a dict: ``status`` (M, A) int32 — 0 placed, 1 no intersection (``place_hand``'s None), 2 not decided here (ask
+    ``place_hand``) — ``base_pos`` (M, A, 3), ``base_rot`` (M, A, 3, 3) float32, ``simplex`` (M, A, 3) int32 (the facet's vertices,
+    indices within the mesh) and ``t`` (M, A) float64 (the hit is ``t * direction``).  Rows with status != 0 are zeros, simplex -1.
+
+    GPU tensors run the kernel.  CPU tensors take the same rule in float64 NumPy (``base_pos`` / ``base_rot`` are then float64):
+    the pattern of ``grasp_close``, for hosts without a GPU and for tests."""
+    as_np = lambda a, dtype: np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype)  # noqa: E731
+    offsets, dirs, tip = as_np(vert_offset, np.int64).reshape(-1), as_np(directions, np.float64), as_np(tip_offset, np.float64).reshape(-1)
+    hand_distance = float(hand_distance)
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("a3vt: hull_place wants a tensor verts (V, 3)")
+    if dirs.ndim != 2 or dirs.shape[1] != 3 or tip.shape != (3,) or len(offsets) < 2:
+        raise ValueError(f"a3vt: hull_place wants vert_offset (M + 1,), directions (A, 3) and tip_offset (3,), got {offsets.shape}, "
+                         f"{dirs.shape} and {tip.shape}")
+    M, A, V = len(offsets) - 1, len(dirs), verts.shape[0]
+    names = ("status", "base_pos", "base_rot", "simplex", "t")
+    if not verts.is_cuda:
+        if not 1 <= A <= HULL_MAX_ACTIONS or offsets[0] < 0 or (np.diff(offsets) < 0).any() or offsets[-1] > V or \
+                not (np.isfinite(dirs).all() and np.isfinite(tip).all() and np.isfinite(hand_distance)) or not dirs.any(axis=1).all():
+            raise ValueError(f"a3vt: hull_place: A={A} must lie in 1..{HULL_MAX_ACTIONS}, vert_offset must start at >= 0, not decrease "
+                             f"and end at <= V={V}, and directions, tip_offset and hand_distance must be finite, no direction zero")
+        out = _hull_place_host(verts.detach().numpy(), offsets, dirs, hand_distance, tip)
+        return {name: torch.from_numpy(np.ascontiguousarray(a)) for name, a in zip(names, out)}
+    dev = verts.device
+    verts = _req(verts, "verts")
+    offsets = offsets.astype(np.int32)
+    out = (torch.empty((M, A), dtype=torch.int32, device=dev), torch.empty((M, A, 3), dtype=torch.float32, device=dev),
+           torch.empty((M, A, 3, 3), dtype=torch.float32, device=dev), torch.empty((M, A, 3), dtype=torch.int32, device=dev),
+           torch.empty((M, A), dtype=torch.float64, device=dev))
+    host = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().a3vt_hull_place(_lib.ptr(verts) if V else None, V, host(offsets), M, host(dirs), A, hand_distance, host(tip),
+                                               *(_lib.ptr(t) for t in out), _stream()), "hull_place")
+    return dict(zip(names, out))
+
+
 # The reference's vision scene (simulator/rendering/vision_renderer.py:35-77): the camera 0.4243 from the origin and looking at it,
 # pyrender's default background as RENDER_DEFAULTS has it, the object's colour, four point lights (x, y, z, intensity).
 VISION_DEFAULTS = dict(yfov=60.0 / 180.0 * np.pi, znear=0.01, zfar=10.0, width=256, height=256,

@@ -13,6 +13,10 @@ its own in place of trimesh.  Difference: the reference takes the face of ``inde
 normal while taking the FARTHEST hit for the position; here the normal is the farthest hit's own facet's.  On a convex hull that
 contains the origin the ray has one hit and the two agree.
 
+``KinematicGrasp(placement="device")`` places the hand with ``ops.hull_place`` instead (``a3vt_hull_place``, csrc/hull_place.hip): the
+same farthest hit and facet plane from a linear programme over the vertices, all actions of all objects in one launch and no hull;
+the pairs it leaves undecided (status 2) go to ``place_hand``.  An option: ``DEVICE_PLACEMENT_DEFAULT`` is False.
+
 ``KinematicGrasp`` closes all placed grasps of all objects in one ``ops.grasp_close`` call; ``GraspFrames`` serves the result as the
 ``frames`` mapping of ``RenderedSampler``."""
 from collections.abc import Mapping
@@ -26,6 +30,10 @@ from ..hand import poses_as_reference
 
 HAND_DISTANCE = 0.013                 # the reference's hand_distance
 FINGERTIP_OFFSET = (0.0, 0.0, 0.133)  # "displacement of the fingertip from the center of the hand" (:100-104)
+# Where KinematicGrasp places the hand when it is not told: False = place_hand on the host, True = ops.hull_place.  The device form
+# is an option until a change of its own turns it on: its base poses may differ from the host's by one float32 ulp, and with them
+# everything downstream (profiles/grasp_place_ab.txt records whether the project's rule for a default is met).
+DEVICE_PLACEMENT_DEFAULT = False
 _DIRECTIONS = {}
 
 
@@ -102,25 +110,61 @@ def place_hand(verts, action, num_actions=50, hand_distance=HAND_DISTANCE, facet
 
 
 class KinematicGrasp:
-    """``grasp_table``: the finger frames of every action of a list of objects — placement on the host, ONE ``ops.grasp_close``
+    """``grasp_table``: the finger frames of every action of a list of objects — placement, then ONE ``ops.grasp_close``
     call for all placed grasps of all objects.  ``hand``: a ``HandModel``.  ``device``: where the closing runs (None: the GPU
-    when there is one; "cpu" takes the float64 NumPy form of the rule).  **Not pybullet: see the module's docstring.**"""
+    when there is one; "cpu" takes the float64 NumPy form of the rule).  ``placement``: "host" — ``place_hand`` per action on
+    SciPy's hull — or "device" — ONE ``ops.hull_place`` call for all actions of all objects, ``place_hand`` only for the pairs it
+    leaves undecided (status 2); None: ``DEVICE_PLACEMENT_DEFAULT``.  **Not pybullet: see the module's docstring.**"""
 
-    def __init__(self, hand, steps=64, device=None):
+    def __init__(self, hand, steps=64, device=None, placement=None):
+        if placement is None:
+            placement = "device" if DEVICE_PLACEMENT_DEFAULT else "host"
+        if placement not in ("host", "device"):
+            raise ValueError(f"a3vt: KinematicGrasp: placement={placement!r} must be None, 'host' or 'device'")
+        self.placement = placement
         self.hand, self.steps = hand, int(steps)
         self.device = utils._default_device() if device is None else torch.device(device)
         self.table = hand.table()
-        self.placement_seconds = 0.0          # host time of the last grasp_table call's place_hand calls (tools/grasp_bench.py)
+        self.placement_seconds = 0.0          # host time of the last grasp_table call up to its grasp_close call (tools/grasp_bench.py)
+        self.undecided = 0                    # pairs of the last grasp_table call that ops.hull_place left to place_hand
 
-    def grasp_table(self, geometry, ids, num_actions=50, want_q=False, want_blocked_step=False, want_hand_pose=False):
+    def _place_on_device(self, verts, verts_t, A):
+        """All (object, action) pairs in one ``ops.hull_place`` call and one read of its status -> ``placed`` (the (e, a) pairs
+        in row order), ``base_pos`` (G, 3) and ``base_rot`` (G, 3, 3) float32 on the device.  Pairs of status 2 go to
+        ``place_hand``, on a hull made when an object's first such pair comes up."""
+        found = _ops.hull_place(verts_t, np.cumsum([0] + [len(v) for v in verts]), directions(A), HAND_DISTANCE, FINGERTIP_OFFSET)
+        status = found["status"].cpu().numpy()
+        pos, rot = found["base_pos"].to(torch.float32).reshape(-1, 3), found["base_rot"].to(torch.float32).reshape(-1, 3, 3)
+        present = status == 0
+        hulls, rows, poses = {}, [], []
+        for e, a in np.argwhere(status == 2).tolist():
+            if e not in hulls:
+                hulls[e] = hull_facets(verts[e])
+            pose = place_hand(verts[e], a, A, facets=hulls[e]) if hulls[e] is not None else None
+            if pose is not None:
+                present[e, a] = True
+                rows.append(e * A + a)
+                poses.append(pose)
+        self.undecided = int((status == 2).sum())
+        if rows:
+            at = torch.tensor(rows, dtype=torch.int64, device=pos.device)
+            pos[at] = torch.from_numpy(np.array([p for p, _ in poses], np.float32)).to(pos.device)
+            rot[at] = torch.from_numpy(np.array([r for _, r in poses], np.float32)).to(pos.device)
+        placed = [tuple(pair) for pair in np.argwhere(present).tolist()]
+        at = torch.tensor([e * A + a for e, a in placed], dtype=torch.int64, device=pos.device)
+        return placed, pos[at], rot[at]
+
+    def grasp_table(self, geometry, ids, num_actions=50, want_q=False, want_blocked_step=False, want_hand_pose=False, want_base=False):
         """``geometry``: a mapping ``{id: (verts, faces)}``.  Returns a dict with ``pos`` (E, A, 4, 3) and ``rot`` (E, A, 4, 3, 3)
         float32 and ``present`` (E, A, 4) bool arrays — ``present`` is false, and the frames zero, for all four fingers of a grasp
         that could not be placed — and on request ``q`` (E, A, 16), ``blocked_step`` (E, A, 16) and ``hand_pose`` (E lists of A
-        entries: the reference's list of 28 ``(position, xyz-Euler)`` pairs, None for an unplaced grasp)."""
+        entries: the reference's list of 28 ``(position, xyz-Euler)`` pairs, None for an unplaced grasp) and ``base_pos``
+        (E, A, 3) / ``base_rot`` (E, A, 3, 3) float32, the hand's base poses as ``ops.grasp_close`` got them (``want_base``)."""
         import time
         E, A = len(ids), int(num_actions)
         verts, faces, offsets, base = [], [], [0], 0
         placed, base_pos, base_rot = [], [], []
+        self.undecided = 0
         start = time.perf_counter()
         for e, obj in enumerate(ids):
             v, f = geometry[obj]
@@ -129,6 +173,8 @@ class KinematicGrasp:
             faces.append(f + base)
             base += len(v)
             offsets.append(offsets[-1] + len(f))
+            if self.placement == "device":
+                continue
             facets = hull_facets(v)
             for a in range(A if facets is not None else 0):
                 pose = place_hand(v, a, A, facets=facets)
@@ -136,6 +182,11 @@ class KinematicGrasp:
                     placed.append((e, a))
                     base_pos.append(pose[0])
                     base_rot.append(pose[1])
+        up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype)).to(self.device)  # noqa: E731
+        verts_t = None
+        if self.placement == "device" and E:
+            verts_t = up(np.concatenate(verts), np.float32)
+            placed, base_pos, base_rot = self._place_on_device(verts, verts_t, A)
         self.placement_seconds = time.perf_counter() - start
         out = dict(pos=np.zeros((E, A, 4, 3), np.float32), rot=np.zeros((E, A, 4, 3, 3), np.float32), present=np.zeros((E, A, 4), bool))
         if want_q:
@@ -144,13 +195,20 @@ class KinematicGrasp:
             out["blocked_step"] = np.zeros((E, A, 16), np.int32)
         if want_hand_pose:
             out["hand_pose"] = [[None] * A for _ in range(E)]
+        if want_base:
+            out["base_pos"], out["base_rot"] = np.zeros((E, A, 3), np.float32), np.zeros((E, A, 3, 3), np.float32)
         if not placed:
             return out
-        up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype)).to(self.device)  # noqa: E731
         G = len(placed)
-        closed = _ops.grasp_close(up(np.concatenate(verts), np.float32), up(np.concatenate(faces), np.int32), offsets,
-                                  [e for e, _ in placed], up(np.array(base_pos).reshape(G, 3), np.float32),
-                                  up(np.array(base_rot).reshape(G, 3, 3), np.float32), self.table, self.hand.q0, self.steps)
+        if verts_t is None:
+            verts_t = up(np.concatenate(verts), np.float32)
+            base_pos_t, base_rot_t = up(np.array(base_pos).reshape(G, 3), np.float32), up(np.array(base_rot).reshape(G, 3, 3), np.float32)
+        else:
+            base_pos_t, base_rot_t = base_pos, base_rot
+            if want_base or want_hand_pose:
+                base_pos, base_rot = base_pos_t.cpu().numpy(), base_rot_t.cpu().numpy()
+        closed = _ops.grasp_close(verts_t, up(np.concatenate(faces), np.int32), offsets, [e for e, _ in placed], base_pos_t, base_rot_t,
+                                  self.table, self.hand.q0, self.steps)
         host = {name: t.cpu().numpy() for name, t in closed.items()
                 if name in ("frame_pos", "frame_rot") or (name == "q" and want_q) or (name == "blocked_step" and want_blocked_step)
                 or (name in ("link_pos", "link_rot") and want_hand_pose)}
@@ -160,6 +218,8 @@ class KinematicGrasp:
             out["q"][index] = host["q"]
         if want_blocked_step:
             out["blocked_step"][index] = host["blocked_step"]
+        if want_base:
+            out["base_pos"][index], out["base_rot"][index] = np.array(base_pos).reshape(G, 3), np.array(base_rot).reshape(G, 3, 3)
         if want_hand_pose:
             for g, (e, a) in enumerate(placed):
                 out["hand_pose"][e][a] = poses_as_reference(base_pos[g], base_rot[g], host["link_pos"][g], host["link_rot"][g])

@@ -373,7 +373,7 @@ def save_touch_signals(data_root, batch=8, num_actions=50, overwrite=False, devi
     return counts
 
 
-def save_simulation(data_root, hand, batch=8, num_actions=50, overwrite=False, steps=64, device=None, signals=True):
+def save_simulation(data_root, hand, batch=8, num_actions=50, overwrite=False, steps=64, device=None, signals=True, placement=None):
     """The reference's ``save_simulation`` (:122-209) on a tree: the grasp of every action of every object of
     ``<data_root>/object_info/``, then the vision image and the touch records.  **The grasp is ``KinematicGrasp``'s
     (``simulator/physics/grasping.py``): the reference's hand placement, and a kinematic closing rule that is a stand-in for five
@@ -383,7 +383,8 @@ def save_simulation(data_root, hand, batch=8, num_actions=50, overwrite=False, s
     dict, which ``recorded.tree_frames`` reads — one file for every finger of a placed grasp and none for a grasp that could not
     be placed ("no_intersection"; the action's directory is made either way, as the reference makes it).  ``batch`` objects per
     ``KinematicGrasp.grasp_table`` call (one ``ops.grasp_close`` call each), in sorted order of the ids.  ``hand``: a ``HandModel``
-    or a path ``HandModel.load`` takes (None: ``PTEROTACTYL_HAND``).
+    or a path ``HandModel.load`` takes (None: ``PTEROTACTYL_HAND``).  ``placement``: ``KinematicGrasp``'s — "host", "device"
+    (``ops.hull_place``: all actions of a batch's objects in one launch) or None for its default.
 
     Frames are never silently replaced: without ``overwrite`` an object that already holds any ``*_ref_frame.npy`` is skipped
     (``skipped_existing``) unless it carries the marker ``grasp_info/<id>/.baking`` of an interrupted run; such an object's frames,
@@ -411,7 +412,8 @@ def save_simulation(data_root, hand, batch=8, num_actions=50, overwrite=False, s
             counts["skipped_existing"] += 1
         else:
             todo.append(obj)
-    grasper = KinematicGrasp(hand, steps=steps, device=utils._default_device() if device is None else torch.device(device)) if todo else None
+    grasper = KinematicGrasp(hand, steps=steps, device=utils._default_device() if device is None else torch.device(device),
+                             placement=placement) if todo else None
     for at in range(0, len(todo), batch):
         group = todo[at:at + batch]
         geometry = {obj: (np.load(os.path.join(object_dir, f"{obj}_verts.npy")), np.load(os.path.join(object_dir, f"{obj}_faces.npy")))

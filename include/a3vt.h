@@ -819,6 +819,68 @@ double a3vt_grasp_reach(const double *hand_table, int chain);
 int a3vt_grasp_launches(long long *counts /*[2]*/, int reset);
 
 /* ---------------------------------------------------------------------------------------------
+ * The hand's placement on the convex hull of a mesh's vertices, without a hull (pterotactyl/simulator/physics/grasping.py::place_hand,
+ * csrc/hull_place.hip): the base pose of the hand for each of A actions on each of M meshes.
+ *
+ * place_hand uses only the farthest point t d of the ray from the origin along the action's direction d that is still inside the
+ * convex hull, and the plane of the facet there.  That is a linear programme in three variables: the largest t with t d in the
+ * convex hull of the vertices.  Its optimal basis is three vertices that span the facet.  It is solved by SUPPORT PASSES — the
+ * lowest index i of the largest n . v_i over the mesh's vertices — and no hull is built.
+ *
+ * The meshes: verts (V, 3) fp32 on the DEVICE; vert_offset (M + 1) a HOST table: mesh m owns the vertices vert_offset[m] ..
+ * vert_offset[m + 1] - 1, ALL of them, referenced by a face or not (as place_hand takes them).  directions (A, 3) and tip_offset
+ * (3) are HOST tables of doubles; d = directions[a] is used as given, not normalised, and t is in units of it.
+ *
+ * The rule, per mesh m and action a.  All arithmetic is float64 on the fp32 vertices converted exactly; no multiply-add is fused;
+ * a dot product is (n.x v.x + n.y v.y) + n.z v.z.
+ * 0. A mesh with fewer than 4 vertices or a non-finite coordinate: status 1 (place_hand returns None).  This check comes first.
+ * 1. Frame.  e = the coordinate axis of d's smallest |component| (the lowest axis on a tie); x = (d x e) / |d x e|,
+ *    y = (d x x) / |d x x|.  The projection of vertex v_i is p_i = (v_i . x, v_i . y).  The support along a 2-D direction u is the
+ *    support pass of n = u.x x + u.y y, and its support value is p_w . u of the winning vertex w.
+ * 2. Phase 1, a 2-D GJK on the p_i: a = support along (1, 0): p_a.x < 0 is status 1, p_a.x == 0 status 2.  b = support along
+ *    -p_a.  Then, up to 32 times: c = support along the normal of edge a b that faces the origin, (-e.y, e.x) or its negative for
+ *    e = p_b - p_a, by the sign of e.y p_a.x - e.x p_a.y.  With o_ac = (p_c - p_a) x (-p_a), b_ac = (p_c - p_a) x (p_b - p_a) and
+ *    o_bc, a_bc alike for edge b c: if o_ac and b_ac differ in sign the origin is outside edge a c, and c replaces b; else if o_bc
+ *    and a_bc differ, c replaces a; else the triangle's projection holds the origin and phase 1 ends.
+ *    Every support value below 0 is a separating direction: status 1, the ray misses.  Exact ties are status 2: a support value of
+ *    0, a support vertex already in the simplex, the origin on the line of the edge, one of the four cross products 0, the pass cap.
+ *    One exception: on the OPENING edge (a, b straight from the two opening supports) the origin on the edge's line is no tie — it
+ *    lies strictly between a and b since p_b . (-p_a) > 0 — and the search goes on along (-e.y, e.x).  That is the case of every
+ *    mesh that is symmetric about the origin, where b is a's antipode.
+ * 3. Phase 2, pivots, up to 64 times: N = (b - a) x (c - a), n = N / (N . d) (N . d == 0: status 2), t = n . a.  w = the support
+ *    pass of n, hi / lo the largest / smallest n . v_i.  If hi <= t or w is in the basis, the basis is optimal.  Otherwise w enters
+ *    and one vertex leaves by the ratio test: with area = (p_b - p_a) x (p_c - p_a) (0: status 2), lambda = (p_b x p_c, p_c x p_a,
+ *    p_a x p_b) / area clamped from below at 0 and mu = ((p_b - p_w) x (p_c - p_w), (p_c - p_w) x (p_a - p_w), (p_a - p_w) x
+ *    (p_b - p_w)) / area, the vertex k with the smallest lambda_k / mu_k over mu_k > 0 leaves (the first on a tie; none: status 2).
+ *    The pass cap is status 2.
+ * 4. Checks, in order: t <= 0 is status 1 (the line meets the hull behind the origin); hi - lo <= 1e-12 x the mesh's largest
+ *    |coordinate| is status 2 (a flat hull, which Qhull refuses; hi and lo are the last pass's, so this costs no pass).
+ * 5. The pose, place_hand line for line: point = d t; normal = N / |N|, negated if |point|^2 > |point + 1e-4 normal|^2;
+ *    position = point + hand_distance normal; normal -= 0.001 per component; b = normal / |normal|; with v = (-1, 0, 0) x b,
+ *    c = -b.x, s^2 = b.z^2 + b.y^2 and K the cross-product matrix of v: R = I + K + K K ((1 - c) / s^2); s^2 < 1e-24 is status 2
+ *    (the reference's reflection case); base_pos = position - R tip_offset.  (place_hand's quaternion round trips change R by
+ *    about 1e-16 and are not restated.)
+ *
+ * Outputs (DEVICE), written for every pair, row m A + a: status int32 — 0 placed, 1 no intersection (place_hand's None), 2 not
+ * decided here: the caller asks place_hand; base_pos (3) and base_rot (3 x 3, row-major) fp32, the float64 pose rounded once;
+ * simplex (3) int32, the basis's vertices as indices WITHIN the mesh; t float64.  Rows with status != 0 are zeros, simplex -1.
+ * No atomics: two calls write the same bytes, and a pair's row does not depend on the rest of the batch.
+ *
+ * One workgroup per pair, one launch per 128 meshes (all pairs in ONE launch for M <= 128: the directions and the launch's
+ * vertex ranges travel in the kernel arguments) on `stream`, no host synchronisation.
+ *
+ * Limits: 1 <= M <= 2^20; 1 <= A <= 128; M A <= 2^20; 0 <= V <= 2^28; vert_offset starts at >= 0, does not decrease and ends at
+ * <= V; directions, tip_offset and hand_distance finite, no direction zero.  Pointers non-NULL (verts may be NULL when V == 0)
+ * and 4-byte aligned (directions, tip_offset and t: 8).  Anything else returns non-zero with a message in a3vt_last_error that
+ * names hull_place, the argument and its value.  Nothing is launched.
+ *
+ * a3vt_hull_place_launches: [0] the a3vt_hull_place calls that launched since the last reset, [1] the kernels they launched;
+ * returns 2. */
+int a3vt_hull_place(const float *verts, int V, const int32_t *vert_offset, int M, const double *directions, int A, double hand_distance,
+                    const double *tip_offset, int32_t *status, float *base_pos, float *base_rot, int32_t *simplex, double *t, void *stream);
+int a3vt_hull_place_launches(long long *counts /*[2]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The ground-truth point cloud of a mesh: utility/data_making.py::extract_points (mesh_to_voxel, extract_ODMs, apply_ODMs,
  * voxel_to_pointcloud, realign_points of utility/utils.py) for a batch of M meshes.
  *
