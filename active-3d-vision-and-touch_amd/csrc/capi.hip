@@ -1901,6 +1901,133 @@ int a3vt_scene_render(const float *verts, int V, const int32_t *faces, const uin
 
 int a3vt_scene_launches(long long *counts, int reset) { return g_scene_launches.read(counts, reset); }
 
+// ---- scenes of posed instances (posed_render.hip) ------------------------------------------------------------------------------------
+namespace {
+LaunchCounts<3> g_posed_launches;
+
+// One HOST offset table of n + 1 entries against its table of `count` rows (scene_offsets_check under another name in the message).
+int posed_offsets_check(const char *who, const char *name, const int32_t *offset, int n, int count, const char *table) {
+  if (offset[0] < 0) {
+    set_error("%s: %s[0]=%d is below 0", who, name, (int)offset[0]);
+    return -1;
+  }
+  for (int m = 0; m < n; ++m) {
+    if (offset[m + 1] < offset[m]) {
+      set_error("%s: %s[%d]=%d is below %s[%d]=%d: offsets must not decrease", who, name, m + 1, (int)offset[m + 1], name, m,
+                (int)offset[m]);
+      return -1;
+    }
+  }
+  if (offset[n] > count) {
+    set_error("%s: %s[%d]=%d runs past %s=%d", who, name, n, (int)offset[n], table, count);
+    return -1;
+  }
+  return 0;
+}
+}  // namespace
+
+int a3vt_scene_render_posed(const float *part_verts, int PV, const int32_t *part_faces, int PF, const int32_t *part_face_offset,
+                            const float *part_bound, int P, const int32_t *inst_part, const float *inst_pos, const float *inst_rot,
+                            const uint8_t *inst_rgb, int N, const int32_t *inst_offset, const float *cam_pos, const float *cam_rot, int I,
+                            float yfov, float znear, float zfar, int W, int H, const float *lights, int L, float ambient,
+                            const uint8_t *background, uint8_t *rgb, float *depth, int32_t *prim_inst, int32_t *prim_face, void *stream) {
+  const char *who = "scene_render_posed";
+  if (check_range(who, "I", I, 1, kSceneMaxImages) || check_range(who, "P", P, 1, kPosedMaxParts) ||
+      check_range(who, "W", W, 1, kSceneMaxSide) || check_range(who, "H", H, 1, kSceneMaxSide) ||
+      check_range(who, "L", L, 0, kSceneMaxLights) || check_range(who, "PV", PV, 0, kSceneMaxIndex) ||
+      check_range(who, "PF", PF, 0, kSceneMaxIndex) || check_range(who, "N", N, 0, kPosedMaxInstances))
+    return -1;
+  if (!(yfov > 0.f && (double)yfov < 3.14159265358979323846)) {
+    set_error("%s: yfov=%g outside (0, pi)", who, (double)yfov);
+    return -1;
+  }
+  if (!(znear > 0.f)) {
+    set_error("%s: znear=%g must be > 0", who, (double)znear);
+    return -1;
+  }
+  if (!(znear < zfar && zfar <= 3.402823466e38f)) {
+    set_error("%s: zfar=%g must be finite and above znear=%g", who, (double)zfar, (double)znear);
+    return -1;
+  }
+  if (!(ambient >= -3.402823466e38f && ambient <= 3.402823466e38f)) {
+    set_error("%s: ambient=%g must be finite", who, (double)ambient);
+    return -1;
+  }
+  if (check_ptrs(who, {{"part_verts", part_verts, PV > 0, 4, "required when PV > 0"},
+                       {"part_faces", part_faces, PF > 0, 4, "required when PF > 0"},
+                       {"part_face_offset", part_face_offset, true, 4, "required (a host table)"},
+                       {"part_bound", part_bound, true, 4, "required (a host table)"},
+                       {"inst_part", inst_part, N > 0, 4, "required when N > 0"},
+                       {"inst_pos", inst_pos, N > 0, 4, "required when N > 0"},
+                       {"inst_rot", inst_rot, N > 0, 4, "required when N > 0"},
+                       {"inst_rgb", inst_rgb, N > 0, 1, "required when N > 0"},
+                       {"inst_offset", inst_offset, true, 4, "required (a host table)"},
+                       {"cam_pos", cam_pos, true, 4, "required"},
+                       {"cam_rot", cam_rot, true, 4, "required"},
+                       {"lights", lights, L > 0, 4, "required when L > 0 (a host table)"},
+                       {"background", background, true, 1, "required (a host table)"},
+                       {"rgb", rgb, true, 1, "required"},
+                       {"depth", depth, true, 4, "required"},
+                       {"prim_inst", prim_inst, prim_face != nullptr, 4, "required when prim_face is given"},
+                       {"prim_face", prim_face, prim_inst != nullptr, 4, "required when prim_inst is given"}}))
+    return -1;
+  // the host tables' contents
+  if (posed_offsets_check(who, "part_face_offset", part_face_offset, P, PF, "PF") ||
+      posed_offsets_check(who, "inst_offset", inst_offset, I, N, "N"))
+    return -1;
+  for (int p = 0; p < P; ++p) {
+    for (int k = 0; k < 4; ++k) {
+      const float x = part_bound[4 * p + k];
+      if (!(x >= (k == 3 ? 0.f : -3.402823466e38f) && x <= 3.402823466e38f)) {
+        set_error("%s: part_bound[%d][%d]=%g must be finite%s", who, p, k, (double)x, k == 3 ? " and not below 0" : "");
+        return -1;
+      }
+    }
+  }
+  const int rc = launch_scene_render_posed(part_verts, PV, part_faces, part_face_offset, part_bound, P, inst_part, inst_pos, inst_rot,
+                                           inst_rgb, inst_offset, cam_pos, cam_rot, I, yfov, znear, zfar, W, H, lights, L, ambient,
+                                           background, rgb, depth, prim_inst, prim_face, static_cast<hipStream_t>(stream));
+  if (rc < 0) return rc;
+  g_posed_launches.add(0, 1);
+  g_posed_launches.add(1, rc);
+  return 0;
+}
+
+int a3vt_pose_parts(const float *part_verts, int PV, const int32_t *part_faces, int PF, const int32_t *part_vert_offset,
+                    const int32_t *part_face_offset, int P, const int32_t *inst_part, const float *inst_pos, const float *inst_rot,
+                    const uint8_t *inst_rgb, int N, const int32_t *vert_base, const int32_t *face_base, float *verts_out, int TV,
+                    int32_t *faces_out, uint8_t *face_rgb_out, int TF, void *stream) {
+  const char *who = "pose_parts";
+  if (check_range(who, "P", P, 1, kPosedMaxParts) || check_range(who, "PV", PV, 0, kSceneMaxIndex) ||
+      check_range(who, "PF", PF, 0, kSceneMaxIndex) || check_range(who, "N", N, 0, kPosedMaxInstances) ||
+      check_range(who, "TV", TV, 0, kSceneMaxIndex) || check_range(who, "TF", TF, 0, kSceneMaxIndex))
+    return -1;
+  if (check_ptrs(who, {{"part_verts", part_verts, PV > 0, 4, "required when PV > 0"},
+                       {"part_faces", part_faces, PF > 0, 4, "required when PF > 0"},
+                       {"part_vert_offset", part_vert_offset, true, 4, "required (a host table)"},
+                       {"part_face_offset", part_face_offset, true, 4, "required (a host table)"},
+                       {"inst_part", inst_part, N > 0, 4, "required when N > 0"},
+                       {"inst_pos", inst_pos, N > 0, 4, "required when N > 0"},
+                       {"inst_rot", inst_rot, N > 0, 4, "required when N > 0"},
+                       {"inst_rgb", inst_rgb, N > 0, 1, "required when N > 0"},
+                       {"vert_base", vert_base, N > 0, 4, "required when N > 0"},
+                       {"face_base", face_base, N > 0, 4, "required when N > 0"},
+                       {"verts_out", verts_out, TV > 0, 4, "required when TV > 0"},
+                       {"faces_out", faces_out, TF > 0, 4, "required when TF > 0"},
+                       {"face_rgb_out", face_rgb_out, TF > 0, 1, "required when TF > 0"}}))
+    return -1;
+  if (posed_offsets_check(who, "part_vert_offset", part_vert_offset, P, PV, "PV") ||
+      posed_offsets_check(who, "part_face_offset", part_face_offset, P, PF, "PF"))
+    return -1;
+  const int rc = launch_pose_parts(part_verts, part_faces, part_vert_offset, part_face_offset, P, inst_part, inst_pos, inst_rot, inst_rgb,
+                                   N, vert_base, face_base, verts_out, TV, faces_out, face_rgb_out, TF, static_cast<hipStream_t>(stream));
+  if (rc < 0) return rc;
+  g_posed_launches.add(2, rc);
+  return 0;
+}
+
+int a3vt_posed_launches(long long *counts, int reset) { return g_posed_launches.read(counts, reset); }
+
 // ---- the ground-truth point cloud of a batch of meshes (voxel.hip) -----------------------------------------------------------------
 namespace {
 LaunchCounts<3> g_voxel_launches;

@@ -486,6 +486,38 @@ int launch_scene_render(const float *verts, int V, const int32_t *faces, const u
                         const float *cam_rot, int I, float yfov, float znear, float zfar, int W, int H, const float *lights, int L,
                         float ambient, const uint8_t *background, uint8_t *rgb, float *depth, int32_t *prim, hipStream_t s);
 
+// posed_render.hip: scene_render's images of scenes of INSTANCES — a part (a face range of a shared template table) under a rigid pose
+// with one colour — without writing the posed triangles out; and pose_parts, which does write them out, by the same device function.
+// The per-image instance ranges and the per-part tables travel by value: with the lights they stay below 4 KiB of kernel arguments.
+constexpr int kPosedMaxParts = 96;            // P (24 bytes each of the kernel-argument block)
+constexpr int kPosedMaxInstances = 1 << 24;   // N
+struct PosedTables {
+  int32_t inst0[kSceneImagesPerLaunch], inst1[kSceneImagesPerLaunch];   // image i of the launch owns the instances inst0[i] .. inst1[i] - 1
+  int32_t face0[kPosedMaxParts], face1[kPosedMaxParts];                 // part p owns the faces face0[p] .. face1[p] - 1 of part_faces
+  float bound[kPosedMaxParts][4];                                       // centre and radius of a sphere around part p's vertices
+  float light[kSceneMaxLights][4];                                      // position, intensity
+  int32_t n_parts, n_lights;
+  float ambient;
+  uint8_t background[4];
+};
+struct PosedParts {                           // pose_parts: part p owns the vertices vert0[p] .. vert1[p] - 1 and the faces face0[p] .. face1[p] - 1
+  int32_t vert0[kPosedMaxParts], vert1[kPosedMaxParts], face0[kPosedMaxParts], face1[kPosedMaxParts];
+  int32_t n_parts;
+};
+// part_face_offset (P + 1), part_bound (P x 4), inst_offset (I + 1), lights and background on the HOST, already checked.  Returns the
+// number of launches, or a negative error code with the message set.
+int launch_scene_render_posed(const float *part_verts, int PV, const int32_t *part_faces, const int32_t *part_face_offset,
+                              const float *part_bound, int P, const int32_t *inst_part, const float *inst_pos, const float *inst_rot,
+                              const uint8_t *inst_rgb, const int32_t *inst_offset, const float *cam_pos, const float *cam_rot, int I,
+                              float yfov, float znear, float zfar, int W, int H, const float *lights, int L, float ambient,
+                              const uint8_t *background, uint8_t *rgb, float *depth, int32_t *prim_inst, int32_t *prim_face,
+                              hipStream_t s);
+// part_vert_offset and part_face_offset (P + 1) on the HOST, already checked; vert_base and face_base (N + 1) on the device.
+int launch_pose_parts(const float *part_verts, const int32_t *part_faces, const int32_t *part_vert_offset, const int32_t *part_face_offset,
+                      int P, const int32_t *inst_part, const float *inst_pos, const float *inst_rot, const uint8_t *inst_rgb, int N,
+                      const int32_t *vert_base, const int32_t *face_base, float *verts_out, int TV, int32_t *faces_out,
+                      uint8_t *face_rgb_out, int TF, hipStream_t s);
+
 // voxel.hip: the ground-truth point cloud of a batch of meshes (utility/data_making.py::extract_points): voxelise by adaptive
 // subdivision, column ranges (the six depth maps), carve + surface, realign + gather.  The launch_* return the number of operations
 // they enqueued (kernels, the clear, the optional copies), or a negative error code with the message set.

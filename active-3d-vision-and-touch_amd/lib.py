@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("A3VT_LIB", os.path.join(_HERE, "liba3vt.so"))  # A3VT
 SOURCES = ["capi.hip", "gcn_gemm.hip", "gcn_gemmw.hip", "gcn_dww.hip", "gcn_gemm16.hip", "gcn_gemm3.hip", "gcn_csr.hip", "gcn_csrq.hip", "gcn_csrqs.hip", "gcn_bf16s.hip", "posenc.hip", "posenc_wide.hip", "bias_grad.hip", "bnrelu.hip", "conv5.hip", "conv5f.hip", "adam.hip", "sample.hip", "chamfer.hip", "nn_prune.hip",
            "pooling.hip", "fold.hip", "ddqn.hip", "qnet_input.hip", "latent_nn.hip", "latent_policy.hip", "ddqn_latent.hip",
            "candidate_tally.hip", "touch_render.hip", "voxel.hip", "scene_render.hip", "touch_assemble.hip", "chart_head.hip",
-           "touch_pack.hip", "grasp_close.hip", "hull_place.hip"]
+           "touch_pack.hip", "grasp_close.hip", "hull_place.hip", "posed_render.hip"]
 # Per-file extra flags (none at present; sample.hip / gcn_csr.hip rely on IEEE NaN semantics — the reference's NaN
 # scrubs, a3vt_check_finite — so fast-math style flags must never be applied globally).
 # chamfer.hip: keep the nearest-neighbour loop on scalar fp32 ops (the SLP vectoriser would re-pack it into v_pk_*_f32,

@@ -2123,6 +2123,166 @@ def scene_render(verts, faces, face_rgb, centres, radii, sphere_rgb, face_offset
     return out
 
 
+POSED_LIMITS = dict(parts=96, instances=1 << 24)    # csrc/kernels.h's kPosedMaxParts / kPosedMaxInstances
+
+
+def posed_launches(reset=False):
+    """``a3vt_scene_render_posed`` calls accepted, the kernels they launched and the kernels of ``a3vt_pose_parts`` since the last
+    reset (a test hook, as ``scene_launches``)."""
+    return _launch_counts("a3vt_posed_launches", ("calls", "kernels", "pose_parts"), reset)
+
+
+class PartTable:
+    """The template parts of ``scene_render_posed`` / ``pose_parts``: ``parts`` is a sequence of ``(verts (n, 3), faces (m, 3))``
+    HOST arrays, the faces with indices into their own part's vertices.  Holds ``verts`` (PV, 3) float32 and ``faces`` (PF, 3) int32
+    (made global) on ``device`` (None: the current GPU; "cpu" keeps them on the host, for ``pose_parts``' NumPy form), and on the
+    host ``vert_offset`` / ``face_offset`` (P + 1,) int32 and ``bound`` (P, 4) float32: per part the middle of the finite vertices'
+    bounds and the largest distance to one, computed in float64 against the float32 centre and rounded UP to float32 (a part
+    without a finite vertex gets a zero sphere: none of its faces can be hit).  A face index outside its part's vertices is refused."""
+
+    def __init__(self, parts, device=None):
+        parts = [(np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3)) for v, f in parts]
+        if not 1 <= len(parts) <= POSED_LIMITS["parts"]:
+            raise ValueError(f"a3vt: PartTable holds 1..{POSED_LIMITS['parts']} parts (they travel in the launch's arguments), got {len(parts)}")
+        verts, faces, bound, base = [], [], np.zeros((len(parts), 4), np.float32), 0
+        for p, (v, f) in enumerate(parts):
+            if len(f) and (f.min() < 0 or f.max() >= len(v)):
+                raise ValueError(f"a3vt: PartTable: part {p} has face indices outside its {len(v)} vertices")
+            verts.append(v)
+            faces.append(f + base)
+            base += len(v)
+            good = v[np.isfinite(v).all(axis=1)].astype(np.float64)
+            if len(good):
+                centre = ((good.min(axis=0) + good.max(axis=0)) / 2).astype(np.float32)
+                radius = np.sqrt(((good - centre.astype(np.float64)) ** 2).sum(axis=1).max()) * (1 + 2.0 ** -50)
+                r32 = np.float32(radius)
+                bound[p, :3], bound[p, 3] = centre, r32 if float(r32) >= radius else np.nextafter(r32, np.float32(np.inf))
+        self.num_parts = len(parts)
+        self.vert_offset = np.cumsum([0] + [len(v) for v, _ in parts]).astype(np.int32)
+        self.face_offset = np.cumsum([0] + [len(f) for _, f in parts]).astype(np.int32)
+        self.bound = bound
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.verts = torch.from_numpy(np.concatenate(verts).astype(np.float32).reshape(-1, 3)).to(device)
+        self.faces = torch.from_numpy(np.concatenate(faces).astype(np.int32).reshape(-1, 3)).to(device)
+
+
+def _posed_instances(table, inst_part, inst_pos, inst_rot, inst_rgb, who, cuda):
+    if not isinstance(table, PartTable):
+        raise ValueError(f"a3vt: {who} wants an ops.PartTable")
+    if cuda:
+        inst_part, inst_rgb = _req(inst_part, "inst_part", torch.int32), _req(inst_rgb, "inst_rgb", torch.uint8)
+        inst_pos, inst_rot = _req(inst_pos, "inst_pos"), _req(inst_rot, "inst_rot")
+        _req(table.verts, "table.verts"), _req(table.faces, "table.faces", torch.int32)
+    N = inst_part.shape[0]
+    if inst_part.shape != (N,) or inst_pos.shape != (N, 3) or inst_rot.shape != (N, 3, 3) or inst_rgb.shape != (N, 3):
+        raise ValueError(f"a3vt: {who} wants inst_part (N,), inst_pos (N, 3), inst_rot (N, 3, 3) and inst_rgb (N, 3), got "
+                         f"{tuple(inst_part.shape)}, {tuple(inst_pos.shape)}, {tuple(inst_rot.shape)} and {tuple(inst_rgb.shape)}")
+    return inst_part, inst_pos, inst_rot, inst_rgb, N
+
+
+def scene_render_posed(table, inst_part, inst_pos, inst_rot, inst_rgb, inst_offset, cam_pos, cam_rot, yfov=VISION_DEFAULTS["yfov"],
+                       znear=VISION_DEFAULTS["znear"], zfar=VISION_DEFAULTS["zfar"], width=VISION_DEFAULTS["width"],
+                       height=VISION_DEFAULTS["height"], lights=VISION_DEFAULTS["lights"], ambient=VISION_DEFAULTS["ambient"],
+                       background=VISION_DEFAULTS["background"], want_prim=True):
+    """Colour, depth and primitive images of I views over scenes of posed INSTANCES of ``table``'s parts
+    (``a3vt_scene_render_posed``, csrc/posed_render.hip: one launch per 128 images on the current stream, no workspace, no host
+    synchronisation).  ``scene_render``'s ray caster and Lambert shading — NOT pyrender's shader, never compared with it, no alpha.
+
+    Device tensors: ``inst_part`` (N,) int32, ``inst_pos`` (N, 3) and ``inst_rot`` (N, 3, 3) float32, ``inst_rgb`` (N, 3) uint8,
+    ``cam_pos`` (I, 3), ``cam_rot`` (I, 3, 3).  Host tables: ``inst_offset`` (I + 1,) — image i owns the instances
+    ``inst_offset[i] .. inst_offset[i + 1] - 1`` —, ``lights``, ``background``.  A vertex v of an instance becomes
+    ``fma(R[r][0], v.x, fma(R[r][1], v.y, fma(R[r][2], v.z, p[r])))`` per row; from there the rule is ``scene_render``'s, so ``rgb``
+    and ``depth`` equal ``scene_render`` on ``pose_parts``' output bit for bit.  An instance with a part id outside the table or a
+    non-finite pose is skipped.  Returns ``{"rgb", "depth"}`` and, with ``want_prim``, ``"prim_inst"`` (the instance's index) and
+    ``"prim_face"`` (the face's index into ``table.faces``), both -1 without a hit.  The whole contract is in ``include/a3vt.h``."""
+    inst_part, inst_pos, inst_rot, inst_rgb, N = _posed_instances(table, inst_part, inst_pos, inst_rot, inst_rgb, "scene_render_posed", True)
+    cam_pos, cam_rot = _req(cam_pos, "cam_pos"), _req(cam_rot, "cam_rot")
+    I = cam_pos.shape[0]
+    if cam_pos.shape != (I, 3) or cam_rot.shape != (I, 3, 3) or I < 1:
+        raise ValueError(f"a3vt: scene_render_posed wants cam_pos (I, 3) and cam_rot (I, 3, 3), I >= 1, got {tuple(cam_pos.shape)} and "
+                         f"{tuple(cam_rot.shape)}")
+    inst_offset = _host_table(inst_offset, "inst_offset", np.int32, (I + 1,))
+    lights = _host_table(np.zeros((0, 4)) if len(lights) == 0 else lights, "lights", np.float32, (None, 4))
+    background = _host_table(background, "background", np.uint8, (3,))
+    W, H = int(width), int(height)
+    if not (1 <= W <= SCENE_LIMITS["side"] and 1 <= H <= SCENE_LIMITS["side"]):      # (before the outputs are sized by them)
+        raise RuntimeError(f"a3vt: scene_render_posed: W={W} H={H} outside 1..{SCENE_LIMITS['side']}")
+    dev = cam_pos.device
+    rgb = torch.empty((I, H, W, 3), dtype=torch.uint8, device=dev)
+    depth = torch.empty((I, H, W), dtype=torch.float32, device=dev)
+    prim_inst = torch.empty((I, H, W), dtype=torch.int32, device=dev) if want_prim else None
+    prim_face = torch.empty((I, H, W), dtype=torch.int32, device=dev) if want_prim else None
+    host = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    PV, PF = table.verts.shape[0], table.faces.shape[0]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().a3vt_scene_render_posed(
+            _lib.ptr(table.verts) if PV else None, PV, _lib.ptr(table.faces) if PF else None, PF, host(table.face_offset), host(table.bound),
+            table.num_parts, *((_lib.ptr(t) if N else None) for t in (inst_part, inst_pos, inst_rot, inst_rgb)), N, host(inst_offset),
+            _lib.ptr(cam_pos), _lib.ptr(cam_rot), I, float(yfov), float(znear), float(zfar), W, H, host(lights), len(lights), float(ambient),
+            host(background), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(prim_inst), _lib.ptr(prim_face), _stream()), "scene_render_posed")
+    out = {"rgb": rgb, "depth": depth}
+    if want_prim:
+        out["prim_inst"], out["prim_face"] = prim_inst, prim_face
+    return out
+
+
+def pose_parts(table, inst_part, inst_pos, inst_rot, inst_rgb, inst_offset=None):
+    """The instances of ``scene_render_posed`` written out as triangles (``a3vt_pose_parts``, one launch): instance by instance, the
+    part's vertices posed by the kernel's own device function, its faces re-based onto them, the instance's colour per face.
+    Returns ``verts`` (TV, 3), ``faces`` (TF, 3) int32, ``face_rgb`` (TF, 3) uint8 — what ``scene_render`` takes — and on the host
+    ``vert_base`` / ``face_base`` (N + 1,): instance n owns the rows ``base[n] .. base[n + 1] - 1``, so its face ``f`` of
+    ``table.faces`` is row ``face_base[n] + f - table.face_offset[part]``; with ``inst_offset`` (I + 1,) also ``face_offset``
+    (I + 1,), the images' face ranges.  An instance with a part id outside the table owns no rows.  ``inst_part`` is read on the
+    host to size the output: this call synchronises, unlike the renderer.
+
+    CPU tensors take the same rule in NumPy, each fma as a float64 product and sum rounded to float32 once — which may differ from
+    the device's single rounding in the last bit (double rounding)."""
+    cuda = isinstance(inst_pos, torch.Tensor) and inst_pos.is_cuda
+    inst_part, inst_pos, inst_rot, inst_rgb, N = _posed_instances(table, inst_part, inst_pos, inst_rot, inst_rgb, "pose_parts", cuda)
+    part = inst_part.cpu().numpy().astype(np.int64)
+    known = (part >= 0) & (part < table.num_parts)
+    safe = np.where(known, part, 0)
+    vert_base = np.concatenate([[0], np.cumsum(np.where(known, np.diff(table.vert_offset)[safe], 0))]).astype(np.int64)
+    face_base = np.concatenate([[0], np.cumsum(np.where(known, np.diff(table.face_offset)[safe], 0))]).astype(np.int64)
+    TV, TF = int(vert_base[-1]), int(face_base[-1])
+    if max(TV, TF) > 1 << 28:
+        raise ValueError(f"a3vt: pose_parts: {TV} vertices / {TF} faces are more than the {1 << 28} of one table")
+    out = {"vert_base": vert_base.astype(np.int32), "face_base": face_base.astype(np.int32)}
+    if inst_offset is not None:
+        out["face_offset"] = face_base[np.asarray(_host_table(inst_offset, "inst_offset", np.int32, (None,)), np.int64)].astype(np.int32)
+    if not cuda:
+        pv, pf = table.verts.cpu().numpy(), table.faces.cpu().numpy()
+        pos, rot, rgb = inst_pos.numpy().astype(np.float64), inst_rot.numpy().astype(np.float64), inst_rgb.numpy()
+        verts, faces, face_rgb = np.zeros((TV, 3), np.float32), np.zeros((TF, 3), np.int32), np.zeros((TF, 3), np.uint8)
+        fma = lambda a, b, c: (a * b + c).astype(np.float32).astype(np.float64)  # noqa: E731
+        for n in np.flatnonzero(known):
+            v0, v1 = table.vert_offset[part[n]], table.vert_offset[part[n] + 1]
+            f0, f1 = table.face_offset[part[n]], table.face_offset[part[n] + 1]
+            v = pv[v0:v1].astype(np.float64)
+            with np.errstate(invalid="ignore", over="ignore"):
+                for r in range(3):
+                    verts[vert_base[n]:vert_base[n + 1], r] = fma(rot[n, r, 0], v[:, 0], fma(rot[n, r, 1], v[:, 1],
+                                                                                             fma(rot[n, r, 2], v[:, 2], pos[n, r])))
+            local = pf[f0:f1].astype(np.int64) - v0
+            faces[face_base[n]:face_base[n + 1]] = np.where((local >= 0) & (local < v1 - v0), local + vert_base[n], -1)
+            face_rgb[face_base[n]:face_base[n + 1]] = rgb[n]
+        return dict(out, verts=torch.from_numpy(verts), faces=torch.from_numpy(faces), face_rgb=torch.from_numpy(face_rgb))
+    dev = inst_pos.device
+    verts = torch.empty((TV, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((TF, 3), dtype=torch.int32, device=dev)
+    face_rgb = torch.empty((TF, 3), dtype=torch.uint8, device=dev)
+    vb, fb = torch.from_numpy(out["vert_base"]).to(dev), torch.from_numpy(out["face_base"]).to(dev)
+    host = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    PV, PF = table.verts.shape[0], table.faces.shape[0]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().a3vt_pose_parts(
+            _lib.ptr(table.verts) if PV else None, PV, _lib.ptr(table.faces) if PF else None, PF, host(table.vert_offset),
+            host(table.face_offset), table.num_parts, *((_lib.ptr(t) if N else None) for t in (inst_part, inst_pos, inst_rot, inst_rgb)),
+            N, _lib.ptr(vb) if N else None, _lib.ptr(fb) if N else None, _lib.ptr(verts) if TV else None, TV,
+            _lib.ptr(faces) if TF else None, _lib.ptr(face_rgb) if TF else None, TF, _stream()), "pose_parts")
+    return dict(out, verts=verts, faces=faces, face_rgb=face_rgb)
+
+
 # csrc/kernels.h's kVoxelMinDim / kVoxelMaxDim / kVoxelMaxMeshes / kVoxelMaxCells / kVoxelMaxDepth
 VOXEL_LIMITS = dict(min_dim=4, max_dim=256, meshes=4096, cells=1 << 30, depth=12)
 

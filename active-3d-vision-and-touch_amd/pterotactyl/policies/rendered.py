@@ -17,6 +17,7 @@ The result dict has the reference's keys (its spellings included):
     finger_transform_rot_M   (E, 4, 3, 3) float32
     touch_point_cloud        on request: per element four float32 arrays (n, 3), empty (0, 3) for a finger that is not "touch"
     vision                   on request: E arrays (H, W, 3) uint8, the object alone under the reference's vision scene
+    vision_occluded          on request (needs ``hand_visual``): E arrays (H, W, 3) uint8, the object with the posed hand in front
 
 Sources:
 * frames: a mapping ``{(object_id, action): (pos (4, 3), rot (4, 3, 3), present (4,) bool)}`` or a dataset root holding
@@ -36,9 +37,18 @@ end to end (``ops.touch_pack``, one more launch) — which is what ``data_making
 ``ops.VISION_DEFAULTS`` (``simulator/rendering/vision_renderer.py:35-77``).  THE SHADING IS NOT PYRENDER'S: it is ``scene_render``'s
 Lambert model on ray-cast hits at pixel centres, and no image of it has been compared with one of pyrender's.
 
+``vision_occluded=True`` adds the reference's occluded view (``sampler.py:166-173``: the same scene after ``update_hand``): the
+object and the 21 nodes of a ``simulator/hand.py::HandVisual`` posed by the grasp's links (``frames.hand_links``), all K * E images of
+a ``sample_many`` from ONE ``ops.scene_render_posed`` call (``a3vt_scene_render_posed``, csrc/posed_render.hip), which draws rigid
+instances of shared parts without writing the posed triangles out.  Stated deviations: Lambert shading, not pyrender's, and no
+image compared with one of pyrender's; the digit is drawn OPAQUE (pyrender blends its alpha of 175; ``object_colours``' alpha is
+ignored likewise); faces are taken as stored, no ``add_faces``; the poses are the kinematic grasp's, not Bullet's; the parts sit in the
+URDF link frames (the reference's ``getLinkState(...)[:2]`` is the inertial frame: no link of the URDF gives its ``<inertial>`` an
+origin, so the two coincide); an UNPLACED grasp shows the object alone (the reference leaves the hand wherever Bullet has it).
+
 Frames are an input here.  ``simulator/physics/grasping.py::GraspFrames`` makes them from the meshes by a KINEMATIC grasp (not
 pybullet's dynamics, never compared with pybullet's frames) and is passed as ``frames`` unchanged.  Out of scope: Bullet's grasp
-physics, the TACTO renderer and the hand meshes in the vision scene (``vision_occluded``)."""
+physics and the TACTO renderer."""
 import os
 from collections.abc import Mapping
 
@@ -56,6 +66,12 @@ MAX_VIEWS = 1 << 16                     # views of one a3vt_touch_render call (c
 # sizes (profiles/touch_signals_ab.txt).  Measured: 1.49 x at 1 600 views with a fifth of the pixels in contact, no difference at 12
 # views or with every pixel in contact — the rule is not met, the packed read is an option.
 PACK_POINTS_DEFAULT = False
+# Whether ``vision_occluded`` images come from the posed kernel (``ops.scene_render_posed``) or from the materialised form
+# (``ops.pose_parts``, then ``ops.scene_render``) when the caller does not say; the bits are the same.  The project's rule for a
+# default: True only where tools/occluded_bench.py measured the posed kernel's p90 below the materialised form's p10 at both sizes
+# (profiles/occluded_vision_ab.txt).  Measured, host wall: 0.68 ms against 0.78 at I = 3 and 5.07 against 6.60 at I = 150 (1.16 x and
+# 1.30 x), p90 below p10 at both, with 66 MiB against 152 MiB of allocator peak at I = 150: the rule is met.
+POSED_RENDER_DEFAULT = True
 
 
 def pack_host(out, want_touch=True, want_points=True, capacity=None):
@@ -86,7 +102,7 @@ def camera_matrix(orientation):
 class RenderedSampler:
     def __init__(self, frames, geometry=None, bs=None, vision=False, render=None, to_host=True, device=None, max_depth=0.025,
                  yfov=40.0 / 180.0 * np.pi, znear=1e-4, zfar=10.0, resolution=[256, 256], object_colours=None, render_scene=None,
-                 pack=None, pack_points=None):
+                 pack=None, pack_points=None, hand_visual=None, render_posed=None):
         """``frames`` / ``geometry``: the sources described above (``geometry=None``: the ``.npy`` files beside the names).  ``bs``
         and ``vision`` are accepted for the reference's constructor shape and not needed.  ``render``: a callable with the
         signature and result of ``ops.touch_render`` that replaces it — it then gets CPU tensors unless ``device`` says otherwise
@@ -96,7 +112,11 @@ class RenderedSampler:
         ``resolution`` (width, height) and ``object_colours`` — one RGB(A) colour or one per loaded object, None: the reference's
         (228, 217, 111); alpha is ignored — are the reference's, for ``vision=True``.  ``render_scene`` / ``pack``: callables that
         replace ``ops.scene_render`` / ``ops.touch_pack`` (with a ``render`` given, ``pack`` defaults to ``pack_host``).
-        ``pack_points``: whether contact clouds are read back packed; None: ``PACK_POINTS_DEFAULT``.  The results are the same bits."""
+        ``pack_points``: whether contact clouds are read back packed; None: ``PACK_POINTS_DEFAULT``.  The results are the same bits.
+
+        ``hand_visual``: a ``simulator/hand.py::HandVisual``, for ``vision_occluded=True``; ``frames`` must then offer
+        ``hand_links(object_id, action)`` (``GraspFrames`` does; a data-set tree stores no link poses).  ``render_posed``: a callable
+        that replaces ``ops.scene_render_posed``."""
         if not isinstance(frames, Mapping) and not os.path.isdir(os.path.join(str(frames), "grasp_info")):
             raise ValueError(f"RenderedSampler: {frames!r} is neither a mapping of frames nor a directory holding grasp_info/")
         if geometry is not None and not isinstance(geometry, Mapping):
@@ -114,6 +134,7 @@ class RenderedSampler:
         self.pack_points = PACK_POINTS_DEFAULT if pack_points is None else bool(pack_points)
         self.device = torch.device("cpu") if device is None else torch.device(device)
         self.resolution, self.object_colours = (int(resolution[0]), int(resolution[1])), object_colours
+        self.hand_visual, self.render_posed, self.parts = hand_visual, render_posed, None
         self.ids, self.table, self.face_offset = [], None, [0]
 
     def load_objects(self, batch, from_dataset=True, scale=3.1):
@@ -139,6 +160,11 @@ class RenderedSampler:
         self.table = (up(np.concatenate(verts) if verts else np.zeros((0, 3)), np.float32),
                       up(np.concatenate(faces) if faces else np.zeros((0, 3)), np.int32), up(np.array(offsets), np.int32))
         self.face_offset = offsets
+        self.parts = None
+        if self.hand_visual is not None:                       # the hand's parts, then one part per object: one table for the call
+            from ... import ops
+            local = [(v, f - b) for v, f, b in zip(verts, faces, np.cumsum([0] + [len(v) for v in verts]))]
+            self.parts = ops.PartTable(list(self.hand_visual.parts) + local, device=self.device)
 
     def frames_of(self, obj, action):
         if isinstance(self.frames, Mapping):
@@ -159,17 +185,8 @@ class RenderedSampler:
             raise ValueError(f"RenderedSampler: {len(parameters)} camera parameters for {E} loaded objects")
         if E == 0:
             return []
-        cam_pos, cam_rot = np.tile(np.asarray(D["cam_pos"], np.float32), (E, 1)), np.zeros((E, 3, 3), np.float32)
-        cam_rot[:] = camera_matrix(D["cam_euler_xyz_deg"])
-        for e, pair in enumerate(parameters or ()):
-            if pair is not None:
-                cam_pos[e], cam_rot[e] = np.asarray(pair[0], np.float32).reshape(3), camera_matrix(pair[1])
-        colours = np.asarray(D["colour"] if self.object_colours is None else self.object_colours)
-        if colours.ndim == 1:
-            colours = np.tile(colours, (E, 1))
-        if colours.shape not in ((E, 3), (E, 4)):
-            raise ValueError(f"RenderedSampler: object_colours is one RGB(A) colour or one per object ({E}), got shape {colours.shape}")
-        per_face = np.repeat(np.ascontiguousarray(colours[:, :3], np.uint8), np.diff(self.face_offset), axis=0)
+        cam_pos, cam_rot = self._vision_cameras(parameters)
+        per_face = np.repeat(self._object_rgb(), np.diff(self.face_offset), axis=0)
         verts, faces, _ = self.table
         dev = verts.device
         render_scene = ops.scene_render if self.render_scene is None else self.render_scene
@@ -180,6 +197,106 @@ class RenderedSampler:
                            ambient=D["ambient"], background=D["background"], want_prim=False)["rgb"]
         return list(rgb.cpu().numpy()) if self.to_host else list(rgb)
 
+    def _vision_cameras(self, parameters):
+        """The E elements' vision cameras ``(cam_pos (E, 3), cam_rot (E, 3, 3))`` float32: the reference's, moved per element by
+        ``parameters``."""
+        from ... import ops
+        D, E = ops.VISION_DEFAULTS, len(self.ids)
+        cam_pos, cam_rot = np.tile(np.asarray(D["cam_pos"], np.float32), (E, 1)), np.zeros((E, 3, 3), np.float32)
+        cam_rot[:] = camera_matrix(D["cam_euler_xyz_deg"])
+        for e, pair in enumerate(parameters or ()):
+            if pair is not None:
+                cam_pos[e], cam_rot[e] = np.asarray(pair[0], np.float32).reshape(3), camera_matrix(pair[1])
+        return cam_pos, cam_rot
+
+    def _object_rgb(self):
+        """``object_colours`` as (E, 3) uint8, alpha dropped."""
+        from ... import ops
+        E = len(self.ids)
+        colours = np.asarray(ops.VISION_DEFAULTS["colour"] if self.object_colours is None else self.object_colours)
+        if colours.ndim == 1:
+            colours = np.tile(colours, (E, 1))
+        if colours.shape not in ((E, 3), (E, 4)):
+            raise ValueError(f"RenderedSampler: object_colours is one RGB(A) colour or one per object ({E}), got shape {colours.shape}")
+        return np.ascontiguousarray(colours[:, :3], np.uint8)
+
+    def occluded_instances(self, action_lists, parameters=None):
+        """The instance tables of the K * E occluded images, image (k, e) at row k * E + e, as host arrays: ``inst_part``,
+        ``inst_pos``, ``inst_rot``, ``inst_rgb``, ``inst_offset`` (K * E + 1,), ``cam_pos``, ``cam_rot``.  Per image: the element's
+        object (part ``len(hand_visual.parts) + e``) under the identity in its ``object_colours`` colour, then — unless the grasp
+        could not be placed — the hand's 21 nodes in ``HandVisual``'s order, each under its link's pose (the base's for link -1)."""
+        hv, E = self.hand_visual, len(self.ids)
+        if not hasattr(self.frames, "hand_links"):
+            raise ValueError("RenderedSampler: vision_occluded needs the grasp's link poses, and this `frames` source has no "
+                             "hand_links(object_id, action) (a data-set tree stores finger frames only): pass a GraspFrames")
+        if self.parts is None:
+            raise RuntimeError("RenderedSampler: load_objects has not been called")
+        if parameters is not None and len(parameters) != E:
+            raise ValueError(f"RenderedSampler: {len(parameters)} camera parameters for {E} loaded objects")
+        for actions in action_lists:
+            if len(actions) != E:
+                raise ValueError(f"RenderedSampler: {len(actions)} actions for {E} loaded objects")
+        K = len(action_lists)
+        colours, (cam_pos, cam_rot) = self._object_rgb(), self._vision_cameras(parameters)
+        node_part = np.array([n[0] for n in hv.nodes], np.int32)
+        node_link = np.array([n[1] for n in hv.nodes], np.int64)
+        node_rgb = np.array([n[2] for n in hv.nodes], np.uint8).reshape(-1, 3)
+        part, pos, rot, rgb, offset = [], [], [], [], [0]
+        eye = np.eye(3, dtype=np.float32)
+        for actions in action_lists:
+            for e, (obj, action) in enumerate(zip(self.ids, actions)):
+                part.append(np.array([len(hv.parts) + e], np.int32))
+                pos.append(np.zeros((1, 3), np.float32))
+                rot.append(eye[None])
+                rgb.append(colours[e:e + 1])
+                links = self.frames.hand_links(obj, int(action))
+                if links is not None:
+                    base_pos, base_rot, link_pos, link_rot = (np.asarray(a, np.float32) for a in links)
+                    if node_link.max(initial=-1) >= len(link_pos):
+                        raise ValueError(f"RenderedSampler: hand_visual names link {int(node_link.max())}, the grasp has {len(link_pos)} links")
+                    base = (node_link < 0)
+                    at = np.where(base, 0, node_link)
+                    part.append(node_part)
+                    pos.append(np.where(base[:, None], base_pos.reshape(1, 3), link_pos[at]))
+                    rot.append(np.where(base[:, None, None], base_rot.reshape(1, 3, 3), link_rot[at]))
+                    rgb.append(node_rgb)
+                offset.append(offset[-1] + 1 + (len(node_part) if links is not None else 0))
+        cat = lambda rows, shape, dtype: np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(shape), dtype)  # noqa: E731
+        return dict(inst_part=cat(part, (0,), np.int32), inst_pos=cat(pos, (0, 3), np.float32), inst_rot=cat(rot, (0, 3, 3), np.float32),
+                    inst_rgb=cat(rgb, (0, 3), np.uint8), inst_offset=np.array(offset, np.int32),
+                    cam_pos=np.tile(cam_pos, (K, 1)), cam_rot=np.tile(cam_rot, (K, 1, 1)))
+
+    def occluded_images(self, action_lists, parameters=None, posed=None):
+        """The ``"vision_occluded"`` entries of K action lists: K lists of E images (H, W, 3) uint8 — arrays with ``to_host``, else
+        device tensors —, the object with the posed hand under the reference's vision scene (``occluded_instances`` states what
+        is drawn; the module's docstring states the deviations).  All K * E images come from ONE ``ops.scene_render_posed`` call
+        without the primitive images; ``posed=False`` (None: ``POSED_RENDER_DEFAULT``) writes the posed triangles out with
+        ``ops.pose_parts`` and renders them with ``ops.scene_render`` instead — the same bits.  Every image is rendered on its
+        own, so K lists give what K single calls give bit for bit."""
+        from ... import ops
+        if self.hand_visual is None:
+            raise ValueError("RenderedSampler: occluded_images needs a hand_visual")
+        K, E, D = len(action_lists), len(self.ids), ops.VISION_DEFAULTS
+        t = self.occluded_instances(action_lists, parameters)
+        if K * E == 0:
+            return [[] for _ in range(K)]
+        dev = self.parts.verts.device
+        up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        scene = dict(yfov=D["yfov"], znear=D["znear"], zfar=D["zfar"], width=self.resolution[0], height=self.resolution[1],
+                     lights=D["lights"], ambient=D["ambient"], background=D["background"], want_prim=False)
+        inst = [up(t[name]) for name in ("inst_part", "inst_pos", "inst_rot", "inst_rgb")]
+        if POSED_RENDER_DEFAULT if posed is None else posed:
+            render_posed = ops.scene_render_posed if self.render_posed is None else self.render_posed
+            rgb = render_posed(self.parts, *inst, t["inst_offset"], up(t["cam_pos"]), up(t["cam_rot"]), **scene)["rgb"]
+        else:
+            render_scene = ops.scene_render if self.render_scene is None else self.render_scene
+            m = ops.pose_parts(self.parts, *inst, inst_offset=t["inst_offset"])
+            rgb = render_scene(m["verts"], m["faces"], m["face_rgb"], torch.zeros((0, 3), device=dev), torch.zeros(0, device=dev),
+                               torch.zeros((0, 3), dtype=torch.uint8, device=dev), list(m["face_offset"]), [0] * (K * E + 1),
+                               list(range(K * E)), up(t["cam_pos"]), up(t["cam_rot"]), **scene)["rgb"]
+        images = list(rgb.cpu().numpy()) if self.to_host else list(rgb)
+        return [images[k * E:(k + 1) * E] for k in range(K)]
+
     def sample(self, actions, touch=True, touch_point_cloud=False, vision=False, vision_occluded=False, parameters=None,
                pack_points=None, **unused):
         return self.sample_many([actions], touch=touch, touch_point_cloud=touch_point_cloud, vision=vision,
@@ -189,16 +306,22 @@ class RenderedSampler:
                     pack_points=None, **unused):
         """``[sample(actions) for actions in action_lists]`` with all K * E * 4 views rendered in ONE call — what a greedy step's
         candidate loop asks for.  Every view is rendered on its own, so the results are those of the single calls bit for bit.
-        ``vision``: every result carries the same ``"vision"`` list (``vision_images(parameters)``: the images do not depend on the
+        ``vision_occluded`` (with a ``hand_visual``): result k carries ``occluded_images(action_lists)[k]`` under
+        ``"vision_occluded"``, all K * E images from one more call.  ``vision``: every result carries the same ``"vision"`` list (``vision_images(parameters)``: the images do not depend on the
         actions, so they are rendered once).  ``pack_points`` (None: the instance's): the clouds reach the host as the offsets
         table, one small read, and the rows that exist; the padded buffer is not copied."""
-        if vision_occluded:
+        if vision_occluded and self.hand_visual is None:
             raise NotImplementedError("RenderedSampler: vision_occluded needs the hand model (the reference's objects/hand meshes "
                                       "posed by the grasp), which this package does not carry")
         K, E = len(action_lists), len(self.ids)
         for actions in action_lists:
             if len(actions) != E:
                 raise ValueError(f"RenderedSampler: {len(actions)} actions for {E} loaded objects")
+        if vision_occluded:
+            occluded = self.occluded_images(action_lists, parameters)
+            return [dict(result, vision_occluded=images) for result, images in
+                    zip(self.sample_many(action_lists, touch, touch_point_cloud, vision=vision, parameters=parameters,
+                                         pack_points=pack_points), occluded)]
         if vision:
             images = self.vision_images(parameters)
             return [dict(result, vision=images) for result in self.sample_many(action_lists, touch, touch_point_cloud,

@@ -18,7 +18,10 @@ an angle of a fixed joint is ignored everywhere here.  It is kept as the referen
 Collision boxes.  The URDF's ``<box>`` where a link's collision gives one, otherwise the axis-aligned bounds of the collision mesh's
 vertices under the collision origin: centre and half-extents in the link frame.  A box whose largest extent is below 1 mm (the
 ``end_*`` markers) is dropped: that link carries no box.  This is a simplification of the collision geometry, part of the kinematic
-stand-in (``physics/grasping.py``); pybullet collides with the meshes' convex hulls."""
+stand-in (``physics/grasping.py``); pybullet collides with the meshes' convex hulls.
+
+``HandVisual``: the hand's VISUAL meshes as the reference's vision scene draws them (``simulator/rendering/vision_renderer.py``):
+ten distinct parts and the 21 nodes that place them on the base and on 20 links.  It carries no data either: see ``HandVisual.load``."""
 import math
 import os
 import struct
@@ -31,6 +34,13 @@ TOUCH_CAMERAS = [6, 13, 20, 27]
 COL_PARENT, COL_TYPE, COL_XYZ, COL_ROT, COL_AXIS, COL_LOWER, COL_UPPER, COL_HAS_BOX, COL_BOX_CENTRE, COL_BOX_HALF, TABLE_COLS = \
     0, 1, 2, 5, 14, 17, 18, 19, 20, 23, 26
 MIN_BOX_EXTENT = 1e-3
+# The vision scene's hand (vision_renderer.py:17-18, :94-123, :140-161).  The digit's alpha (175) is not used: it is drawn opaque.
+HAND_COLOUR, DIGIT_COLOUR = (119, 136, 153), (119, 225, 153)
+VISUAL_PARTS = ("0_base", "1_finger", "2_finger", "3_finger", "4_finger", "5_digit", "6_thumb", "7_thumb", "8_thumb", "9_thumb")
+# init_hand's nodes in order, as part indices: the base, three fingers of four segments and a digit, the thumb's four and a digit
+VISUAL_NODE_PARTS = (0,) + (1, 2, 3, 4, 5) * 3 + (6, 7, 8, 9, 5)
+# update_hand's index list: the link whose pose each node after the base takes, as rows of HandModel's table
+VISUAL_NODE_LINKS = (-1, 0, 1, 2, 3, 4, 7, 8, 9, 10, 11, 14, 15, 16, 17, 18, 21, 22, 23, 24, 25)
 _FIELDS = ("names", "parent", "origin_xyz", "origin_rpy", "axis", "revolute", "lower", "upper", "has_box", "box_centre", "box_half", "q0")
 
 
@@ -226,3 +236,66 @@ def poses_as_reference(base_pos, base_rot, link_pos, link_rot):
     for i in range(1, len(link_pos)):
         out.append((tuple(float(x) for x in link_pos[i]), matrix_euler_xyz(np.asarray(link_rot[i], np.float64))))
     return out
+
+
+class HandVisual:
+    """The hand of the reference's vision scene: ``parts``, a list of ``(verts (n, 3) float32, faces (m, 3) int32)`` — the distinct
+    meshes, each once —, and ``nodes``, a list of ``(part, link, rgb)``: ``init_hand``'s 21 nodes in its order, ``link`` the row of
+    ``HandModel``'s table whose pose ``update_hand`` gives the node (-1: the base), ``rgb`` ``HAND_COLOUR`` or, for the four
+    ``5_digit`` nodes, ``DIGIT_COLOUR``.
+
+    The parts are drawn in the link frames ``ops.grasp_close`` returns.  The reference poses them by ``getLinkState(...)[:2]``, the
+    INERTIAL frame; none of the URDF's 29 links gives its ``<inertial>`` an ``<origin>``, so the two frames coincide and no
+    correction is applied.  Faces are taken as stored (no ``add_faces``; the caster is two-sided).  Seen on the reference's files:
+    every finger part's bounds equal its link's collision box in the link frame, except ``6_thumb`` on link 21, whose bounds are the
+    box's turned half a turn about x (it is drawn as the file has it), and ``5_digit``, whose collision mesh is another file."""
+
+    def __init__(self, parts, nodes=None):
+        self.parts = [(np.ascontiguousarray(v, np.float32).reshape(-1, 3), np.ascontiguousarray(f, np.int32).reshape(-1, 3)) for v, f in parts]
+        if nodes is None:
+            nodes = [(part, link, DIGIT_COLOUR if VISUAL_PARTS[part] == "5_digit" else HAND_COLOUR)
+                     for part, link in zip(VISUAL_NODE_PARTS, VISUAL_NODE_LINKS)]
+        self.nodes = [(int(part), int(link), tuple(int(c) for c in rgb)) for part, link, rgb in nodes]
+        for p, (v, f) in enumerate(self.parts):
+            if len(f) and (f.min() < 0 or f.max() >= len(v)):
+                raise ValueError(f"a3vt: HandVisual: part {p} has face indices outside its {len(v)} vertices")
+        if any(not 0 <= part < len(self.parts) or link < -1 or len(rgb) != 3 for part, link, rgb in self.nodes):
+            raise ValueError("a3vt: HandVisual: a node names a part that is not there, a link below -1 or a colour that is not RGB")
+
+    @property
+    def links(self):
+        """The nodes' link rows, in node order (-1: the base)."""
+        return [link for _, link, _ in self.nodes]
+
+    @property
+    def num_faces(self):
+        return sum(len(self.parts[part][1]) for part, _, _ in self.nodes)
+
+    @classmethod
+    def load(cls, path=None):
+        """A ``HandVisual`` from a directory laid out as the reference's ``objects/hand/meshes_obj`` (``<part>.obj`` for the ten
+        names of ``VISUAL_PARTS``, read with ``mesh.load_obj``) or from a ``.npz`` made by ``save``; ``path=None``: what the
+        environment variable ``PTEROTACTYL_HAND_MESHES`` names."""
+        if path is None:
+            path = os.environ.get("PTEROTACTYL_HAND_MESHES")
+            if not path:
+                raise ValueError("a3vt: HandVisual.load: no path given and PTEROTACTYL_HAND_MESHES is not set (the package carries no "
+                                 "hand data: pass the reference's objects/hand/meshes_obj or an .npz made by HandVisual.save)")
+        path = str(path)
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                names = [str(n) for n in z["part_names"]]
+                parts = [(z[f"verts_{n}"], z[f"faces_{n}"]) for n in names]
+                nodes = list(zip(z["node_part"].tolist(), z["node_link"].tolist(), z["node_rgb"].tolist()))
+            return cls(parts, nodes)
+        from ... import mesh
+        return cls([mesh.load_obj(os.path.join(path, name + ".obj")) for name in VISUAL_PARTS])
+
+    def save(self, path):
+        """The parts and nodes as a ``.npz``: arrays only (float32 vertices, int32 faces, the node table)."""
+        names = [VISUAL_PARTS[p] if len(self.parts) == len(VISUAL_PARTS) else f"part{p}" for p in range(len(self.parts))]
+        arrays = {"part_names": np.array(names), "node_part": np.array([n[0] for n in self.nodes], np.int32),
+                  "node_link": np.array([n[1] for n in self.nodes], np.int32), "node_rgb": np.array([n[2] for n in self.nodes], np.uint8)}
+        for name, (v, f) in zip(names, self.parts):
+            arrays[f"verts_{name}"], arrays[f"faces_{name}"] = v, f
+        np.savez_compressed(path, **arrays)

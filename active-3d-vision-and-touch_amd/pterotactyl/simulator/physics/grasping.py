@@ -154,12 +154,16 @@ class KinematicGrasp:
         at = torch.tensor([e * A + a for e, a in placed], dtype=torch.int64, device=pos.device)
         return placed, pos[at], rot[at]
 
-    def grasp_table(self, geometry, ids, num_actions=50, want_q=False, want_blocked_step=False, want_hand_pose=False, want_base=False):
+    def grasp_table(self, geometry, ids, num_actions=50, want_q=False, want_blocked_step=False, want_hand_pose=False, want_base=False,
+                    want_links=False):
         """``geometry``: a mapping ``{id: (verts, faces)}``.  Returns a dict with ``pos`` (E, A, 4, 3) and ``rot`` (E, A, 4, 3, 3)
         float32 and ``present`` (E, A, 4) bool arrays — ``present`` is false, and the frames zero, for all four fingers of a grasp
         that could not be placed — and on request ``q`` (E, A, 16), ``blocked_step`` (E, A, 16) and ``hand_pose`` (E lists of A
         entries: the reference's list of 28 ``(position, xyz-Euler)`` pairs, None for an unplaced grasp) and ``base_pos``
-        (E, A, 3) / ``base_rot`` (E, A, 3, 3) float32, the hand's base poses as ``ops.grasp_close`` got them (``want_base``)."""
+        (E, A, 3) / ``base_rot`` (E, A, 3, 3) float32, the hand's base poses as ``ops.grasp_close`` got them (``want_base``).
+        ``want_links``: also ``link_pos`` (E, A, L, 3) and ``link_rot`` (E, A, L, 3, 3) float32, the world poses of all L links as
+        ``ops.grasp_close`` returns them (zero for an unplaced grasp), and the base poses."""
+        want_base = want_base or want_links
         import time
         E, A = len(ids), int(num_actions)
         verts, faces, offsets, base = [], [], [0], 0
@@ -197,6 +201,9 @@ class KinematicGrasp:
             out["hand_pose"] = [[None] * A for _ in range(E)]
         if want_base:
             out["base_pos"], out["base_rot"] = np.zeros((E, A, 3), np.float32), np.zeros((E, A, 3, 3), np.float32)
+        if want_links:
+            L = self.hand.num_links
+            out["link_pos"], out["link_rot"] = np.zeros((E, A, L, 3), np.float32), np.zeros((E, A, L, 3, 3), np.float32)
         if not placed:
             return out
         G = len(placed)
@@ -211,7 +218,7 @@ class KinematicGrasp:
                                   self.table, self.hand.q0, self.steps)
         host = {name: t.cpu().numpy() for name, t in closed.items()
                 if name in ("frame_pos", "frame_rot") or (name == "q" and want_q) or (name == "blocked_step" and want_blocked_step)
-                or (name in ("link_pos", "link_rot") and want_hand_pose)}
+                or (name in ("link_pos", "link_rot") and (want_hand_pose or want_links))}
         index = tuple(np.array(placed).T)
         out["pos"][index], out["rot"][index], out["present"][index] = host["frame_pos"], host["frame_rot"], True
         if want_q:
@@ -220,6 +227,8 @@ class KinematicGrasp:
             out["blocked_step"][index] = host["blocked_step"]
         if want_base:
             out["base_pos"][index], out["base_rot"][index] = np.array(base_pos).reshape(G, 3), np.array(base_rot).reshape(G, 3, 3)
+        if want_links:
+            out["link_pos"][index], out["link_rot"][index] = host["link_pos"], host["link_rot"]
         if want_hand_pose:
             for g, (e, a) in enumerate(placed):
                 out["hand_pose"][e][a] = poses_as_reference(base_pos[g], base_rot[g], host["link_pos"][g], host["link_rot"][g])
@@ -233,7 +242,27 @@ class GraspFrames(Mapping):
 
     def __init__(self, grasper, geometry, num_actions=50):
         self.grasper, self.geometry, self.num_actions = grasper, geometry, int(num_actions)
-        self._tables = {}
+        self._tables, self._link_tables = {}, {}
+
+    def link_table(self, obj):
+        """``grasp_table(..., want_links=True)`` of one object, made on first touch and kept, as ``table`` keeps its own; it also
+        serves ``table`` (the same call gives the same frames)."""
+        if obj not in self._link_tables:
+            full = self.grasper.grasp_table(self.geometry, [obj], self.num_actions, want_links=True)
+            self._link_tables[obj] = full
+            self._tables.setdefault(obj, {name: full[name] for name in ("pos", "rot", "present")})
+        return self._link_tables[obj]
+
+    def hand_links(self, obj, action):
+        """``(base_pos (3,), base_rot (3, 3), link_pos (L, 3), link_rot (L, 3, 3))`` float32 of a grasp — the hand's base pose and
+        the world poses of all its links after closing, what ``HandVisual``'s nodes are posed by —, or None for a grasp that could
+        not be placed."""
+        if obj not in self.geometry or not 0 <= int(action) < self.num_actions:
+            raise KeyError((obj, action))
+        t, a = self.link_table(obj), int(action)
+        if not t["present"][0, a].any():
+            return None
+        return t["base_pos"][0, a], t["base_rot"][0, a], t["link_pos"][0, a], t["link_rot"][0, a]
 
     def table(self, obj):
         if obj not in self._tables:

@@ -1014,6 +1014,71 @@ int a3vt_scene_render(const float *verts, int V, const int32_t *faces, const uin
 int a3vt_scene_launches(long long *counts /*[2]*/, int reset);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scenes of posed instances: the vision scene with the hand in it (simulator/rendering/vision_renderer.py's update_hand + render;
+ * Sampler.sample's vision_occluded), without writing the posed triangles out.
+ *
+ * THIS IS NOT PYRENDER'S SHADER: it is a3vt_scene_render's ray caster.  The digit's alpha is not blended.  No image of it has been
+ * compared with one of pyrender's.
+ *
+ * An INSTANCE is a part, a rigid pose and a colour.  A part is a face range of a shared template table.  An image's object is an
+ * instance under the identity pose, the Allegro hand 21 more.
+ *   part_verts       [PV][3] fp32 and part_faces [PF][3] int32 (indices into part_verts, already global): the templates
+ *   part_face_offset [P + 1] int32, HOST: part p owns the faces part_face_offset[p] .. part_face_offset[p + 1] - 1
+ *   part_bound       [P][4] fp32, HOST: centre and radius of a sphere that holds every finite vertex the part's faces use
+ *   inst_part        [N] int32, inst_pos [N][3], inst_rot [N][3][3] fp32 (row-major), inst_rgb [N][3] uint8: the instances
+ *   inst_offset      [I + 1] int32, HOST: image i owns the instances inst_offset[i] .. inst_offset[i + 1] - 1; the range may be empty
+ *   cam_pos, cam_rot, yfov, znear, zfar, W, H, lights, L, ambient, background, rgb, depth: exactly a3vt_scene_render's
+ *   prim_inst        [I][H][W] int32 out, or NULL: the global instance index (into inst_part), -1 without a hit
+ *   prim_face        [I][H][W] int32 out, or NULL: the face's index into part_faces, -1 without a hit.  Both or neither.
+ *
+ * The rule.
+ * - A template vertex v of an instance with the pose (R, p) becomes, per row r,
+ *     w_r = fmaf(R[r][0], v.x, fmaf(R[r][1], v.y, fmaf(R[r][2], v.z, p[r]))).
+ *   R is used as given: nothing checks that it is a rotation, so a scale or a shear poses the part as the formula says.
+ * - From w on everything is a3vt_scene_render's rule, word for word and by the same device code (csrc/scene_dev.h): the camera
+ *   transform, the rounded edge functions oriented by vertex index, the plane from the vertices in index order, two-sided, inclusive
+ *   edges, the depth range, Lambert shading of the winner read again by its indices, with the instance's colour.
+ * - Among hits of exactly equal depth the lower (instance index, face index) wins.
+ * - An instance is skipped as a whole if its part id lies outside [0, P) or an entry of its pose is not finite: this is checked on
+ *   the device.  A face with a non-finite posed coordinate, or with an index outside [0, PV), is skipped and changes nothing else.
+ * Consequence: rgb and depth equal, bit for bit, what a3vt_scene_render gives for the triangles a3vt_pose_parts writes out, and
+ * (prim_inst, prim_face) is that call's prim under the materialised numbering.
+ *
+ * Culling is conservative for ANY finite R: an instance is bounded by its part's sphere with the centre posed like a vertex and the
+ * radius scaled by the Frobenius norm of R (>= the largest stretch of R), faces then one by one as in a3vt_scene_render.
+ *
+ * One launch per 128 images on `stream`; a workgroup takes a 16 x 16 tile.  No allocation, no workspace, no host synchronisation, no
+ * atomics: the same bits on every call, and an image does not depend on what else is in the batch.
+ *
+ * a3vt_pose_parts: the materialised formulation, one launch.  Instance n writes, with the same device function, its part's posed
+ * vertices to verts_out[vert_base[n] ..], its part's faces re-based onto them to faces_out[face_base[n] ..] and its colour once per
+ * face to face_rgb_out.  part_vert_offset [P + 1] int32, HOST: part p owns the vertices part_vert_offset[p] .. part_vert_offset[p + 1]
+ * - 1 of part_verts; a face index outside its own part's vertices is written as -1 (a3vt_scene_render skips such a face).  vert_base
+ * and face_base are [N + 1] int32 on the DEVICE, the caller's running sums; an instance whose part id is out of range, or whose
+ * ranges do not have its part's sizes or leave [0, TV) / [0, TF), writes nothing.
+ * a3vt_posed_launches: since the last reset, [0] the a3vt_scene_render_posed calls that were accepted, [1] the kernels they launched,
+ * [2] the kernels of a3vt_pose_parts; returns 3.
+ *
+ * Limits.
+ * - 1 <= I <= 65536, 1 <= P <= 96, 0 <= N <= 16777216, 1 <= W, H <= 2048, 0 <= L <= 8, 0 <= PV, PF, TV, TF <= 268435456.
+ * - The instance tables may be NULL when N == 0, part_verts / part_faces when PV == 0 / PF == 0, lights when L == 0.
+ * - 0 < znear < zfar < infinity; 0 < yfov < pi; ambient finite; part_bound finite with a radius >= 0.
+ * - part_face_offset, part_vert_offset and inst_offset start at >= 0, do not decrease and end at <= PF, <= PV and <= N.
+ * - Pointers to fp32 and int32 are 4-byte aligned; the byte tables need no alignment.
+ * - Anything else, or a missing required pointer, returns non-zero with a message in a3vt_last_error that names the argument and
+ *   its value.  Nothing is launched. */
+int a3vt_scene_render_posed(const float *part_verts, int PV, const int32_t *part_faces, int PF, const int32_t *part_face_offset,
+                            const float *part_bound, int P, const int32_t *inst_part, const float *inst_pos, const float *inst_rot,
+                            const uint8_t *inst_rgb, int N, const int32_t *inst_offset, const float *cam_pos, const float *cam_rot, int I,
+                            float yfov, float znear, float zfar, int W, int H, const float *lights, int L, float ambient,
+                            const uint8_t *background, uint8_t *rgb, float *depth, int32_t *prim_inst, int32_t *prim_face, void *stream);
+int a3vt_pose_parts(const float *part_verts, int PV, const int32_t *part_faces, int PF, const int32_t *part_vert_offset,
+                    const int32_t *part_face_offset, int P, const int32_t *inst_part, const float *inst_pos, const float *inst_rot,
+                    const uint8_t *inst_rgb, int N, const int32_t *vert_base, const int32_t *face_base, float *verts_out, int TV,
+                    int32_t *faces_out, uint8_t *face_rgb_out, int TF, void *stream);
+int a3vt_posed_launches(long long *counts /*[3]*/, int reset);
+
+/* ---------------------------------------------------------------------------------------------
  * The supervised latent policy's value network (policies/supervised/model.py, train.py:119-158), fp32 throughout.
  *
  * The network is a table of at most 16 layers, read on the host and passed to the kernels by value.  Layer l computes
